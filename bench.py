@@ -11,7 +11,11 @@ one-hot labels (BenchmarkDataSetIterator semantics: one fixed random batch, re-f
 ``--variant canonical`` runs standard ResNet-50 instead. Every timed step is a full training
 iteration: forward, backward, (DP) gradient all-reduce, fused RmsProp update of all 25.6M params.
 
-Usage: python bench.py [--gpus N --steps K --warmup W --batch B]
+Usage: python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the JSON line. ``--dump-outputs DIR`` also writes what
+the last timed step left with the caller (DIR/params.npy, DIR/gradients.npy, DIR/score.npy; see dump_outputs).
+``--full`` is where measurements beyond the headline figure belong (none today: the secondary benchmarks are the
+separate tools/bench_*.py programs), so that a plain run stays lean.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N  (one rank per GPU, RCCL), or
 plain ``python bench.py --gpus N`` for the in-process ParallelWrapper (one host thread per GPU, ncclCommInitAll).
 """
@@ -60,7 +64,15 @@ def main():
                          "whenever --gpus N > 1 is run WITHOUT torchrun (the reference's ParallelWrapper design); "
                          "1 forces it (also at N = 1), 0 disables it. Ignored under torchrun (WORLD_SIZE set), which "
                          "runs one process per GPU over torch.distributed's RCCL group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left with the caller (updated parameters, "
+                         "gradient view, score) to DIR/<name>.npy as float32 / float64 (rank 0's replica)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond the headline figure (nothing today; a plain "
+                         "run does only set-up, warm-up, the timed steps and the result line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     under_torchrun = "WORLD_SIZE" in os.environ
     if not under_torchrun and (args.inprocess == 1 or (args.inprocess < 0 and args.gpus > 1)):
         return main_inprocess(args)
@@ -142,6 +154,8 @@ def main():
     ips = B * world * args.steps / elapsed
     final_score = net.score()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(net, args.dump_outputs)
         model_name = "ResNet-50 (DL4J zoo ResNet50 graph)" if args.variant == "dl4j" else "ResNet-50 (canonical)"
         print(json.dumps({
             "metric": "images/sec (whole node) ResNet-50 training at 1/2/4/8 MI355X",
@@ -181,6 +195,30 @@ def memory_report(device):
             "peak_mem_torch_gib": round(torch_peak / g, 2), "peak_mem_engine_gib": round(eng_peak / g, 2),
             "engine_reserved_gib": round(eng_reserved / g, 2), "device_used_gib": round((total - free) / g, 2),
             "device_total_gib": round(total / g, 1)}
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024     # elements kept of each flat vector: 2 x 16 MiB of float32, under the 64 MB cap
+
+
+def dump_outputs(net, out_dir):
+    """``--dump-outputs``: what a caller of the timed path (``net.fit``) holds after the last timed step, as
+    ``out_dir/<name>.npy``: ``params`` (the flat parameter vector after the update), ``gradients`` (the flat gradient
+    view as that step left it), both float32, and ``score`` (float64, shape [1]). A flat vector longer than
+    DUMP_SAMPLE elements is written as a fixed sample of it: the elements at the sorted indices drawn without
+    replacement by ``numpy.random.default_rng(0)``, the same in every run and build, so two dumps compare element
+    for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(net.numParams())
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, size=DUMP_SAMPLE, replace=False)))
+    for name, t in (("params", net.params()), ("gradients", net.getFlattenedGradients())):
+        t = t.detach().reshape(-1)
+        if idx is not None:
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(device="cpu", dtype=torch.float32).numpy())
+    np.save(os.path.join(out_dir, "score.npy"), np.asarray([net.score()], dtype=np.float64))
 
 
 def main_inprocess(args):
@@ -227,6 +265,8 @@ def main_inprocess(args):
     elapsed = time.perf_counter() - t0
     ms = elapsed / args.steps * 1000.0
     ips = B * N * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(net, args.dump_outputs)
     model_name = "ResNet-50 (DL4J zoo ResNet50 graph)" if args.variant == "dl4j" else "ResNet-50 (canonical)"
     print(json.dumps({
         "metric": "images/sec (whole node) ResNet-50 training at 1/2/4/8 MI355X",

@@ -1,19 +1,17 @@
-"""Reference-owned fixtures for the CPU suite: the copies vendored under tests/fixtures (tools/vendor_fixtures.py),
-falling back to the reference tree when a copy is missing. Numeric literals of reference unit tests come from the
-vendored JSON extracts (tests/fixtures/java/<Test>.json), never from parsing Java at test time."""
+"""Reference-owned fixtures for the CPU suite: the copies vendored under tests/fixtures (tools/vendor_fixtures.py);
+nothing outside the repository is read. Numeric literals of reference unit tests come from the vendored JSON
+extracts (tests/fixtures/java/<Test>.json), never from parsing Java at test time."""
 import json
 import os
 
 import torch
 
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures")
-REF = "/root/reference"
 
 
 def path(rel):
-    """Vendored copy of reference file / directory ``rel`` (relative to the reference root), else the original."""
-    v = os.path.join(FIX, rel)
-    return v if os.path.exists(v) else os.path.join(REF, rel)
+    """Vendored copy of reference file / directory ``rel`` (relative to the reference root)."""
+    return os.path.join(FIX, rel)
 
 
 def exists(rel):
