@@ -11,6 +11,7 @@ Weights are re-laid-out once per parameter version (KRSC for forward, flipped CR
 import ctypes
 import weakref
 import contextlib
+import functools
 import os
 
 import numpy as np
@@ -19,7 +20,7 @@ import torch
 
 from ..memory import arena
 
-from . import native, nd4j_kernels, side_stream, tunedb
+from . import autotune, native, nd4j_kernels, side_stream
 from .native import _ptr, _stream, c_int, c_ll, c_void_p
 
 native.register_sig("dl4j_conv_w_relayout", [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
@@ -382,6 +383,8 @@ HALO_VAR = 101       # halo-staged 3x3 / 64-channel kernel (csrc/conv_halo.hip),
 native.register_sig("dl4j_conv_halo_plan", [c_int] * 15 + [ctypes.POINTER(c_int)], restype=c_ll)
 native.register_sig("dl4j_conv_halo", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 +
                     [ctypes.c_float, c_void_p, c_void_p])
+native.register_sig("dl4j_conv_stream", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 +
+                    [ctypes.c_float, c_void_p, c_void_p])
 _HALO_PLANS = {}
 
 
@@ -414,8 +417,6 @@ def _fwd_launch(variant, x, wk, bias, y, geom, beta, ts):
                                 _stream())
         return 1 if (rc == 0 and ts is not None) else rc
     if variant == STREAM_VAR:
-        native.register_sig("dl4j_conv_stream", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 +
-                            [ctypes.c_float, c_void_p, c_void_p])
         rc = lib.dl4j_conv_stream(_dtc(x), _ptr(x), _ptr(wk), _ptr(bias), _ptr(y), *geom, float(beta), _ptr(ts),
                                   _stream())
         return 1 if (rc == 0 and ts is not None) else rc
@@ -436,35 +437,19 @@ def _v3_pick(key, launch, out, make_ts, allow_r2=True):
     DL4J_AMD_CONV_TUNE=0, use the remembered choice or the engine's default tile."""
     v = _V3_CHOICE.get(key)
     if v is not None:
-        return v
-    v = tunedb.lookup("conv_v3", key)
-    if v is not None:
-        _V3_CHOICE[key] = v
-        return v
+        return v                                       # steady state: nothing below is built per launch
     lib = native.load()
     geom = key[1]
-    M, K = geom[0] * geom[13] * geom[14], geom[4]
-    if torch.cuda.is_current_stream_capturing() or os.environ.get("DL4J_AMD_CONV_TUNE", "1") != "1":
-        return lib.dl4j_conv_v3_default_variant(M, K)
     # allow_r2=False: the round-2 kernel lacks an epilogue the caller needs (BN-backward sums), so its lower kernel
     # time would not be the lower step time
-    cands = list(range(lib.dl4j_conv_v3_num_variants())) + [STREAM_VAR, HALO_VAR] + \
-        ([-1] if out.dtype == torch.bfloat16 and allow_r2 else [])
-    scratch = torch.empty_like(out)
-    if key[0] == "bwd_acc":
-        scratch.copy_(out)
-    best, bt = None, None
-    with side_stream.suspended():
-        for var in cands:
-            ts = make_ts(var)
-            if launch(var, scratch, ts) not in (0, 1):
-                continue
-            t = _timed(lambda: launch(var, scratch, ts), reps=tunedb.reps(3))
-            if bt is None or t < bt:
-                best, bt = var, t
-    v = _V3_CHOICE[key] = best if best is not None else -1
-    tunedb.record("conv_v3", key, v)
-    return v
+    r2 = [-1] if out.dtype == torch.bfloat16 and allow_r2 else []
+    scratch = functools.cache(lambda: out.clone() if key[0] == "bwd_acc" else torch.empty_like(out))
+    ts = functools.lru_cache(maxsize=1)(make_ts)       # one statistics buffer per candidate, not per launch
+    return autotune.pick(
+        _V3_CHOICE, key, table="conv_v3", enabled=_tune_on(), inline=True, ok=(0, 1), fallback=-1,
+        candidates=lambda: list(range(lib.dl4j_conv_v3_num_variants())) + [STREAM_VAR, HALO_VAR] + r2,
+        run=lambda var: launch(var, scratch(), ts(var)),
+        default=lambda: lib.dl4j_conv_v3_default_variant(geom[0] * geom[13] * geom[14], geom[4]))[0]
 
 
 def _conv2d_bwd(x, w, dy, stride, pad4, dilation, need_dx, need_dw, need_db, gW=None, gb=None, grads_zeroed=False,
@@ -585,9 +570,7 @@ def _conv2d_bwd(x, w, dy, stride, pad4, dilation, need_dx, need_dw, need_db, gW=
                 dx = dx[:, :, pad4[0]:pad4[0] + H, pad4[2]:pad4[2] + W]
     if not need_dw:
         return dx, None, None
-    directw = gW is not None and gW.dtype == torch.float32 and gW.is_contiguous()
-    directb = gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()
-    if directw and (directb or not need_db) and side_stream.active():
+    if _is_direct(gW) and (_is_direct(gb) or not need_db) and side_stream.active():
         # dW only writes the persistent fp32 gradient views: run it on the overlap stream next to dX
         side_stream.run(lambda: _conv2d_wrw(x, dy, N, H, W, C, K, R, S, OH, OW, stride, pad4, dilation, need_db, gW,
                                             gb, grads_zeroed, pw and gemm_dw), x, dy)
@@ -676,38 +659,38 @@ def _bwd_data_phases(dy, w, plan, N, H, W, C, K, OH, OW, stride, dx_accum, adt):
 def _conv2d_wrw(x, dy, N, H, W, C, K, R, S, OH, OW, stride, pad4, dilation, need_db, gW, gb, grads_zeroed, use_gemm):
     """Weight (and bias) gradient of a channels-last bf16 conv; returns (dW, db), each None when it was written
     straight into the given fp32 view."""
-    lib = native.load()
-    dW_out = db_out = None
+    dWt, direct = _grad_dst(gW, (K, C, R, S), x.device)
+    dbt, directb = _grad_dst(gb, (K,), x.device) if need_db else (None, True)
     if use_gemm:
         # dW[K, C] = dY^T[K, M] . X[M, C], fp32 straight into the flat-gradient view; bias = column sums of dY
         from .gemm import mmul
         M = N * H * W
-        direct = gW is not None and gW.dtype == torch.float32 and gW.is_contiguous()
-        dWt = gW if direct else torch.empty((K, C, R, S), dtype=torch.float32, device=x.device)
         dy_rows = dy.permute(0, 2, 3, 1).reshape(M, K)
         mmul(dy_rows.t(), x.permute(0, 2, 3, 1).reshape(M, C), out=dWt.reshape(K, C))
-        dW_out = None if direct else dWt
         if need_db:
-            directb = gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()
-            dbt = gb.reshape(-1) if directb else torch.empty(K, dtype=torch.float32, device=x.device)
             native.channel_sum(dy_rows, out=dbt)
-            db_out = None if directb else dbt
-        return dW_out, db_out
-    direct = gW is not None and gW.dtype == torch.float32 and gW.is_contiguous()
-    dWt = gW if direct else torch.empty((K, C, R, S), dtype=torch.float32, device=x.device)
-    geom = (N, H, W, C, K, R, S, stride[0], stride[1], pad4[0], pad4[2], dilation[0], dilation[1], OH, OW)
-    v = _wrw_pick(geom, x, dy, dWt, need_db, grads_zeroed) if V3 else ("r2",)
-    if v[0] != "r2":
-        # round-3 engines (tile-engine v3 / halo): per-split fp32 slabs + fixed-order reduce into the DL4J layout
-        db_out = dbt = None
-        if need_db:
-            directb = gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()
-            dbt = gb.reshape(-1) if directb else torch.empty(K, dtype=torch.float32, device=x.device)
-            db_out = None if directb else dbt
-        native._check(_wrw_launch(v, x, dy, dWt, geom, dbt), "conv_wrw_" + v[0])
-        return (None if direct else dWt), db_out
-    return _conv2d_wrw_r2(x, dy, N, H, W, C, K, R, S, OH, OW, stride, pad4, dilation, need_db, gW, gb,
-                          grads_zeroed, dWt, direct)
+    else:
+        geom = (N, H, W, C, K, R, S, stride[0], stride[1], pad4[0], pad4[2], dilation[0], dilation[1], OH, OW)
+        v = _wrw_pick(geom, x, dy, dWt, need_db) if V3 else ("r2",)
+        if v[0] != "r2":
+            # round-3 engines (tile-engine v3 / halo): per-split fp32 slabs + fixed-order reduce into the DL4J layout
+            native._check(_wrw_launch(v, x, dy, dWt, geom, dbt), "conv_wrw_" + v[0])
+        else:
+            _conv2d_wrw_r2(x, dy, geom, dWt, dbt, direct and grads_zeroed, directb and grads_zeroed)
+    return (None if direct else dWt), (None if directb else dbt)
+
+
+def _is_direct(g):
+    """A caller's gradient view the kernels can write straight into (fp32, contiguous)."""
+    return g is not None and g.dtype == torch.float32 and g.is_contiguous()
+
+
+def _grad_dst(g, shape, device):
+    """Destination of a weight / bias gradient: ``(g as shape, True)`` for a caller's fp32 contiguous view, otherwise
+    ``(a fresh fp32 tensor, False)`` that the caller gets back."""
+    if _is_direct(g):
+        return (g if g.shape == shape else g.reshape(shape)), True
+    return torch.empty(shape, dtype=torch.float32, device=device), False
 
 
 _WRW_CHOICE = {}
@@ -756,96 +739,61 @@ def _halo_candidates(geom):
     return out
 
 
-def _wrw_pick(geom, x, dy, dWt, need_db, grads_zeroed):
+def _wrw_pick(geom, x, dy, dWt, need_db):
     """Per-shape weight-gradient kernel: the first eager call times the halo engine (variants x split counts), the
     round-3 tile variants and the round-2 atomic kernel (on scratch outputs, inline on this stream) and keeps the
     fastest. Deterministic mode excludes the round-2 atomic kernel. Under HIP-graph capture: the remembered choice,
     else the first halo candidate, else tile variant 0."""
-    det = deterministic()
+    det, bf16 = deterministic(), x.dtype == torch.bfloat16
     key = (geom, det, x.dtype)
     v = _WRW_CHOICE.get(key)
     if v is not None:
         return v
-    v = tunedb.lookup("conv_wrw", key)
-    if v is not None:
-        _WRW_CHOICE[key] = v
-        return v
-    lib = native.load()
-    halo = _halo_candidates(geom)
-    if torch.cuda.is_current_stream_capturing() or os.environ.get("DL4J_AMD_CONV_TUNE", "1") != "1":
-        return halo[0] if halo else ("v3", 0)
-    N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, OH, OW = geom
-    scratch = torch.empty_like(dWt)
-    sdb = torch.empty(K, dtype=torch.float32, device=dWt.device) if need_db else None
-    r2 = [] if det or x.dtype != torch.bfloat16 else [("r2",)]
-    cands = halo + [("v3", i) for i in range(lib.dl4j_conv_wrw_v3_num_variants())] + r2
-    best, bt = None, None
-    with side_stream.suspended():
-        for c in cands:
-            if c[0] != "r2":
-                def run(c=c):
-                    return _wrw_launch(c, x, dy, scratch, geom, sdb)
-            else:
-                def run():
-                    return _conv2d_wrw_r2(x, dy, N, H, W, C, K, R, S, OH, OW, (sh, sw), (ph, 0, pw, 0), (dh, dw),
-                                          need_db, scratch, sdb, False, scratch, True) and 0
-            if (run() or 0) != 0:
-                continue
-            t = _timed(run, reps=tunedb.reps(3))
-            if bt is None or t < bt:
-                best, bt = c, t
-    v = _WRW_CHOICE[key] = best if best is not None else (("r2",) if x.dtype == torch.bfloat16 else ("v3", 0))
-    tunedb.record("conv_wrw", key, v)
-    return v
+    scratch = functools.cache(lambda: torch.empty_like(dWt))
+    sdb = functools.cache(lambda: torch.empty(geom[4], dtype=torch.float32, device=dWt.device) if need_db else None)
+
+    def run(c):
+        if c[0] != "r2":
+            return _wrw_launch(c, x, dy, scratch(), geom, sdb())
+        _conv2d_wrw_r2(x, dy, geom, scratch(), sdb(), False, False)
+        return 0
+    return autotune.pick(
+        _WRW_CHOICE, key, table="conv_wrw", enabled=_tune_on(), inline=True, run=run,
+        candidates=lambda: _halo_candidates(geom) + [("v3", i) for i in range(
+            native.load().dl4j_conv_wrw_v3_num_variants())] + ([("r2",)] if bf16 and not det else []),
+        default=lambda: (_halo_candidates(geom) or [("v3", 0)])[0],
+        fallback=("r2",) if bf16 else ("v3", 0))[0]
 
 
-def _conv2d_wrw_r2(x, dy, N, H, W, C, K, R, S, OH, OW, stride, pad4, dilation, need_db, gW, gb, grads_zeroed, dWt,
-                   direct):
+def _conv2d_wrw_r2(x, dy, geom, dWt, dbt, w_zeroed, b_zeroed):
     """Round-2 weight-gradient kernel (csrc/conv_igemm.hip): fp32 atomics into a KRSC workspace + permute, or the
-    deterministic per-split slab variant."""
+    deterministic per-split slab variant. dWt ([K][C][R][S]) / dbt (None: no bias gradient) are the fp32
+    destinations; w_zeroed / b_zeroed: the caller guarantees they already hold zeros."""
     lib = native.load()
-    db_out = None
+    N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, OH, OW = geom
     if deterministic():
         # per-split fp32 slabs + fixed-order reduce straight into the DL4J layout: bitwise reproducible
-        dbt = None
-        if need_db:
-            directb = gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()
-            dbt = gb.reshape(-1) if directb else torch.empty(K, dtype=torch.float32, device=x.device)
-        splits = WRW_SPLITS.get((N, H, W, C, K, R, S, tuple(stride)), 0)
+        splits = WRW_SPLITS.get((N, H, W, C, K, R, S, (sh, sw)), 0)
         nf = lib.dl4j_conv_wrw_det_floats(N, C, K, R, S, OH, OW, splits)
         part = _det_scratch(nf, x.device)
-        rc = lib.dl4j_conv_wrw_det(_ptr(x), _ptr(dy), _ptr(dWt), _ptr(dbt), _ptr(part), N, H, W, C, K, R, S,
-                                   stride[0], stride[1], pad4[0], pad4[2], dilation[0], dilation[1], OH, OW, splits,
-                                   _stream())
+        rc = lib.dl4j_conv_wrw_det(_ptr(x), _ptr(dy), _ptr(dWt), _ptr(dbt), _ptr(part), *geom, splits, _stream())
         native._check(rc, "conv_wrw_det")
-        db_out = None
-        if need_db:
-            db_out = None if (gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()) else dbt
-        return (None if direct else dWt), db_out
+        return
     # the kernel accumulates in [K][R][S][C]; identical to DL4J's [K][C][R][S] when R == S == 1
     if R == 1 and S == 1:
         ws = dWt
-        if not (direct and grads_zeroed):
+        if not w_zeroed:
             nd4j_kernels.zero_(ws)
     else:
         ws = _zeroed_wrw_ws(K, R, S, C, x.device)
-    dbt = None
-    if need_db:
-        directb = gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()
-        dbt = gb.reshape(-1) if directb else torch.empty(K, dtype=torch.float32, device=x.device)
-        if not (directb and grads_zeroed):
-            nd4j_kernels.zero_(dbt)
-    splits = _wrw_splits(lib, x, dy, ws, dbt, N, H, W, C, K, R, S, stride, pad4, dilation, OH, OW)
-    rc = lib.dl4j_conv_wrw(_ptr(x), _ptr(dy), _ptr(ws), _ptr(dbt), N, H, W, C, K, R, S, stride[0], stride[1],
-                           pad4[0], pad4[2], dilation[0], dilation[1], OH, OW, splits, _stream())
+    if dbt is not None and not b_zeroed:
+        nd4j_kernels.zero_(dbt)
+    splits = _wrw_splits(x, dy, ws, dbt, geom)
+    rc = lib.dl4j_conv_wrw(_ptr(x), _ptr(dy), _ptr(ws), _ptr(dbt), *geom, splits, _stream())
     native._check(rc, "conv_wrw")
     if ws is not dWt:
         rc = lib.dl4j_conv_wrw_permute(_ptr(ws), _ptr(dWt), K, C, R, S, 1, _stream())
         native._check(rc, "conv_wrw_permute")
-    dW_out = None if direct else dWt
-    if need_db:
-        db_out = None if (gb is not None and gb.dtype == torch.float32 and gb.is_contiguous()) else dbt
-    return dW_out, db_out
 
 
 def _wrw_default_splits(M, K, RSC):
@@ -855,28 +803,27 @@ def _wrw_default_splits(M, K, RSC):
     return max(1, min((384 + tiles - 1) // tiles, maxs)), maxs
 
 
-def _wrw_splits(lib, x, dy, ws, dbt, N, H, W, C, K, R, S, stride, pad4, dilation, OH, OW):
+def _wrw_splits(x, dy, ws, dbt, geom):
     """Per-shape pixel-split count of the weight-gradient kernel. The first eager call of a shape times the heuristic
     count and its neighbours (x0.5, x2, x4: fill vs fp32-atomic epilogue traffic trade differently per shape) on a
     scratch accumulator and keeps the fastest; graph-captured calls use the remembered value (heuristic if none)."""
-    key = (N, H, W, C, K, R, S, tuple(stride))
+    N, H, W, C, K, R, S, sh, sw = geom[:9]
+    key = (N, H, W, C, K, R, S, (sh, sw))
     sp = WRW_SPLITS.get(key)
     if sp is not None:
         return sp
-    if torch.cuda.is_current_stream_capturing() or os.environ.get("DL4J_AMD_CONV_TUNE", "1") != "1":
-        return 0
-    s0, maxs = _wrw_default_splits(N * OH * OW, K, R * S * C)
-    cands = sorted({c for c in (s0 // 2, s0, 2 * s0, 4 * s0) if 1 <= c <= maxs})
-    scratch = torch.zeros_like(ws)
-    sdb = torch.zeros_like(dbt) if dbt is not None else None
+    lib = native.load()
+    scratch = functools.cache(lambda: torch.zeros_like(ws))
+    sdb = functools.cache(lambda: torch.zeros_like(dbt) if dbt is not None else None)
 
-    def run(c):
-        return lambda: native._check(
-            lib.dl4j_conv_wrw(_ptr(x), _ptr(dy), _ptr(scratch), _ptr(sdb), N, H, W, C, K, R, S, stride[0], stride[1],
-                              pad4[0], pad4[2], dilation[0], dilation[1], OH, OW, c, _stream()), "conv_wrw")
-    best = min(cands, key=lambda c: _timed(run(c), reps=3))
-    WRW_SPLITS[key] = best
-    return best
+    def cands():
+        s0, maxs = _wrw_default_splits(N * geom[13] * geom[14], K, R * S * C)
+        return sorted({c for c in (s0 // 2, s0, 2 * s0, 4 * s0) if 1 <= c <= maxs})
+    return autotune.pick(
+        WRW_SPLITS, key, enabled=_tune_on(), probe=False, scale_reps=False,
+        candidates=cands, default=lambda: 0,
+        run=lambda c: native._check(lib.dl4j_conv_wrw(_ptr(x), _ptr(dy), _ptr(scratch()), _ptr(sdb()), *geom, c,
+                                                      _stream()), "conv_wrw"))[0]
 
 
 GEMM_1X1 = os.environ.get("DL4J_AMD_CONV1X1_GEMM", "1") == "1"
@@ -894,30 +841,21 @@ def _is_pointwise(R, S, stride, pad4, dilation):
 _CHOICE = {}
 
 
-def _timed(fn, reps=2):
-    """GPU milliseconds per call with the host enqueue hidden (ops/timing.py)."""
-    from .timing import gpu_time
-    return gpu_time(fn, reps=reps)
+def _tune_on():
+    return os.environ.get("DL4J_AMD_CONV_TUNE", "1") == "1"
 
 
 def _choose(key, run_gemm, run_old):
     c = _CHOICE.get(key)
-    if c is None:
-        if not GEMM_1X1:
-            return False
-        c = tunedb.lookup("conv_1x1", key)
-        if c is not None:
-            _CHOICE[key] = c
-            return c
-        if torch.cuda.is_current_stream_capturing() or os.environ.get("DL4J_AMD_CONV_TUNE", "1") != "1":
-            return True
-        # candidates run inline on this stream: on the overlap stream they would still be writing their scratch
-        # outputs after those are freed, and the main-stream timing events would not cover them
-        with side_stream.suspended():
-            tg, to = _timed(run_gemm, reps=tunedb.reps(2)), _timed(run_old, reps=tunedb.reps(2))
-        c = _CHOICE[key] = tg <= to
-        tunedb.record("conv_1x1", key, c)
-    return c
+    if c is not None:
+        return c
+    if not GEMM_1X1:
+        return False
+    # candidates run inline on this stream: on the overlap stream they would still be writing their scratch
+    # outputs after those are freed, and the main-stream timing events would not cover them. GEMM first: it wins ties
+    return autotune.pick(_CHOICE, key, table="conv_1x1", enabled=_tune_on(), inline=True, probe=False, reps=2,
+                         candidates=lambda: (True, False), run=lambda gemm: run_gemm() if gemm else run_old(),
+                         default=lambda: True)[0]
 
 
 def _pad_ch(t, n, dim=1, cl=False):

@@ -16,11 +16,12 @@ BaseOutputLayer.java:151,178, recurrent/LSTMHelpers.java:206,212,522,616-676, Sa
   allocator.
 """
 import ctypes
+import functools
 import os
 
 import torch
 
-from . import fallback, tunedb
+from . import autotune, fallback, tunedb
 from .dispatch import use_native
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -97,31 +98,19 @@ def _candidates(M, N, K, batch, default):
     return out
 
 
-def _autotune(launch, c_t, M, N, K, batch, default, splits_ok=True, lib=False, zz=None):
-    """First eager call of a problem shape: time every kernel configuration (tile shape x split-K; plus the library
-    GEMM when ``lib``) on a scratch destination and keep the fastest. ``zz``: the call's pre-activation buffer, so
-    every candidate is timed with its epilogue (a forward activation rewrites it, dgelu reads it). Never runs while a
-    HIP graph is being captured; the cost-model plan is used there."""
-    from .timing import gpu_time
-    tmp = torch.empty_strided(c_t.size(), c_t.stride(), dtype=c_t.dtype, device=c_t.device)
-    best, best_t = default, None
-    log = [] if _TUNE_LOG else None
-    for cand in _candidates(M, N, K, batch, default) + ([LIB_CFG] if lib else []):
-        if cand[1] > 1 and not splits_ok:
-            continue
-        if launch(cand[0], cand[1], tmp, 0.0, zz) != 0:
-            continue
-        # GPU-side time (stream parked during the enqueue): small GEMMs are shorter than the host launch path
-        t = gpu_time(lambda: launch(cand[0], cand[1], tmp, 0.0, zz), reps=tunedb.reps(3), warmup=0)
-        if log is not None:
-            log.append((t, cand))
-        if best_t is None or t < best_t:
-            best, best_t = cand, t
-    if log:
-        log.sort()
-        print(f"[gemm-tune] M={M} N={N} K={K} batch={batch} out={c_t.dtype} zz={zz is not None} best={best} " +
-              " ".join(f"{c[0]}/{c[1]}:{t * 1e3:.1f}" for t, c in log[:8]), flush=True)
-    return best
+def _autotune(key, launch, c_t, candidates, default, zz=None):
+    """``(cfg, from_db)`` for a problem key: the first eager call times every candidate configuration (tile shape x
+    split-K, plus the library GEMM where it applies) on a scratch destination shaped like ``c_t`` and keeps the
+    fastest. ``zz``: the call's pre-activation buffer, so every candidate is timed with its epilogue (a forward
+    activation rewrites it, dgelu reads it). ``default()`` (the cost-model plan, first among the candidates) is used
+    while a HIP graph is being captured, with DL4J_AMD_GEMM_TUNE=0, and when every candidate refuses."""
+    tmp = functools.cache(lambda: torch.empty_strided(c_t.size(), c_t.stride(), dtype=c_t.dtype, device=c_t.device))
+
+    def log(best, times):
+        print(f"[gemm-tune] M={key[0]} N={key[1]} K={key[2]} batch={key[3]} out={c_t.dtype} zz={zz is not None} "
+              f"best={best} " + " ".join(f"{c[0]}/{c[1]}:{t * 1e3:.1f}" for t, c in sorted(times)[:8]), flush=True)
+    return autotune.pick(_TUNED, key, table="gemm", enabled=_TUNE, warmup=0, candidates=candidates, default=default,
+                         run=lambda c: launch(c[0], c[1], tmp(), 0.0, zz), log=log if _TUNE_LOG else None)
 
 
 def _p(t):
@@ -344,26 +333,18 @@ def mmul(a, b, out=None, bias=None, bias_dim=1, act=None, alpha=1.0, beta=0.0, o
             if swap or batch != 1:
                 raise ValueError("GEMM BatchNorm statistics need a row-major, unbatched destination")
             kst = key + ("stats", stats_tag)
-            cfg = (_FORCE_CFG[0], 1) if _FORCE_CFG is not None else _TUNED.get(kst)
-            from_db = False
+            dflt = (4, 1) if K % 64 == 0 else (2, 1)
+            cfg, from_db = (_FORCE_CFG[0], 1) if _FORCE_CFG is not None else _TUNED.get(kst), False
             if cfg is None:
-                cfg = tunedb.lookup("gemm", kst)
-                if cfg is not None:
-                    _TUNED[kst] = cfg
-                    from_db = True
-                else:
-                    cfg = (4, 1) if K % 64 == 0 else (2, 1)
-                    if _TUNE and not torch.cuda.is_current_stream_capturing():
-                        cfg = _autotune(lambda c_, s_, d_, bt_, zz_: launch(c_, s_, d_, bt_, zz_, stats), c_t, Mx, Nx,
-                                        K, batch, cfg, splits_ok=False)
-                        _TUNED[kst] = cfg
-                        tunedb.record("gemm", kst, cfg)
+                # the statistics epilogue runs unsplit (it is launched with splits = 1 below)
+                cfg, from_db = _autotune(kst, lambda c_, s_, d_, bt_, zz_: launch(c_, s_, d_, bt_, zz_, stats), c_t,
+                                         lambda: [c for c in _candidates(Mx, Nx, K, batch, dflt) if c[1] == 1],
+                                         lambda: dflt)
             rc = launch(cfg[0], 1, c_t, float(beta), z, stats)
             if rc != 0 and from_db:
                 # a recorded choice this build refuses: drop it and take the planner's default configuration
                 tunedb.forget("gemm", kst)
-                cfg = (4, 1) if K % 64 == 0 else (2, 1)
-                _TUNED[kst] = cfg
+                cfg = _TUNED[kst] = dflt
                 rc = launch(cfg[0], 1, c_t, float(beta), z, stats)
             if rc != 0:
                 raise RuntimeError(f"HIP gemm (stats) failed with code {rc}")
@@ -378,22 +359,11 @@ def mmul(a, b, out=None, bias=None, bias_dim=1, act=None, alpha=1.0, beta=0.0, o
 
             def launch(cfg, sp, dst, bt, zz, ts=None):
                 return libmm(dst, bt) if cfg == LIB_CFG[0] else kern(cfg, sp, dst, bt, zz, ts)
-        from_db = False
-        if _FORCE_CFG is not None:
-            cfg = _FORCE_CFG
-        else:
-            cfg = _TUNED.get(key)
-            if cfg is None:
-                cfg = tunedb.lookup("gemm", key)
-                if cfg is not None:
-                    _TUNED[key] = cfg
-                    from_db = True
-                else:
-                    cfg = _plan(lib, Mx, Nx, K, batch)
-                    if _TUNE and not torch.cuda.is_current_stream_capturing():
-                        cfg = _autotune(launch, c_t, Mx, Nx, K, batch, cfg, lib=libmm is not None, zz=z)
-                        _TUNED[key] = cfg
-                        tunedb.record("gemm", key, cfg)
+        cfg, from_db = _FORCE_CFG if _FORCE_CFG is not None else _TUNED.get(key), False
+        if cfg is None:
+            plan = functools.cache(lambda: _plan(lib, Mx, Nx, K, batch))
+            cfg, from_db = _autotune(key, launch, c_t, lambda: _candidates(Mx, Nx, K, batch, plan()) +
+                                     ([LIB_CFG] if libmm is not None else []), plan, zz=z)
         if cfg == LIB_CFG:
             fallback.record("gemm", "library GEMM (hipBLASLt) picked by the autotuner (DL4J_AMD_GEMM_LIB=1)")
         rc = launch(cfg[0], cfg[1], c_t, float(beta), z)
@@ -431,14 +401,14 @@ def mmul(a, b, out=None, bias=None, bias_dim=1, act=None, alpha=1.0, beta=0.0, o
                        z is not None)
                 use_lib = _TUNED.get(k32) if _F32_FORCE is None else _F32_FORCE
                 if use_lib is None:
-                    use_lib = False
-                    if _TUNE and not torch.cuda.is_current_stream_capturing():
-                        from .timing import gpu_time
-                        tmp = torch.empty_strided(c_t.size(), c_t.stride(), dtype=c_t.dtype, device=c_t.device)
-                        if simple(tmp, 0.0) == 0 and libmm(tmp, 0.0) == 0:
-                            use_lib = gpu_time(lambda: libmm(tmp, 0.0), reps=3, warmup=0) < \
-                                gpu_time(lambda: simple(tmp, 0.0), reps=3, warmup=0)
-                        _TUNED[k32] = use_lib
+                    tmp = functools.cache(lambda: torch.empty_strided(c_t.size(), c_t.stride(), dtype=c_t.dtype,
+                                                                      device=c_t.device))
+                    # timed only when both launch; the exact kernel first: the library must be strictly faster
+                    both = lambda: simple(tmp(), 0.0) == 0 and libmm(tmp(), 0.0) == 0   # noqa: E731
+                    use_lib = autotune.pick(
+                        _TUNED, k32, enabled=_TUNE, warmup=0, scale_reps=False, probe=False, fallback=False,
+                        candidates=lambda: (False, True) if both() else (), default=lambda: False,
+                        run=lambda use: (libmm if use else simple)(tmp(), 0.0))[0]
                 if use_lib:
                     run = libmm
                     fallback.record("gemm", "fp32 library GEMM (hipBLASLt) picked by the autotuner")

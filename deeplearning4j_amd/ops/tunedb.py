@@ -1,7 +1,8 @@
 """Persistent kernel-choice database (the framework's perf-db, in the role of MIOpen's find-db / hipBLASLt's tuning
 files): the autotuners' per-shape decisions — GEMM tile configuration x split-K (ops/gemm.py), convolution tile
 variant, weight-gradient engine, 1x1-conv GEMM-vs-implicit-GEMM (ops/conv_native.py) — keyed by (table, problem
-key) for one GPU architecture.
+key) for one GPU architecture. Its one consumer is ``ops/autotune.py``: ``autotune.pick`` looks a key up before it
+times anything and records what it decided; every chooser of those two modules is a call of it.
 
 * Lookup: ``deeplearning4j_amd/ops/tunedb/<arch>.json`` (or ``DL4J_AMD_TUNE_DB``) is read once; a shape found there
   is not re-timed, so a fresh process takes the recorded choice at its first call (no tuning pass in the first
@@ -14,7 +15,8 @@ key) for one GPU architecture.
 * The file also records the compute-unit count of the device it was timed on; on a device of the same architecture
   with another CU count (a partitioned or binned part) the decisions are ignored and the autotuners re-time.
 * A recorded choice a kernel refuses at launch (non-zero return code) is dropped with ``forget`` and the caller
-  falls back to its planner / autotuner instead of failing.
+  falls back to its planner / autotuner instead of failing (``pick`` reports ``from_db`` for this; ``gemm.mmul`` is
+  the caller that does it so far, the conv tables do not).
 """
 import atexit
 import json

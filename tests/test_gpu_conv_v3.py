@@ -274,3 +274,68 @@ def test_conv_tile_statistics_feed_batchnorm(cuda, N, H):
     ref = torch.relu((yf - mean.view(1, -1, 1, 1)) * torch.rsqrt(var + 1e-5).view(1, -1, 1, 1) * gamma.view(1, -1, 1, 1)
                      + beta.view(1, -1, 1, 1))
     _close(out, ref, 3e-2)
+
+
+def test_tuned_choices_are_found_under_their_literal_database_keys(cuda, tmp_path, monkeypatch):
+    """The key layouts of the shipped kernel-choice database, pinned: a database written with LITERAL keys (never
+    computed by the code under test) must serve a 3x3 forward, backward-data and weight-gradient conv, a 1x1 forward
+    conv (and the GEMM it runs as) and a plain mmul without anything being timed; each chooser's memo then holds the
+    database's value under the literal key and every result matches the fp32 torch reference."""
+    import json
+    from deeplearning4j_amd.ops import gemm, timing, tunedb
+    bf16 = torch.bfloat16
+    geom = (4, 14, 14, 64, 64, 3, 3, 1, 1, 1, 1, 1, 1, 14, 14)       # N,H,W,C,K,R,S,sh,sw,pt,pl,dh,dw,OH,OW
+    k_fwd = ("fwd", geom, True, False, bf16)
+    k_bwd = ("bwd", geom, bf16, False)                                # the transposed conv has the same geometry here
+    k_wrw = (geom, False, bf16)
+    k_1x1 = ("fwd", (2, 64, 11, 13), (256, 64, 1, 1), True, False, bf16)
+    k_1x1_gemm = (286, 256, 64, 1, 1, 1, True, True, True, True)      # the 1x1 conv as Y[NHW, K] = X[NHW, C] . W^T
+    k_gemm = (256, 128, 64, 1, 1, 1, True, False, True, True)
+    lib = gemm._lib()
+    plan_1x1, plan = gemm._plan(lib, 286, 256, 64, 1), gemm._plan(lib, 256, 128, 64, 1)   # the build's defaults
+    db = tmp_path / "db.json"
+    db.write_text(json.dumps({"version": 2, "arch": "gfx950", "tables": {
+        "conv_v3": {repr(k_fwd): 0, repr(k_bwd): 0},
+        "conv_wrw": {repr(k_wrw): ["v3", 0]},
+        "conv_1x1": {repr(k_1x1): True},
+        "gemm": {repr(k_1x1_gemm): list(plan_1x1), repr(k_gemm): list(plan)}}}))
+    monkeypatch.setenv("DL4J_AMD_TUNE_DB", str(db))
+    monkeypatch.delenv("DL4J_AMD_TUNE_DB_SKIP", raising=False)
+    monkeypatch.delenv("DL4J_AMD_DETERMINISTIC", raising=False)
+    monkeypatch.setattr(tunedb, "_db", None)
+    monkeypatch.setattr(tunedb, "_path_used", None)
+    for mod, name in ((conv_native, "_V3_CHOICE"), (conv_native, "_WRW_CHOICE"), (conv_native, "_CHOICE"),
+                      (gemm, "_TUNED")):
+        monkeypatch.setattr(mod, name, {})
+    monkeypatch.setattr(timing, "gpu_time", lambda *a, **k: pytest.fail("a choice in the database was re-timed"))
+
+    case = (4, 64, 14, 14, 64, 3, 3, (1, 1), (1, 1, 1, 1), (1, 1))
+    _, _, _, _, _, _, _, stride, pad4, dil = case
+    x, w, b = _data(case)
+    xr, wr = x.float().requires_grad_(True), w.float().requires_grad_(True)
+    yr = _ref(xr, wr, b, stride, pad4, dil)
+    g = torch.Generator().manual_seed(5)
+    dy = torch.randn(yr.shape, generator=g).cuda().bfloat16().contiguous(memory_format=torch.channels_last)
+    yr.backward(dy.float())
+    conv_native.bump_version()
+    y = conv_native.conv2d_fwd(x, w, b, stride, pad4, dil)
+    dx, _, _ = conv_native.conv2d_bwd(x, w, dy, stride, pad4, dil, True, False, False)
+    _, dW, db_ = conv_native.conv2d_bwd(x, w, dy, stride, pad4, dil, False, True, True)
+    case1 = (2, 64, 11, 13, 256, 1, 1, (1, 1), (0, 0, 0, 0), (1, 1))
+    x1, w1, b1 = _data(case1)
+    y1 = conv_native.conv2d_fwd(x1, w1, b1, (1, 1), (0, 0, 0, 0), (1, 1))
+    ga = torch.randn(256, 64, generator=g).cuda().bfloat16()
+    gb = torch.randn(64, 128, generator=g).cuda().bfloat16()
+    gc = gemm.mmul(ga, gb)
+    torch.cuda.synchronize()
+
+    assert conv_native._V3_CHOICE == {k_fwd: 0, k_bwd: 0}
+    assert conv_native._WRW_CHOICE == {k_wrw: ("v3", 0)}
+    assert conv_native._CHOICE == {k_1x1: True}
+    assert gemm._TUNED == {k_1x1_gemm: plan_1x1, k_gemm: plan}
+    _close(y, yr, 2e-2)
+    _close(dx, xr.grad, 2e-2)
+    _close(dW, wr.grad, 1e-2)
+    _close(db_, dy.float().sum(dim=(0, 2, 3)), 1e-3)
+    _close(y1, _ref(x1, w1, b1, (1, 1), (0, 0, 0, 0), (1, 1)), 2e-2)
+    _close(gc, ga.float() @ gb.float(), 2e-2)

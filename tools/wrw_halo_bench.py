@@ -42,8 +42,7 @@ def main():
         gW = torch.zeros(K, C, R, S, device="cuda")
         gb = torch.zeros(K, device="cuda")
         geom = (N, H, W, C, K, R, S, st[0], st[1], pad[0], pad[2], dil[0], dil[1], OH, OW)
-        t2 = timeit(lambda: conv_native._conv2d_wrw_r2(x, dy, N, H, W, C, K, R, S, OH, OW, st, pad, dil, True, gW, gb,
-                                                       False, gW, True), a.reps)
+        t2 = timeit(lambda: conv_native._conv2d_wrw_r2(x, dy, geom, gW, gb, False, False), a.reps)
         tv = min(timeit(lambda v=v: conv_native._wrw_v3_launch(v, x, dy, gW, geom, gb), a.reps) for v in range(nv))
         tg = float("inf")
         if R == 1 and S == 1 and st == (1, 1) and not any(pad):
