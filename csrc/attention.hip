@@ -85,13 +85,59 @@ __device__ __forceinline__ float wsum16(float v) {
   return v + __shfl_xor(v, 32, 64);
 }
 
+// ------------------------------------------------------------------------------------------------ dropout mask
+// Attention-probability dropout (DROP = true instances of the three kernels below; the DROP = false instances are
+// the kernels without it, no run-time branch). The keep mask is never stored: it is a pure function of
+// (seed, offset, b*H + h, q, k), independent of tiling, NB, head size and kernel, regenerated in the backward.
+//   * one Philox-4x32-10 call covers the 4x4 (q, k) tile: counter {k >> 2, q >> 2, b*H + h, low 32 bits of offset},
+//     key {seed low, seed high};
+//   * element (q & 3, k & 3) is byte (k & 3) of result word (q & 3); it is kept iff byte >= thr, thr = round(drop*256);
+//   * kept probabilities are rescaled by 1 / keep_eff, keep_eff = 1 - thr/256 (the rate actually drawn).
+// A lane of the forward / dQ kernels holds one query x 4 consecutive keys per 16x16 accumulator tile (one word, four
+// bytes), a lane of the dK/dV kernel one key x 4 consecutive queries (one byte of each word): one call per lane per
+// tile in all three. offset is read from device memory (the layer's step counter), so graph replays draw new masks.
+// ops/transformer_native.py::attn_dropout_keep is the host oracle of this mapping.
+struct DropArgs {
+  unsigned long long seed;
+  const long long* offset;
+  unsigned thr;
+  float inv_keep;
+};
+__device__ __forceinline__ uint4 attn_drop_tile(unsigned long long seed, unsigned off, unsigned bh, unsigned q4,
+                                                unsigned k4) {
+  return philox4x32_10(make_uint4(k4, q4, bh, off), make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+}
+__device__ __forceinline__ unsigned attn_drop_word(const uint4& t, int qi) {
+  return qi == 0 ? t.x : (qi == 1 ? t.y : (qi == 2 ? t.z : t.w));
+}
+__device__ __forceinline__ bool attn_drop_keep(unsigned word, int ki, unsigned thr) {
+  return ((word >> (8 * ki)) & 0xffu) >= thr;
+}
+
+// test / debug only: the keep mask [B*H, T, T] as uint8 (1 = kept), one thread per element
+__global__ void __launch_bounds__(256) attn_drop_mask_kernel(unsigned char* __restrict__ out, long long total, int T,
+                                                             DropArgs da) {
+  const unsigned off = (unsigned)da.offset[0];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int k = (int)(i % T);
+    const long long r = i / T;
+    const int q = (int)(r % T);
+    const unsigned bh = (unsigned)(r / T);
+    const uint4 t = attn_drop_tile(da.seed, off, bh, (unsigned)q >> 2, (unsigned)k >> 2);
+    out[i] = attn_drop_keep(attn_drop_word(t, q & 3), k & 3, da.thr) ? 1 : 0;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 // NB key blocks are staged per round (NB = 2 for D = 64: a T = 128 sequence is one round, one global round trip and
 // one barrier pair instead of two); every thread issues all of the round's K and V loads before any LDS store.
-template <int D, typename hb, int NB>
+// DROP: O = (P o D) V with the running max / sum and lse from the undropped scores (lse is that of the DROP = false
+// kernel); dropped probabilities are zeroed before the PV product and 1/keep_eff is folded into the final 1/l.
+template <int D, typename hb, int NB, bool DROP = false>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const hb* __restrict__ qkv, const float* __restrict__ mask,
                                                        hb* __restrict__ out, float* __restrict__ lse, int T, int H,
-                                                       float scale2, int causal) {
+                                                       float scale2, int causal, DropArgs da) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = NB * BLK + 8;
   constexpr int CPR = D / 8, PER = BLK * CPR / 256;              // 16-byte chunks per row / per thread per block
@@ -111,6 +157,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const hb* __restrict__ qk
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) acc[dt] = f4_t{0.f, 0.f, 0.f, 0.f};
   float m = kNegInf, l = 0.f;
+  unsigned drop_off = 0;
+  if constexpr (DROP) drop_off = (unsigned)da.offset[0];
   const float* mrow = mask ? mask + (long long)b * T : nullptr;
   const int nkb = causal ? min((blockIdx.x * BLK + BLK + BLK - 1) / BLK, (T + BLK - 1) / BLK) : (T + BLK - 1) / BLK;
   for (int kb0 = 0; kb0 < nkb; kb0 += NB) {
@@ -175,6 +223,17 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const hb* __restrict__ qk
         }
       l = l * alpha + wsum16(ps);
       m = mn;
+      if constexpr (DROP) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+          const unsigned w = attn_drop_word(
+              attn_drop_tile(da.seed, drop_off, (unsigned)bh, (unsigned)q >> 2, (unsigned)(kb * 16 + mt * 4 + hgrp)),
+              q & 3);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (!attn_drop_keep(w, r, da.thr)) s[mt][r] = 0.f;
+        }
+      }
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) acc[dt] *= alpha;
 #pragma unroll
@@ -187,7 +246,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const hb* __restrict__ qk
     }
   }
   if (q < T) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    float inv = l > 0.f ? 1.f / l : 0.f;
+    if constexpr (DROP) inv *= da.inv_keep;
     hb* orow = out + ((long long)b * T + q) * E + h * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -219,12 +279,13 @@ __global__ void __launch_bounds__(256) attn_bwd_pre_kernel(const hb* __restrict_
   dq_dot[i] = s;
 }
 
-// dQ per query block (forward orientation: query on the lane)
-template <int D, typename hb>
+// dQ per query block (forward orientation: query on the lane). DROP: dS = P o (D o dP - Delta), D in {0, 1/keep_eff}.
+template <int D, typename hb, bool DROP = false>
 __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const hb* __restrict__ qkv, const hb* __restrict__ dout,
                                                           const float* __restrict__ mask, const float* __restrict__ lse,
                                                           const float* __restrict__ dq_dot, hb* __restrict__ dqkv,
-                                                          int T, int H, float scale2, float scale, int causal) {
+                                                          int T, int H, float scale2, float scale, int causal,
+                                                          DropArgs da) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDT = BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Ks[BLK * LDK];
@@ -245,6 +306,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const hb* __restrict__
   }
   const float l2 = lse[(long long)bh * T + qc];
   const float dd = dq_dot[(long long)bh * T + qc];
+  unsigned drop_off = 0;
+  if constexpr (DROP) drop_off = (unsigned)da.offset[0];
   f4_t acc[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) acc[dt] = f4_t{0.f, 0.f, 0.f, 0.f};
@@ -268,15 +331,23 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const hb* __restrict__
       }
     }
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
+    for (int mt = 0; mt < 4; ++mt) {
+      unsigned w = 0;
+      if constexpr (DROP)
+        w = attn_drop_word(
+            attn_drop_tile(da.seed, drop_off, (unsigned)bh, (unsigned)q >> 2, (unsigned)(kb * 16 + mt * 4 + hgrp)),
+            q & 3);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kb * BLK + mt * 16 + hgrp * 4 + r;
         bool ok = key < T && q < T && (!causal || key <= q);
         if (ok && mrow) ok = mrow[key] != 0.f;
         const float p = ok ? exp2f(s[mt][r] * scale2 - l2) : 0.f;
-        s[mt][r] = p * (dp[mt][r] - dd);                       // dS (w.r.t. the scaled scores)
+        float dpv = dp[mt][r];
+        if constexpr (DROP) dpv = attn_drop_keep(w, r, da.thr) ? dpv * da.inv_keep : 0.f;
+        s[mt][r] = p * (dpv - dd);                             // dS (w.r.t. the scaled scores)
       }
+    }
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
       const V8<hb> sb = pack2<hb>(s[2 * k2], s[2 * k2 + 1]);
@@ -295,15 +366,16 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const hb* __restrict__
   }
 }
 
-// dK, dV per key block (key on the lane)
-template <int D, typename hb>
+// dK, dV per key block (key on the lane). DROP: dV = (P o D)^T dO (dropped P zeroed, 1/keep_eff folded into the final
+// store), dS as in the dQ kernel.
+template <int D, typename hb, bool DROP = false>
 __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const hb* __restrict__ qkv,
                                                             const hb* __restrict__ dout,
                                                             const float* __restrict__ mask,
                                                             const float* __restrict__ lse,
                                                             const float* __restrict__ dq_dot,
                                                             hb* __restrict__ dqkv, int T, int H, float scale2,
-                                                            float scale, int causal) {
+                                                            float scale, int causal, DropArgs da) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDQ = D + 8, LDT = BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Qs[BLK * LDQ];
@@ -319,6 +391,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const hb* __restrict
   const hb* dbase = dout + (long long)b * T * E;
   const int key = blockIdx.x * BLK + wave * 16 + col;
   const int kc = min(key, T - 1);
+  unsigned drop_off = 0;
+  if constexpr (DROP) drop_off = (unsigned)da.offset[0];
   bool kvalid = key < T;
   if (kvalid && mask) kvalid = mask[(long long)b * T + key] != 0.f;
   V8<hb> kf[KS], vf[KS];
@@ -357,15 +431,26 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const hb* __restrict
     }
     f4_t ds[4];
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
+    for (int mt = 0; mt < 4; ++mt) {
+      uint4 dtile = make_uint4(0, 0, 0, 0);
+      if constexpr (DROP)
+        dtile = attn_drop_tile(da.seed, drop_off, (unsigned)bh, (unsigned)(qb * 16 + mt * 4 + hgrp),
+                               (unsigned)key >> 2);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qi = mt * 16 + hgrp * 4 + r, q = qb * BLK + qi;
         const bool ok = kvalid && q < T && (!causal || key <= q);
         const float p = ok ? exp2f(s[mt][r] * scale2 - Ls[qi]) : 0.f;
-        s[mt][r] = p;
-        ds[mt][r] = p * (dp[mt][r] - Dd[qi]);
+        if constexpr (DROP) {
+          const bool keep = attn_drop_keep(attn_drop_word(dtile, r), key & 3, da.thr);
+          s[mt][r] = keep ? p : 0.f;
+          ds[mt][r] = p * ((keep ? dp[mt][r] * da.inv_keep : 0.f) - Dd[qi]);
+        } else {
+          s[mt][r] = p;
+          ds[mt][r] = p * (dp[mt][r] - Dd[qi]);
+        }
       }
+    }
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
       const V8<hb> pb = pack2<hb>(s[2 * k2], s[2 * k2 + 1]);
@@ -383,6 +468,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const hb* __restrict
     for (int dt = 0; dt < DT; ++dt) {
       const V4<hb> kv{tobf<hb>(dk[dt][0] * scale), tobf<hb>(dk[dt][1] * scale), tobf<hb>(dk[dt][2] * scale),
                         tobf<hb>(dk[dt][3] * scale)};
+      if constexpr (DROP) dv[dt] *= da.inv_keep;
       const V4<hb> vv{tobf<hb>(dv[dt][0]), tobf<hb>(dv[dt][1]), tobf<hb>(dv[dt][2]), tobf<hb>(dv[dt][3])};
       *reinterpret_cast<V4<hb>*>(dst + E + dt * 16 + hgrp * 4) = kv;
       *reinterpret_cast<V4<hb>*>(dst + 2 * E + dt * 16 + hgrp * 4) = vv;
@@ -391,53 +477,110 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const hb* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ launch
-template <int D, typename hb>
+template <int D, typename hb, bool DROP>
 static int fwd_l(const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H, float scale,
-                 int causal, hipStream_t s) {
+                 int causal, DropArgs da, hipStream_t s) {
   const dim3 grid((T + BLK - 1) / BLK, B * H);
   constexpr int NB = D == 64 ? 2 : 1;
-  hipLaunchKernelGGL((attn_fwd_kernel<D, hb, NB>), grid, dim3(256), 0, s, (const hb*)qkv, mask, (hb*)out, lse, T, H,
-                     scale * kLog2e, causal);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, hb, NB, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, mask, (hb*)out, lse, T,
+                     H, scale * kLog2e, causal, da);
   return (int)hipGetLastError();
 }
 
-template <int D, typename hb>
+template <int D, typename hb, bool DROP>
 static int bwd_l(const void* qkv, const void* out, const void* dout, const float* mask, const float* lse,
-                 float* dq_dot, void* dqkv, int B, int T, int H, float scale, int causal, hipStream_t s) {
+                 float* dq_dot, void* dqkv, int B, int T, int H, float scale, int causal, DropArgs da, hipStream_t s) {
   const long long n = (long long)B * H * T;
   hipLaunchKernelGGL((attn_bwd_pre_kernel<D, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const hb*)out,
                      (const hb*)dout, dq_dot, B, T, H);
   const dim3 grid((T + BLK - 1) / BLK, B * H);
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout, mask, lse,
-                     dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout, mask, lse,
-                     dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal);
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout, mask,
+                     lse, dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal, da);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout, mask,
+                     lse, dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal, da);
   return (int)hipGetLastError();
+}
+
+template <bool DROP>
+static int fwd_dispatch(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H, int D,
+                        float scale, int causal, DropArgs da, hipStream_t s) {
+  if (B < 1 || T < 1 || H < 1 || (dt != 1 && dt != 2)) return -1;
+  if (D == 64) return dt == 1 ? fwd_l<64, __bf16, DROP>(qkv, mask, out, lse, B, T, H, scale, causal, da, s)
+                              : fwd_l<64, _Float16, DROP>(qkv, mask, out, lse, B, T, H, scale, causal, da, s);
+  if (D == 128) return dt == 1 ? fwd_l<128, __bf16, DROP>(qkv, mask, out, lse, B, T, H, scale, causal, da, s)
+                               : fwd_l<128, _Float16, DROP>(qkv, mask, out, lse, B, T, H, scale, causal, da, s);
+  return -1;
+}
+
+template <bool DROP>
+static int bwd_dispatch(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                        const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int D, float scale,
+                        int causal, DropArgs da, hipStream_t s) {
+  if (B < 1 || T < 1 || H < 1 || (dt != 1 && dt != 2)) return -1;
+#define ATTN_BWD(DD, HB) bwd_l<DD, HB, DROP>(qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, scale, causal, da, s)
+  if (D == 64) return dt == 1 ? ATTN_BWD(64, __bf16) : ATTN_BWD(64, _Float16);
+  if (D == 128) return dt == 1 ? ATTN_BWD(128, __bf16) : ATTN_BWD(128, _Float16);
+#undef ATTN_BWD
+  return -1;
+}
+
+// drop in [0, 1) -> thr = round(drop * 256) clamped to [0, 255]; false when drop is out of range
+static bool drop_args(float drop, unsigned long long seed, const long long* offset, DropArgs* da) {
+  if (!(drop >= 0.f && drop < 1.f) || !offset) return false;
+  int thr = (int)(drop * 256.f + 0.5f);
+  thr = thr > 255 ? 255 : thr;
+  da->seed = seed;
+  da->offset = offset;
+  da->thr = (unsigned)thr;
+  da->inv_keep = 256.f / (float)(256 - thr);
+  return true;
 }
 
 // dt: 1 = bf16, 2 = fp16. qkv [B,T,3*H*D]; mask [B,T] fp32 or null; out [B,T,H*D]; lse [B,H,T] fp32.
 // -1 = unsupported shape / dtype.
 DL4J_API int dl4j_attn_fwd_dt(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H,
                               int D, float scale, int causal, hipStream_t s) {
-  if (B < 1 || T < 1 || H < 1 || (dt != 1 && dt != 2)) return -1;
-  if (D == 64) return dt == 1 ? fwd_l<64, __bf16>(qkv, mask, out, lse, B, T, H, scale, causal, s)
-                              : fwd_l<64, _Float16>(qkv, mask, out, lse, B, T, H, scale, causal, s);
-  if (D == 128) return dt == 1 ? fwd_l<128, __bf16>(qkv, mask, out, lse, B, T, H, scale, causal, s)
-                               : fwd_l<128, _Float16>(qkv, mask, out, lse, B, T, H, scale, causal, s);
-  return -1;
+  return fwd_dispatch<false>(dt, qkv, mask, out, lse, B, T, H, D, scale, causal, DropArgs{0, nullptr, 0, 1.f}, s);
 }
 
 // dout [B,T,H*D]; dq_dot: fp32 workspace [B,H,T]; dqkv [B,T,3*H*D] (fully written).
 DL4J_API int dl4j_attn_bwd_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
                               const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int D, float scale,
                               int causal, hipStream_t s) {
-  if (B < 1 || T < 1 || H < 1 || (dt != 1 && dt != 2)) return -1;
-  if (D == 64) return dt == 1 ? bwd_l<64, __bf16>(qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, scale, causal, s)
-                              : bwd_l<64, _Float16>(qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, scale, causal, s);
-  if (D == 128) return dt == 1 ? bwd_l<128, __bf16>(qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, scale, causal, s)
-                               : bwd_l<128, _Float16>(qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, scale, causal,
-                                                      s);
-  return -1;
+  return bwd_dispatch<false>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, D, scale, causal,
+                             DropArgs{0, nullptr, 0, 1.f}, s);
+}
+
+// The same with attention-probability dropout (drop probability in [0, 1), see the mask definition at the top):
+// seed is a host scalar, offset a device pointer to the layer's step counter. lse is that of the undropped scores.
+// -1 also for drop outside [0, 1) or a null offset.
+DL4J_API int dl4j_attn_fwd_drop_dt(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T,
+                                   int H, int D, float scale, int causal, float drop, unsigned long long seed,
+                                   const long long* offset, hipStream_t s) {
+  DropArgs da;
+  if (!drop_args(drop, seed, offset, &da)) return -1;
+  return fwd_dispatch<true>(dt, qkv, mask, out, lse, B, T, H, D, scale, causal, da, s);
+}
+
+DL4J_API int dl4j_attn_bwd_drop_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                                   const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int D,
+                                   float scale, int causal, float drop, unsigned long long seed,
+                                   const long long* offset, hipStream_t s) {
+  DropArgs da;
+  if (!drop_args(drop, seed, offset, &da)) return -1;
+  return bwd_dispatch<true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, D, scale, causal, da, s);
+}
+
+// Test / debug only: keep [B*H, T, T] uint8 (1 = kept) of the mask the DROP kernels apply. Never part of a step.
+DL4J_API int dl4j_attn_drop_mask(unsigned char* keep, int BH, int T, float drop, unsigned long long seed,
+                                 const long long* offset, hipStream_t s) {
+  DropArgs da;
+  if (BH < 1 || T < 1 || !keep || !drop_args(drop, seed, offset, &da)) return -1;
+  const long long total = (long long)BH * T * T;
+  long long blocks = (total + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(attn_drop_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, s, keep, total, T, da);
+  return (int)hipGetLastError();
 }
 
 DL4J_API int dl4j_attn_fwd(const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H, int D,

@@ -163,3 +163,20 @@ __device__ __forceinline__ void idx_decomp4(long long t, int D0, int D1, int D2,
 __device__ __forceinline__ int idx_mod(long long t, int D) {
   return t < 0x7fffffffLL ? (int)((unsigned)t % (unsigned)D) : (int)(t % D);
 }
+
+// Philox-4x32-10 (Salmon et al., SC'11; Random123 reference constants): counter-based RNG of the dropout family
+// (nn_misc.hip), the attention-probability dropout (attention.hip) and the LayerNorm dropout variant (layernorm.hip).
+__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
+  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
+    const unsigned hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
+    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
+    key.x += W0;
+    key.y += W1;
+  }
+  return ctr;
+}
+
+__device__ __forceinline__ float u01(unsigned r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }

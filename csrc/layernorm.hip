@@ -23,12 +23,29 @@ template <> struct V8<float> {
   static __device__ __forceinline__ void st(float* p, const float* o) { Vec8<float>::store(p, o); }
 };
 
+// Hidden dropout fused into the forward (DROP = true instances): s = drop(x) (+ r), the residual is not dropped.
+// The mask is dropout_kernel's (nn_misc.hip, mode 0): element i of x uses lane (i & 3) of
+// philox({i >> 2, offset}, seed) and is kept (and divided by keep) iff u01 < keep, so dl4j_dropout(..., bwd = 1) with
+// the same (seed, offset) applies the same mask to the gradient. x is dropped IN PLACE (xio; every element is read
+// and written by the same lane; the x argument is not touched by these instances): the dropped x is what
+// dl4j_ln_bwd takes as its x, and nothing else reads the undropped GEMM output.
+struct LnDrop {
+  unsigned long long seed;
+  const long long* offset;
+  float keep;
+  void* xio;
+};
+template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
+template <> __device__ __forceinline__ float round_to<bf16>(float v) { return bf2f(f2bf(v)); }
+template <> __device__ __forceinline__ float round_to<f16>(float v) { return (float)(f16)v; }
+
 // CH = 8-element chunks per lane (N <= 512*CH)
-template <typename T, int CH, bool RES>
+template <typename T, int CH, bool RES, bool DROP = false>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ r,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      T* __restrict__ y, float* __restrict__ mean_out,
-                                                     float* __restrict__ rstd_out, long long M, int N, float eps) {
+                                                     float* __restrict__ rstd_out, long long M, int N, float eps,
+                                                     LnDrop dr) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -39,7 +56,25 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const T* __restrict__ x, co
   for (int c = 0; c < CH; ++c) {
     const int ch = lane + c * 64;
     if (ch < nch) {
-      V8<T>::ld(x + row * N + ch * 8, v[c]);
+      if constexpr (DROP) V8<T>::ld((const T*)dr.xio + row * N + ch * 8, v[c]);
+      else V8<T>::ld(x + row * N + ch * 8, v[c]);
+      if constexpr (DROP) {
+        const unsigned long long off = (unsigned long long)dr.offset[0];
+        const uint2 key = make_uint2((unsigned)dr.seed, (unsigned)(dr.seed >> 32));
+        const unsigned long long q0 = (unsigned long long)(row * N + ch * 8) >> 2;   // N % 8 == 0: two whole quads
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const unsigned long long q = q0 + h;
+          const uint4 rn = philox4x32_10(make_uint4((unsigned)q, (unsigned)(q >> 32), (unsigned)off,
+                                                    (unsigned)(off >> 32)), key);
+          const float u[4] = {u01(rn.x), u01(rn.y), u01(rn.z), u01(rn.w)};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[c][4 * h + e] = u[e] < dr.keep ? v[c][4 * h + e] / dr.keep : 0.f;
+        }
+        V8<T>::st((T*)dr.xio + row * N + ch * 8, v[c]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[c][k] = round_to<T>(v[c][k]);   // the stored value is what the backward reads
+      }
       if (RES) {
         float rr[8];
         V8<T>::ld(r + row * N + ch * 8, rr);
@@ -368,17 +403,22 @@ static unsigned* ln_ticket_slot(int cols) {
   return base[dev] + 128 * k;
 }
 
-template <typename T, int CH>
+template <typename T, int CH, bool DROP = false>
 static int fwd_l(const void* x, const void* r, const float* g, const float* b, void* y, float* mean, float* rstd,
-                 long long M, int N, float eps, hipStream_t s) {
+                 long long M, int N, float eps, hipStream_t s, LnDrop dr = LnDrop{0, nullptr, 1.f, nullptr}) {
   const dim3 grid((unsigned)((M + 3) / 4));
   if (r)
-    hipLaunchKernelGGL((ln_fwd_kernel<T, CH, true>), grid, dim3(256), 0, s, (const T*)x, (const T*)r, g, b, (T*)y,
-                       mean, rstd, M, N, eps);
+    hipLaunchKernelGGL((ln_fwd_kernel<T, CH, true, DROP>), grid, dim3(256), 0, s, (const T*)x, (const T*)r, g, b,
+                       (T*)y, mean, rstd, M, N, eps, dr);
   else
-    hipLaunchKernelGGL((ln_fwd_kernel<T, CH, false>), grid, dim3(256), 0, s, (const T*)x, (const T*)nullptr, g, b,
-                       (T*)y, mean, rstd, M, N, eps);
+    hipLaunchKernelGGL((ln_fwd_kernel<T, CH, false, DROP>), grid, dim3(256), 0, s, (const T*)x, (const T*)nullptr, g,
+                       b, (T*)y, mean, rstd, M, N, eps, dr);
   return (int)hipGetLastError();
+}
+template <typename T, int CH>
+static int fwd_drop_l(const void* x, const void* r, const float* g, const float* b, void* y, float* mean, float* rstd,
+                      long long M, int N, float eps, hipStream_t s, LnDrop dr) {
+  return fwd_l<T, CH, true>(x, r, g, b, y, mean, rstd, M, N, eps, s, dr);
 }
 
 static constexpr int kRPW = 16;
@@ -489,6 +529,19 @@ DL4J_API int dl4j_ln_fwd(int dtype, const void* x, const void* r, const float* g
   if (dtype == 1) LN_CH_DISPATCH(fwd_l, bf16, x, r, gamma, beta, y, mean, rstd, M, N, eps, s);
   if (dtype == 2) LN_CH_DISPATCH(fwd_l, f16, x, r, gamma, beta, y, mean, rstd, M, N, eps, s);
   LN_CH_DISPATCH(fwd_l, float, x, r, gamma, beta, y, mean, rstd, M, N, eps, s);
+}
+
+// dl4j_ln_fwd with hidden dropout on x (not on r): keep = RETAIN probability in (0, 1], the mask and scaling of
+// dl4j_dropout mode 0 with the same (seed, offset). x [M, N] is overwritten with the dropped x; pass it as x to
+// dl4j_ln_bwd, whose dx is then the residual's gradient and, through dl4j_dropout(bwd = 1), the producer's.
+DL4J_API int dl4j_ln_fwd_drop(int dtype, void* x, const void* r, const float* gamma, const float* beta, void* y,
+                              float* mean, float* rstd, long long M, int N, float eps, float keep,
+                              unsigned long long seed, const long long* offset, hipStream_t s) {
+  if (N % 8 != 0 || N > 4096 || M < 1 || !x || !offset || !(keep > 0.f && keep <= 1.f)) return -1;
+  const LnDrop dr{seed, offset, keep, x};
+  if (dtype == 1) LN_CH_DISPATCH(fwd_drop_l, bf16, x, r, gamma, beta, y, mean, rstd, M, N, eps, s, dr);
+  if (dtype == 2) LN_CH_DISPATCH(fwd_drop_l, f16, x, r, gamma, beta, y, mean, rstd, M, N, eps, s, dr);
+  LN_CH_DISPATCH(fwd_drop_l, float, x, r, gamma, beta, y, mean, rstd, M, N, eps, s, dr);
 }
 
 // part: fp32 workspace of dl4j_ln_partial_rows(M) * 3 * N floats. dsum (optional, [N] fp32): column sums of dx.

@@ -83,21 +83,7 @@ __global__ __launch_bounds__(256) void lrn_bwd_kernel(const T* __restrict__ x, c
 }
 
 // ------------------------------------------------------------------------------------------------ Philox dropout
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-  const unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-    const unsigned hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += W0;
-    key.y += W1;
-  }
-  return ctr;
-}
-
-__device__ __forceinline__ float u01(unsigned r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
-
+// (philox4x32_10 / u01: common.h, shared with the attention and LayerNorm dropout variants)
 // mode 0 Dropout, 1 AlphaDropout, 2 GaussianDropout, 3 GaussianNoise.  bwd: apply the multiplicative part only.
 // Element i uses lane (i & 3) of philox(counter = {i >> 2, offset}, key = seed).
 template <typename T>

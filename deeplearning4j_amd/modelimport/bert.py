@@ -48,9 +48,28 @@ def _load_config(cfg, src):
         return json.load(fh)
 
 
-def importBert(src, config=None, numLabels=None, seqLen=128, device=None, dataType=None):
+def _dropout_probs(dropout, cfg):
+    """(hidden, attention, classifier) DROP probabilities for ``importBert(dropout=...)``."""
+    if dropout is None:
+        return 0.0, 0.0, 0.0
+    if isinstance(dropout, str):
+        if dropout != "config":
+            raise ValueError(f'dropout must be None, "config" or a drop probability, got {dropout!r}')
+        hid = float(cfg.get("hidden_dropout_prob", 0.0) or 0.0)
+        cls = cfg.get("classifier_dropout")
+        return hid, float(cfg.get("attention_probs_dropout_prob", 0.0) or 0.0), hid if cls is None else float(cls)
+    p = float(dropout)
+    return p, p, p
+
+
+def importBert(src, config=None, numLabels=None, seqLen=128, device=None, dataType=None, dropout=None):
     """Build a BertBase graph with the checkpoint's hyper-parameters and copy its weights. ``numLabels`` defaults to
-    the checkpoint's classifier size (2 when there is none; the classifier then keeps its random init)."""
+    the checkpoint's classifier size (2 when there is none; the classifier then keeps its random init).
+
+    ``dropout`` (DROP probabilities as in HuggingFace's config, applied in training only): ``None`` keeps every
+    dropout at 0; ``"config"`` reads ``hidden_dropout_prob``, ``attention_probs_dropout_prob`` and
+    ``classifier_dropout`` (falling back to ``hidden_dropout_prob``) from the checkpoint's config; a float sets all
+    three."""
     from ..models import BertBase
     from ..nn.conf import DataType
     sd = _load_state(src)
@@ -60,7 +79,9 @@ def importBert(src, config=None, numLabels=None, seqLen=128, device=None, dataTy
         numLabels = sd["classifier.weight"].shape[0] if "classifier.weight" in sd else 2
     model = BertBase(numLabels=numLabels, inputShape=[seqLen], vocabSize=cfg["vocab_size"], hidden=cfg["hidden_size"],
                      layers=cfg["num_hidden_layers"], heads=cfg["num_attention_heads"], ffn=cfg["intermediate_size"],
-                     maxPositions=cfg["max_position_embeddings"], dataType=dataType or DataType.FLOAT)
+                     maxPositions=cfg["max_position_embeddings"], dataType=dataType or DataType.FLOAT,
+                     **dict(zip(("hiddenDropout", "attentionDropout", "classifierDropout"),
+                                _dropout_probs(dropout, cfg))))
     conf = model.conf()
     eps = float(cfg.get("layer_norm_eps", 1e-12))
     for name, v in conf.vertices.items():

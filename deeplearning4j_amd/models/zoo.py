@@ -886,12 +886,23 @@ class BertBase(ZooModel):
     """BERT encoder + [CLS] pooler + softmax classifier (BASELINE.json's BERT-base config; new relative to the
     reference zoo). Defaults are BERT-base: 12 layers, hidden 768, 12 heads, FFN 3072, vocab 30522, 512 positions,
     N(0, 0.02) init, Adam(2e-5). ``inputShape = [seqLen]``; input = token ids [mb, seqLen] (featuresMask [mb, T]
-    marks real tokens)."""
+    marks real tokens).
+
+    ``hiddenDropout`` / ``attentionDropout`` / ``classifierDropout`` are DROP probabilities in [0, 1) as in
+    HuggingFace's config (0.0 = off, the default), applied in training only. ``classifierDropout`` acts on the pooled
+    output through the classifier layer's ``dropOut``, which takes the RETAIN probability 1 - classifierDropout."""
     DEFAULT_SHAPE = [128]
 
     def __init__(self, numLabels=2, seed=123, inputShape=None, vocabSize=30522, hidden=768, layers=12, heads=12,
-                 ffn=3072, maxPositions=512, learningRate=2e-5, **kw):
+                 ffn=3072, maxPositions=512, learningRate=2e-5, hiddenDropout=0.0, attentionDropout=0.0,
+                 classifierDropout=0.0, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
+        if not 0.0 <= float(classifierDropout) < 1.0:
+            from ..exceptions import DL4JInvalidConfigException
+            raise DL4JInvalidConfigException(f"BertBase: classifierDropout is a drop probability in [0, 1), got "
+                                             f"{classifierDropout!r}")
+        self.hiddenDropout, self.attentionDropout = hiddenDropout, attentionDropout
+        self.classifierDropout = float(classifierDropout)
         self.vocabSize, self.hidden, self.layers, self.heads = vocabSize, hidden, layers, heads
         self.ffn, self.maxPositions, self.learningRate = ffn, maxPositions, learningRate
 
@@ -902,15 +913,19 @@ class BertBase(ZooModel):
              .graphBuilder())
         g.addInputs("tokens")
         g.addLayer("embeddings", BertEmbeddingLayer.Builder().nIn(self.vocabSize).nOut(self.hidden)
-                   .maxPositions(self.maxPositions).inputLength(T).build(), "tokens")
+                   .maxPositions(self.maxPositions).inputLength(T).hiddenDropout(self.hiddenDropout).build(), "tokens")
         prev = "embeddings"
         for i in range(self.layers):
             g.addLayer(f"encoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
-                       .nHeads(self.heads).ffnSize(self.ffn).build(), prev)
+                       .nHeads(self.heads).ffnSize(self.ffn).hiddenDropout(self.hiddenDropout)
+                       .attentionDropout(self.attentionDropout).build(), prev)
             prev = f"encoder_{i}"
         g.addLayer("pooler", BertPoolerLayer.Builder().nIn(self.hidden).nOut(self.hidden).build(), prev)
-        g.addLayer("classifier", OutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
-                   .nIn(self.hidden).nOut(self.numLabels).build(), "pooler")
+        cls = OutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX).nIn(self.hidden) \
+            .nOut(self.numLabels)
+        if self.classifierDropout > 0.0:
+            cls = cls.dropOut(1.0 - self.classifierDropout)          # the reference's dropOut is a retain probability
+        g.addLayer("classifier", cls.build(), "pooler")
         g.setOutputs("classifier")
         return g
 

@@ -1383,10 +1383,29 @@ class SameDiffLayerConf(Layer):
             self.nIn = inputType.size if hasattr(inputType, "size") else inputType.arrayElementsPerExample()
 
 
+def _check_drop_prob(layer, name):
+    """``name`` is a DROP probability in [0, 1) (HuggingFace's convention; 0.0 = off) — the opposite of the
+    retain-probability ``dropOut`` of the reference's layers."""
+    v = getattr(layer, name)
+    ok = isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 <= float(v) < 1.0
+    if not ok:
+        raise DL4JInvalidConfigException(
+            f"{type(layer).__name__}: {name} is a drop probability in [0, 1) (0 = no dropout), got {v!r}")
+    setattr(layer, name, float(v))
+
+
 class SelfAttentionLayer(FeedForwardLayer):
-    """Multi-head self attention over RNN-format input [mb, nIn, T] (new: BERT config)."""
-    FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False}
+    """Multi-head self attention over RNN-format input [mb, nIn, T] (new: BERT config).
+
+    ``attentionDropout``: DROP probability in [0, 1) of the attention probabilities, applied in training only
+    (0.0 = off, the default; HuggingFace's ``attention_probs_dropout_prob``, NOT the reference's retain-probability
+    ``dropOut``). The mask is generated inside the flash-attention kernels and never stored."""
+    FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False, "attentionDropout": 0.0}
     RUNTIME = "deeplearning4j_amd.nn.layers.attention:SelfAttentionLayerImpl"
+
+    def _post_init(self):
+        super()._post_init()
+        _check_drop_prob(self, "attentionDropout")
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1420,9 +1439,21 @@ class SelfAttentionLayer(FeedForwardLayer):
 class TransformerEncoderLayer(FeedForwardLayer):
     """One post-LN transformer encoder block (BERT): fused QKV projection -> multi-head attention (flash-style HIP
     kernel) -> output projection -> LayerNorm(+residual) -> FFN (GELU) -> LayerNorm(+residual). RNN-format
-    input/output [mb, nIn, T] (new: BERT-base config of BASELINE.json; not in the reference)."""
-    FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0}
+    input/output [mb, nIn, T] (new: BERT-base config of BASELINE.json; not in the reference).
+
+    ``hiddenDropout`` / ``attentionDropout``: DROP probabilities in [0, 1), applied in training only; 0.0 = off, the
+    default (HuggingFace's ``hidden_dropout_prob`` / ``attention_probs_dropout_prob`` — the opposite of the
+    reference's retain-probability ``dropOut``). Hidden dropout sits at BERT's two sites, LN(drop(ctx Wo + bo) + x)
+    and LN(drop(ffn) + h1), fused into the LayerNorm forward kernel; attention dropout acts on the softmax
+    probabilities inside the flash-attention kernels. No mask is stored on the GPU."""
+    FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
+              "attentionDropout": 0.0}
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
+
+    def _post_init(self):
+        super()._post_init()
+        _check_drop_prob(self, "hiddenDropout")
+        _check_drop_prob(self, "attentionDropout")
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1452,9 +1483,14 @@ class TransformerEncoderLayer(FeedForwardLayer):
 
 class BertEmbeddingLayer(FeedForwardLayer):
     """Token ids [mb, T] -> LayerNorm(word + position + token-type(0) embeddings) as [mb, nOut, T]
-    (nIn = vocabulary size)."""
-    FIELDS = {"maxPositions": 512, "typeVocabSize": 2, "layerNormEps": 1e-12, "inputLength": -1}
+    (nIn = vocabulary size). ``hiddenDropout``: DROP probability in [0, 1) applied after the LayerNorm in training
+    (0.0 = off, the default; HuggingFace's ``hidden_dropout_prob``, not a retain probability)."""
+    FIELDS = {"maxPositions": 512, "typeVocabSize": 2, "layerNormEps": 1e-12, "inputLength": -1, "hiddenDropout": 0.0}
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:BertEmbeddingLayerImpl"
+
+    def _post_init(self):
+        super()._post_init()
+        _check_drop_prob(self, "hiddenDropout")
 
     def getOutputType(self, layerIndex, inputType):
         return InputType.recurrent(self.nOut, self.inputLength)

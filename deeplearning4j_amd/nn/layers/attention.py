@@ -12,14 +12,17 @@ hand-derived backward (no torch.autograd):
             dQKV = attention_bwd(dO) (flash backward kernel, or P-based explicit backward);
             dW{q,k,v} = X^T dQ/dK/dV, db{q,k,v} = colsums;  dX = dQ Wq^T + dK Wk^T + dV Wv^T (beta-accumulated GEMMs)
 Feature masks [mb, T] mask padded keys; masked query rows produce zeros.
+``attentionDropout`` (a DROP probability, training only): the keep mask is generated inside the flash kernels from
+the layer's PhiloxStream and regenerated in the backward; the explicit path takes its mask from ``dropoutKeep``.
 """
 import torch
 
 from .base import LayerImpl, bias_grad_, matmul, weight_grad_
+from .transformer import DropoutSites
 from ...ops.gemm import mmul
 
 
-class SelfAttentionLayerImpl(LayerImpl):
+class SelfAttentionLayerImpl(DropoutSites, LayerImpl):
     def type(self):
         return "RECURRENT"
 
@@ -28,25 +31,31 @@ class SelfAttentionLayerImpl(LayerImpl):
         hs = c.headSize or (c.nOut // c.nHeads)
         return c.nHeads, hs, c.nHeads * hs
 
-    def _attn_fwd(self, qkv, mb, T, H, mask):
+    def _attn_fwd(self, qkv, mb, T, H, mask, drop=0.0):
         from ...ops import transformer_native as TN
         from ...ops import use_native
         q3 = qkv.reshape(mb, T, -1)
         if q3.is_cuda and q3.dtype in (torch.bfloat16, torch.float16) and use_native(q3, "attention") \
                 and TN.attn_supported(q3, H):
+            if drop > 0.0:
+                st = self.dropoutStream("attention")
+                out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), dropout=drop, rng=st)
+                return out, ("native", out, lse, drop, st)
             out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal))
             return out, ("native", out, lse)
         if q3.is_cuda:
             from ...ops import fallback
             fallback.record("attention", f"SelfAttentionLayer head size {q3.shape[-1] // (3 * H)} / {q3.dtype}")
-        out, ctx = TN.attention_fwd_explicit(q3, H, mask, bool(self.conf.causal))
+        keep = self.dropoutKeep("attention", (mb, H, T, T), drop, q3) if drop > 0.0 else None
+        out, ctx = TN.attention_fwd_explicit(q3, H, mask, bool(self.conf.causal), keep=keep)
         return out, ("explicit", ctx)
 
     def _attn_bwd(self, qkv, do, mb, T, H, mask, ctx):
         from ...ops import transformer_native as TN
         if ctx[0] == "native":
+            kw = dict(dropout=ctx[3], rng=ctx[4]) if len(ctx) > 3 else {}
             return TN.attn_bwd(qkv.reshape(mb, T, -1), ctx[1], ctx[2], do.reshape(mb, T, -1), H, mask,
-                               bool(self.conf.causal))
+                               bool(self.conf.causal), **kw)
         return TN.attention_bwd_explicit(ctx[1], do.reshape(mb, T, -1), qkv.dtype)
 
     def activate(self, x, training=False, mask=None, **kw):
@@ -59,7 +68,10 @@ class SelfAttentionLayerImpl(LayerImpl):
         for i, (wk, bk) in enumerate((("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
             mmul(X, self.W(wk), out=qkv[:, i * d:(i + 1) * d], bias=self.Wbias(bk).reshape(-1))
         m = mask.reshape(mb, T) if mask is not None else None
-        o, actx = self._attn_fwd(qkv, mb, T, H, m)
+        drop = float(self.conf.attentionDropout) if training else 0.0
+        if drop > 0.0:
+            self.dropoutBegin(x.device)
+        o, actx = self._attn_fwd(qkv, mb, T, H, m, drop)
         o2 = o.reshape(mb * T, d)
         Y = matmul(o2, self.W("Wo"), bias=self.Wbias("bo"))
         if m is not None:

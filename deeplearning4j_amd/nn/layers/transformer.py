@@ -12,6 +12,16 @@ The backward is written out by hand (no autograd): GEMMs produce fp32 weight gra
 gradient views, attention/LN backward are the matching HIP kernels, and the residual gradients are summed in
 place. Activations cross layer boundaries as [mb, E, T] *views* of token-major memory, so stacking blocks costs
 no transposes. On CPU (and fp64 gradient checks) the same math runs on plain torch ops.
+
+Dropout (training only; ``hiddenDropout`` / ``attentionDropout`` are DROP probabilities, 0 = off = the path above):
+  ctx = attention(qkv) with the keep mask generated inside the flash kernels (csrc/attention.hip, DROP instances)
+  h1  = LN(drop(ctx·Wo + bo) + x),  h2 = LN(drop(ffn) + h1): the mask is applied by the LayerNorm forward kernel as
+        it loads its input (which it overwrites with the dropped values, the x of the unchanged LayerNorm backward)
+Backward of a hidden site: ds from the LayerNorm backward is the residual's gradient; the producer's is ds∘D, one
+launch of the Philox dropout kernel in backward mode (it regenerates the mask), and the producer's bias gradient is
+the column sum of ds∘D by the column-sum kernel — the dropout is NOT fused into the LayerNorm backward kernels.
+Each layer owns one PhiloxStream advanced once per training forward; its sites use keys derived from the layer's
+seed. Off the kernels (CPU, fp32 / fp64, other head sizes) the masks come from ``dropoutKeep``.
 """
 import math
 
@@ -112,26 +122,107 @@ def _ln_bwd(dy, x, res, g, ctx, gview=None, bview=None, dsum_view=None):
     return ds
 
 
+# ------------------------------------------------------------------------------------------------ dropout
+class DropoutSites:
+    """Dropout state of a transformer-family layer: ONE PhiloxStream per layer impl, advanced once per training
+    forward (``dropoutBegin``); the layer's sites draw from streams with keys derived from the layer's seed that
+    share its device counter, so their masks are independent and forward / backward of a step regenerate the same
+    ones. Every mask taken OFF the kernels (CPU, fp32 / fp64, head sizes outside the flash kernel) comes from
+    ``dropoutKeep``, which a test may override to feed the reference path another run's masks."""
+    SITES = ("attention", "hidden1", "hidden2", "embedding")
+    _drop_rng = None
+    _drop_streams = None
+
+    def dropoutBegin(self, device):
+        from ...ops import nn_misc
+        if self._drop_rng is None or self._drop_rng.offset.device != device:
+            # the seed comes from torch's generator WITHOUT advancing it (a first training forward draws the same
+            # reference-path masks as any later one under the same manual_seed); the layer's name and index make it
+            # this layer's own
+            import zlib
+            with torch.random.fork_rng(devices=[]):
+                base = nn_misc.PhiloxStream(device)
+            name = str(getattr(self.conf, "layerName", None) or "")
+            self._drop_rng = base.derive(len(self.SITES) + int(self.index or 0) + (zlib.crc32(name.encode()) << 8))
+            self._drop_streams = {}
+        self._drop_rng.advance()
+
+    def dropoutStream(self, site):
+        st = self._drop_streams.get(site)
+        if st is None:
+            st = self._drop_streams[site] = self._drop_rng.derive(self.SITES.index(site))
+        return st
+
+    def dropoutKeep(self, site, shape, drop, like):
+        """Keep mask of ``shape`` for dropout site ``site``, already scaled by 1/keep (0 = dropped), on ``like``'s
+        device: torch's generator and a saved mask, as nn/conf/regularization.py does on the CPU."""
+        keep = 1.0 - drop
+        return (torch.rand(tuple(shape), device=like.device, dtype=torch.float32) < keep).to(torch.float32) / keep
+
+
+def _ln_fwd_drop(x, res, g, b, eps, drop, owner, site):
+    """LN(drop(x) + res) -> (y, LayerNorm ctx, the x the LayerNorm backward takes, dropout ctx or None)."""
+    if drop <= 0.0:
+        y, ln = _ln_fwd(x, res, g, b, eps)
+        return y, ln, x, None
+    if _native(x, "layernorm"):
+        from ...ops import transformer_native as TN
+        if TN.ln_supported(x, x.shape[-1]):
+            st = owner.dropoutStream(site)
+            r = TN.ln_fwd_dropout(x, g, b, eps, res, drop, st, inplace=True)    # x: a GEMM output nobody else reads
+            if r is not None:
+                y, mean, rstd, xd = r
+                return y, ("native", mean, rstd), xd, ("native", st, drop)
+    keep = owner.dropoutKeep(site, x.shape, drop, x).to(x.dtype)
+    xd = x * keep
+    y, ln = _ln_fwd(xd, res, g, b, eps)
+    return y, ln, xd, ("mask", keep)
+
+
+def _drop_fwd(y, drop, owner, site):
+    """drop(y) as its own launch (the embedding's dropout sits after its LayerNorm) -> (y', dropout ctx)."""
+    from ...ops import nn_misc
+    if y.is_cuda and y.is_contiguous() and nn_misc._dt(y) is not None and ops.use_native(y, "dropout"):
+        st = owner.dropoutStream(site)
+        return nn_misc.dropout_native(y, "dropout", st, False, p=1.0 - drop), ("native", st, drop)
+    keep = owner.dropoutKeep(site, y.shape, drop, y).to(y.dtype)
+    return y * keep, ("mask", keep)
+
+
+def _drop_bwd(d, dctx):
+    """d∘D for the mask of the forward (regenerated by the Philox kernel in backward mode, or the saved one)."""
+    if dctx[0] == "native":
+        from ...ops import nn_misc
+        return nn_misc.dropout_native(d.contiguous(), "dropout", dctx[1], True, p=1.0 - dctx[2])
+    return d * dctx[1].to(d.dtype)
+
+
 # ------------------------------------------------------------------------------------------------ attention
-def _attn_fwd(qkv, B, T, H, mask, causal):
+def _attn_fwd(qkv, B, T, H, mask, causal, drop=0.0, owner=None):
     from ...ops import transformer_native as TN
     if _native(qkv, "attention"):
         q3 = qkv.reshape(B, T, -1)
         if TN.attn_supported(q3, H):
+            if drop > 0.0:
+                st = owner.dropoutStream("attention")
+                out, lse = TN.attn_fwd(q3, H, mask, causal, dropout=drop, rng=st)
+                return out.reshape(B * T, -1), ("native", out, lse, drop, st)
             out, lse = TN.attn_fwd(q3, H, mask, causal)
             return out.reshape(B * T, -1), ("native", out, lse)
     if qkv.is_cuda:
         from ...ops import fallback
         fallback.record("attention", f"head size {qkv.shape[-1] // (3 * H)} / dtype {qkv.dtype}: explicit torch path")
-    o, ctx = TN.attention_fwd_explicit(qkv.reshape(B, T, -1), H, mask, causal)
+    keep = owner.dropoutKeep("attention", (B, H, T, T), drop, qkv) if drop > 0.0 else None
+    o, ctx = TN.attention_fwd_explicit(qkv.reshape(B, T, -1), H, mask, causal, keep=keep)
     return o.reshape(B * T, -1), ("explicit", ctx)
 
 
 def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx):
     from ...ops import transformer_native as TN
     if ctx[0] == "native":
+        kw = dict(dropout=ctx[3], rng=ctx[4]) if len(ctx) > 3 else {}
         return TN.attn_bwd(qkv.reshape(B, T, -1), ctx[1], ctx[2], dctx.reshape(B, T, -1), H, mask,
-                           causal).reshape(B * T, -1)
+                           causal, **kw).reshape(B * T, -1)
     return TN.attention_bwd_explicit(ctx[1], dctx.reshape(B, T, -1), qkv.dtype).reshape(B * T, -1)
 
 
@@ -141,7 +232,7 @@ def _token_major(x):
     return x.permute(0, 2, 1).reshape(mb * T, E)
 
 
-class TransformerEncoderLayerImpl(LayerImpl):
+class TransformerEncoderLayerImpl(DropoutSites, LayerImpl):
     def type(self):
         return "RECURRENT"
 
@@ -153,41 +244,59 @@ class TransformerEncoderLayerImpl(LayerImpl):
         dt = self.W("Wqkv").dtype
         xt = _token_major(x).to(dt)
         m = mask.reshape(B, T) if mask is not None else None
+        pa, ph = (float(c.attentionDropout), float(c.hiddenDropout)) if training else (0.0, 0.0)
+        if pa > 0.0 or ph > 0.0:
+            self.dropoutBegin(x.device)
         qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
-        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal)
+        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
-        h1, ln1 = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
+        h1, ln1, a, d1 = _ln_fwd_drop(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps, ph, self,
+                                      "hidden1")
         # FFN-1 with bias + exact GELU fused into the GEMM epilogue; the pre-activation z1 is kept for backward
         z1 = torch.empty(h1.shape[0], self.W("W1").shape[1], dtype=h1.dtype, device=h1.device)
         f = matmul(h1, self.W("W1"), bias=self.Wbias("b1"), act="gelu", z=z1)
         f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
-        y, ln2 = _ln_fwd(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps)
+        y, ln2, f2, d2 = _ln_fwd_drop(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps, ph, self,
+                                      "hidden2")
         self.maskArray = mask
         if training:
-            self._c = (xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m)
+            self._c = (xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m, d1, d2)
         self.input = x
         return y.reshape(B, T, E).permute(0, 2, 1)
 
     def backpropGradient(self, eps, **kw):
         c = self.conf
-        xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m = self._c
+        xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m, d1, d2 = self._c
         self._c = None
         g = self.grads
         dt = xt.dtype
         dy = _token_major(eps).to(dt)
-        ds2 = _ln_bwd(dy, f2, h1, self.params["ln2g"], ln2, g["ln2g"], g["ln2b"], g["b2"])   # + b2 gradient
-        _wgrad(g["W2"], f, ds2)
-        if _native(ds2, "gemm") and z1.dtype == ds2.dtype:
-            # GELU backward in the GEMM epilogue: dz1 = (ds2 · W2ᵀ) * gelu'(z1)
-            dz1 = mmul(ds2, self.W("W2").t(), act="dgelu", z=z1)
+        # ds2 / ds1: the residual's gradient. Without hidden dropout it is also the producing GEMM's (df2 / da) and its
+        # column sums (b2 / bo gradient) come out of the LayerNorm backward launch; with it the producer's gradient is
+        # ds∘D in a tensor of its own (ds stays the residual accumulator below) and the bias gradient ITS column sums.
+        if d2 is None:
+            ds2 = df2 = _ln_bwd(dy, f2, h1, self.params["ln2g"], ln2, g["ln2g"], g["ln2b"], g["b2"])
         else:
-            dz1 = _gelu_bwd(z1, matmul(ds2, self.W("W2").t()))
+            ds2 = _ln_bwd(dy, f2, h1, self.params["ln2g"], ln2, g["ln2g"], g["ln2b"])
+            df2 = _drop_bwd(ds2, d2)
+            _bsum(g["b2"], df2)
+        _wgrad(g["W2"], f, df2)
+        if _native(df2, "gemm") and z1.dtype == df2.dtype:
+            # GELU backward in the GEMM epilogue: dz1 = (df2 · W2ᵀ) * gelu'(z1)
+            dz1 = mmul(df2, self.W("W2").t(), act="dgelu", z=z1)
+        else:
+            dz1 = _gelu_bwd(z1, matmul(df2, self.W("W2").t()))
         _wgrad(g["W1"], h1, dz1)
         _bsum(g["b1"], dz1)
         dh1 = mmul(dz1, self.W("W1").t(), out=ds2, beta=1.0)          # residual gradient summed in place
-        ds1 = _ln_bwd(dh1, a, xt, self.params["ln1g"], ln1, g["ln1g"], g["ln1b"], g["bo"])   # + bo gradient
-        _wgrad(g["Wo"], ctx, ds1)
-        dctx = matmul(ds1, self.W("Wo").t())
+        if d1 is None:
+            ds1 = da = _ln_bwd(dh1, a, xt, self.params["ln1g"], ln1, g["ln1g"], g["ln1b"], g["bo"])
+        else:
+            ds1 = _ln_bwd(dh1, a, xt, self.params["ln1g"], ln1, g["ln1g"], g["ln1b"])
+            da = _drop_bwd(ds1, d1)
+            _bsum(g["bo"], da)
+        _wgrad(g["Wo"], ctx, da)
+        dctx = matmul(da, self.W("Wo").t())
         dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx)
         _wgrad(g["Wqkv"], xt, dqkv)
         _bsum(g["bqkv"], dqkv)
@@ -196,7 +305,7 @@ class TransformerEncoderLayerImpl(LayerImpl):
         return self.make_gradient(), dx.reshape(B, T, E).permute(0, 2, 1)
 
 
-class BertEmbeddingLayerImpl(LayerImpl):
+class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
     def type(self):
         return "RECURRENT"
 
@@ -213,14 +322,20 @@ class BertEmbeddingLayerImpl(LayerImpl):
             e = self.W("Wword")[idx.reshape(-1)] + self.W("Wpos")[:T].repeat(B, 1) + self.W("Wtype")[0].reshape(1, -1)
             e = e.to(dt).contiguous()
         y, ln = _ln_fwd(e, None, self.params["lng"], self.params["lnb"], c.layerNormEps)
+        dctx = None
+        if training and float(c.hiddenDropout) > 0.0:           # drop(LN(emb)): after the LayerNorm, its own launch
+            self.dropoutBegin(y.device)
+            y, dctx = _drop_fwd(y, float(c.hiddenDropout), self, "embedding")
         if training:
-            self._c = (idx, e, ln, B, T)
+            self._c = (idx, e, ln, B, T, dctx)
         return y.reshape(B, T, -1).permute(0, 2, 1)
 
     def backpropGradient(self, eps, **kw):
-        idx, e, ln, B, T = self._c
+        idx, e, ln, B, T, dctx = self._c
         self._c = None
         dy = _token_major(eps).to(e.dtype)
+        if dctx is not None:
+            dy = _drop_bwd(dy, dctx)
         g = self.grads
         de = _ln_bwd(dy, e, None, self.params["lng"], ln, g["lng"], g["lnb"])
         from ...ops import nd4j_kernels as NK

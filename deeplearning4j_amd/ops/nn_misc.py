@@ -138,6 +138,17 @@ class PhiloxStream:
     def advance(self):
         self.offset.add_(1)
 
+    def derive(self, k):
+        """A stream with its own key (a splitmix64 hash of this seed and ``k``) that SHARES this stream's device
+        counter: the dropout sites of one layer draw independent masks from one counter advanced once per step."""
+        z = (self.seed + 0x9E3779B97F4A7C15 * (int(k) + 1)) & 0xFFFFFFFFFFFFFFFF
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+        d = PhiloxStream.__new__(PhiloxStream)
+        d.seed = z ^ (z >> 31)
+        d.offset = self.offset
+        return d
+
 
 def dropout_native(x, mode, stream, bwd, p=1.0, a=1.0, b=0.0, alpha_p=0.0, sd=0.0):
     """y = f(x) for the dropout family on the GPU (None when the dtype is not covered)."""

@@ -8,7 +8,12 @@ MI355X, bf16 compute / fp32 master weights, synthetic token ids, random-init wei
   --impl torch  like-for-like PyTorch-ROCm comparator: transformers.BertForSequenceClassification in bf16 with
                 torch.optim.AdamW(fused=True) and SDPA attention
 
+--dropout P (default 0) is the DROP probability of every dropout site of either implementation: hidden, attention
+and classifier dropout of the dl4j model; hidden_dropout_prob and attention_probs_dropout_prob of the HuggingFace
+config (whose own default would be 0.1), so both sides of a comparison run the same dropout.
+
 Usage: python tools/bench_bert.py [--impl dl4j|torch] [--batch 32] [--seq 128] [--steps 10] [--warmup 3]
+                                  [--dropout 0.0]
 """
 import argparse
 import json
@@ -29,7 +34,8 @@ def _sync():
 def run_dl4j(args, dev):
     from deeplearning4j_amd.models import BertBase
     from deeplearning4j_amd.nn.conf import DataType
-    net = BertBase(numLabels=2, inputShape=[args.seq], layers=args.layers,
+    net = BertBase(numLabels=2, inputShape=[args.seq], layers=args.layers, hiddenDropout=args.dropout,
+                   attentionDropout=args.dropout, classifierDropout=args.dropout,
                    dataType={"bf16": DataType.BFLOAT16, "fp16": DataType.HALF}.get(args.dtype, DataType.FLOAT)
                    ).init(device=dev)
     g = torch.Generator().manual_seed(0)
@@ -46,7 +52,8 @@ def run_dl4j(args, dev):
 
 def run_torch(args, dev):
     import transformers
-    cfg = transformers.BertConfig(num_hidden_layers=args.layers, num_labels=2, attn_implementation="sdpa")
+    cfg = transformers.BertConfig(num_hidden_layers=args.layers, num_labels=2, attn_implementation="sdpa",
+                                  hidden_dropout_prob=args.dropout, attention_probs_dropout_prob=args.dropout)
     model = transformers.BertForSequenceClassification(cfg).to(dev)
     if args.dtype in ("bf16", "fp16"):
         model = model.to(torch.bfloat16 if args.dtype == "bf16" else torch.float16)
@@ -75,6 +82,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="drop probability of every dropout site (hidden, attention, classifier) of either impl")
     ap.add_argument("--graph", type=int, default=1, help="capture the dl4j training step in HIP graphs")
     args = ap.parse_args()
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
@@ -92,7 +101,7 @@ def main():
         "metric": "BERT-base fine-tuning throughput on one MI355X", "value": round(sps * args.seq, 1),
         "unit": "tokens/sec", "sequences_per_sec": round(sps, 2), "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1000, 2), "higher_is_better": True,
-        "dtype": args.dtype, "impl": args.impl, "hip_graph": bool(args.graph and args.impl == "dl4j"), "data": "synthetic token ids; random-init weights",
+        "dtype": args.dtype, "impl": args.impl, "dropout": args.dropout, "hip_graph": bool(args.graph and args.impl == "dl4j"), "data": "synthetic token ids; random-init weights",
         "config": {"model": f"BERT-base ({args.layers} layers, 768 hidden, 12 heads) + classifier",
                    "batch": args.batch, "seq_len": args.seq, "params": nparams}, "final_score": score()}),
           flush=True)
