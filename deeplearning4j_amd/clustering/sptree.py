@@ -10,16 +10,6 @@ import torch
 
 from ..ops import runtime as RT
 
-c_void_p, c_int, c_double, c_ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_longlong
-RT.register("rt_sptree_build", [c_void_p, c_int, c_int], c_void_p)
-RT.register("rt_sptree_free", [c_void_p], None)
-RT.register("rt_sptree_depth", [c_void_p], c_int)
-RT.register("rt_sptree_cum", [c_void_p], c_int)
-RT.register("rt_sptree_com", [c_void_p, c_void_p], None)
-RT.register("rt_sptree_nonedge", [c_void_p, c_int, c_double, c_void_p], c_double)
-RT.register("rt_bhtsne_gradient", [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int],
-            c_double)
-
 
 class SpTree:
     def __init__(self, data):

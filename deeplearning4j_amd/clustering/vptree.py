@@ -13,11 +13,6 @@ import torch
 from ..ops import runtime as RT
 from .distances import DISTANCES
 
-c_void_p, c_int, c_ull, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_double
-RT.register("rt_vptree_build", [c_void_p, c_int, c_int, c_int, c_int, c_ull], c_void_p)
-RT.register("rt_vptree_free", [c_void_p], None)
-RT.register("rt_vptree_knn", [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int], None)
-
 
 class DataPoint:
     def __init__(self, index, point, invert=False):

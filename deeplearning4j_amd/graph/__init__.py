@@ -19,10 +19,6 @@ import torch
 from ..nlp.embeddings import EmbeddingEngine, F_HS, F_UPD_IN, F_UPD_OUT, InMemoryLookupTable, M_SG
 from ..ops import runtime as RT
 
-c_void_p, c_int, c_ll, c_ull = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong
-RT.register("rt_random_walks", [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_ull, c_int, c_void_p, c_int],
-            c_ll)
-
 
 class NoEdgesException(Exception):
     pass

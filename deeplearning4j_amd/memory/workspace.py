@@ -217,8 +217,8 @@ class MemoryWorkspace:
         for s in shape:
             n *= s
         nbytes = n * torch.empty((), dtype=dtype).element_size()
-        off = _rt.c_ll(0)
-        gen = _rt.c_ll(0)
+        off = ctypes.c_longlong(0)
+        gen = ctypes.c_longlong(0)
         rc = self._lib.rt_ws_alloc(self._h, nbytes, ctypes.byref(off), ctypes.byref(gen))
         if rc == 0 and self._buf is not None and off.value + nbytes <= self._buf.numel():
             t = self._buf[off.value:off.value + nbytes].view(dtype).view(shape)

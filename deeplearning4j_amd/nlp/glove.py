@@ -5,30 +5,12 @@ models/glove/AbstractCoOccurrences.java (windowed co-occurrences weighted 1/dist
 models/embeddings/learning/impl/elements/GloVe.java:182-225 (tied word/context matrix, per-row bias, AdaGrad on
 both; loss f(x)(w_i.w_j + b_i + b_j - log x)^2 with f(x) = min(1, (x/xMax)^alpha)).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from ..ops import runtime as RT
 from .embeddings import InMemoryLookupTable, _np_ptr, _t_ptr
 from .word2vec import Word2Vec, _BaseBuilder
-
-c_void_p, c_int, c_ll, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, \
-    ctypes.c_double
-RT.register("rt_glove_cooccur_new", [c_void_p, c_void_p, c_ll, c_int, c_int], c_void_p)
-RT.register("rt_glove_cooccur_size", [c_void_p], c_ll)
-RT.register("rt_glove_cooccur_fetch", [c_void_p, c_void_p, c_void_p, c_void_p, c_ll], c_ll)
-RT.register("rt_glove_cooccur_free", [c_void_p], None)
-RT.register("rt_glove_apply", [c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                               c_float, c_float, c_float, c_int], c_double)
-
-
-RT.register("rt_cooc_new", [ctypes.c_char_p, c_ll], c_void_p)
-RT.register("rt_cooc_add", [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int], c_int)
-RT.register("rt_cooc_spills", [c_void_p], c_ll)
-RT.register("rt_cooc_finish", [c_void_p, ctypes.c_char_p], c_ll)
-RT.register("rt_cooc_free", [c_void_p], None)
 
 # one merged co-occurrence record as the native counter writes it
 COOC_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("x", "<f4")])
@@ -258,8 +240,6 @@ class Glove(Word2Vec):
         if gpu:
             from ..ops import native
             lib = native.load()
-            native.register_sig("dl4j_glove", [c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
-                                               c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_int, c_void_p])
             cost = torch.zeros(1, device=dev)
             di, dj, dx = (torch.from_numpy(a).to(dev) for a in (ei, ej, ex))
         rt = RT.load()
@@ -273,7 +253,7 @@ class Glove(Word2Vec):
                 cost.zero_()
                 rc = lib.dl4j_glove(_t_ptr(a), _t_ptr(bb), _t_ptr(x), len(ei), _t_ptr(W), _t_ptr(b), _t_ptr(hW),
                                     _t_ptr(hb), D, c.learningRate, self.xMax, self.alpha, _t_ptr(cost),
-                                    max(1, min(8192, V // 32)), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                    max(1, min(8192, V // 32)), torch.cuda.current_stream(dev).cuda_stream)
                 if rc != 0:
                     raise RuntimeError(f"dl4j_glove failed ({rc})")
                 self.lossHistory.append(float(cost.item()))
@@ -311,8 +291,6 @@ class Glove(Word2Vec):
         if gpu:
             from ..ops import native
             lib = native.load()
-            native.register_sig("dl4j_glove", [c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
-                                               c_void_p, c_int, c_float, c_float, c_float, c_void_p, c_int, c_void_p])
             cost = torch.zeros(1, device=dev)
         n, B = len(table), max(1, int(self.streamBlock))
         for _ in range(max(1, c.epochs) * max(1, c.iterations)):
@@ -332,7 +310,7 @@ class Glove(Word2Vec):
                     rc = lib.dl4j_glove(_t_ptr(da), _t_ptr(db_), _t_ptr(dx), len(a), _t_ptr(W), _t_ptr(b),
                                         _t_ptr(hW), _t_ptr(hb), D, c.learningRate, self.xMax, self.alpha,
                                         _t_ptr(cost), max(1, min(8192, V // 32)),
-                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                        torch.cuda.current_stream(dev).cuda_stream)
                     if rc != 0:
                         raise RuntimeError(f"dl4j_glove failed ({rc})")
                 else:

@@ -9,17 +9,10 @@ import torch
 
 from . import native, runtime
 from .dispatch import use_native
-from .native import _ptr, _stream, c_float, c_int, c_ll, c_void_p
+from .native import _ptr, _stream
 
 HEADER = 4
 SPARSE, BITMAP = 0, 1
-
-native.register_sig("dl4j_threshold_encode", [c_void_p, c_ll, c_float, c_void_p, c_int, c_void_p, c_void_p])
-native.register_sig("dl4j_threshold_count", [c_void_p, c_ll, c_float, c_void_p, c_void_p, c_void_p])
-native.register_sig("dl4j_threshold_decode", [c_void_p, c_void_p, c_int, c_float, c_void_p])
-native.register_sig("dl4j_bitmap_encode", [c_void_p, c_ll, c_float, c_void_p, c_void_p, c_void_p])
-native.register_sig("dl4j_bitmap_decode", [c_void_p, c_ll, c_void_p, c_float, c_void_p])
-native.register_sig("dl4j_decode_any", [c_void_p, c_ll, c_int, c_void_p, c_float, c_void_p])
 
 
 def _ws_ints(n):

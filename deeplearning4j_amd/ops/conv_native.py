@@ -21,34 +21,7 @@ import torch
 from ..memory import arena
 
 from . import autotune, native, nd4j_kernels, side_stream
-from .native import _ptr, _stream, c_int, c_ll, c_void_p
-
-native.register_sig("dl4j_conv_w_relayout", [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
-native.register_sig("dl4j_conv_w_relayout_batched", [c_void_p, c_int, c_ll, c_void_p])
-native.register_sig("dl4j_conv_relayout_job_bytes", [])
-native.register_sig("dl4j_conv_relayout_per_block", [])
-native.register_sig("dl4j_conv_w_relayout_tiled", [c_void_p, c_int, c_ll, c_void_p])
-native.register_sig("dl4j_conv_relayout_tile_job_bytes", [])
-native.register_sig("dl4j_conv_relayout_tile_max_rs", [])
-native.register_sig("dl4j_conv_fwd", [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 + [c_void_p, c_void_p])
-native.register_sig("dl4j_conv_bwd_data_s1", [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p])
-native.register_sig("dl4j_conv_bwd_data_1x1", [c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p])
-native.register_sig("dl4j_conv_wrw", [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 16 + [c_void_p])
-native.register_sig("dl4j_conv_set_variant", [c_int])
-native.register_sig("dl4j_conv_set_wrw_variant", [c_int])
-native.register_sig("dl4j_conv_set_wrw_remap", [c_int])
-native.register_sig("dl4j_conv_wrw_permute", [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p])
-native.register_sig("dl4j_conv_wrw_det", [c_void_p] * 5 + [c_int] * 17 + [c_void_p])
-native.register_sig("dl4j_conv_wrw_det_floats", [c_int] * 8, restype=c_ll)
-native.register_sig("dl4j_conv_fwd_v3", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 +
-                    [ctypes.c_float, c_void_p, c_int, c_void_p])
-native.register_sig("dl4j_conv_v3_num_variants", [])
-native.register_sig("dl4j_conv_v3_default_variant", [c_ll, c_int])
-native.register_sig("dl4j_conv_wrw_v3_num_variants", [])
-native.register_sig("dl4j_conv_wrw_v3_ws_floats", [c_int] * 9 + [ctypes.POINTER(c_int)], restype=c_ll)
-native.register_sig("dl4j_conv_wrw_v3", [c_int] + [c_void_p] * 5 + [c_int] * 17 + [c_void_p])
-native.register_sig("dl4j_conv_wrw_halo_ws_floats", [c_int] * 17 + [ctypes.POINTER(c_int)], restype=c_ll)
-native.register_sig("dl4j_conv_wrw_halo", [c_int] + [c_void_p] * 5 + [c_int] * 17 + [c_void_p])
+from .native import _ptr, _stream
 
 # Optional per-shape override of the weight-gradient split count (tuning): {(N,H,W,C,K,R,S,stride): splits}
 WRW_SPLITS = {}
@@ -380,11 +353,6 @@ def _stats_buf(variant, M, K, device, geom=None):
 
 STREAM_VAR = 100     # persistent loader/consumer conv kernel (csrc/gemm_stream.hip conv_stream), a tuner candidate
 HALO_VAR = 101       # halo-staged 3x3 / 64-channel kernel (csrc/conv_halo.hip), a tuner candidate
-native.register_sig("dl4j_conv_halo_plan", [c_int] * 15 + [ctypes.POINTER(c_int)], restype=c_ll)
-native.register_sig("dl4j_conv_halo", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 +
-                    [ctypes.c_float, c_void_p, c_void_p])
-native.register_sig("dl4j_conv_stream", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 15 +
-                    [ctypes.c_float, c_void_p, c_void_p])
 _HALO_PLANS = {}
 
 

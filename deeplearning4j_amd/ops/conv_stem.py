@@ -1,12 +1,10 @@
 """ResNet stem convolution (7x7 / stride 2 / pad 3, 3 -> 64 channels, NHWC bf16) on the dedicated MFMA kernel in
 csrc/conv_stem.hip (the generic implicit-GEMM kernels need C % 8 == 0). Weight layout for the kernel: B[k][n] with
 k = r*24 + s*3 + c (K padded to 192), fragment-packed as [4 n-tiles][6 k-steps][64 lanes][8]."""
-import ctypes
-
 import torch
 
 from . import native
-from .native import _ptr, _stream, c_int, c_void_p
+from .native import _ptr, _stream
 
 _packed = {}
 
@@ -32,8 +30,7 @@ def pack_weights(w):
         ent = _packed[key] = {"pk": torch.empty(4, 6, 64, 8, dtype=torch.bfloat16, device=w.device), "v": -1}
     if ent["v"] != WEIGHT_VERSION[0] or not is_managed(w.data_ptr()):
         lib = native.load()
-        native.register_sig("dl4j_stem_pack_weights", [c_void_p, c_void_p] + [ctypes.c_longlong] * 4 + [c_void_p])
-        rc = lib.dl4j_stem_pack_weights(_ptr(w), _ptr(ent["pk"]), *[int(t) for t in w.stride()], c_void_p(_stream()))
+        rc = lib.dl4j_stem_pack_weights(_ptr(w), _ptr(ent["pk"]), *[int(t) for t in w.stride()], _stream())
         native._check(rc, "stem_pack_weights")
         ent["v"] = WEIGHT_VERSION[0]
     return ent["pk"]
@@ -52,11 +49,10 @@ def forward(x, w, want_stats=False):
     N, _, H, W = x.shape
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     lib = native.load()
-    native.register_sig("dl4j_stem_conv_fwd", [c_void_p] * 4 + [c_int] * 5 + [c_void_p])
     y = torch.empty((N, 64, OH, OW), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
     ts = torch.empty((3, N * OH, 64), dtype=torch.float32, device=x.device) if want_stats else None
     rc = lib.dl4j_stem_conv_fwd(_ptr(x), _ptr(pack_weights(w)), _ptr(y), _ptr(ts), N, H, W, OH, OW,
-                                c_void_p(_stream()))
+                                _stream())
     if rc == -1:
         return None
     native._check(rc, "stem_conv_fwd")
@@ -74,9 +70,6 @@ def backward_weight(x, dy, gW=None, gb=None, need_db=False):
     N, _, H, W = x.shape
     OH, OW = dy.shape[2], dy.shape[3]
     lib = native.load()
-    native.register_sig("dl4j_stem_conv_wrw", [c_void_p] * 5 + [c_int] * 5 + [c_void_p])
-    native.register_sig("dl4j_stem_wrw_workspace_floats", [c_int, c_int])
-    lib.dl4j_stem_wrw_workspace_floats.restype = ctypes.c_longlong
     key = str(x.device)
     nws = lib.dl4j_stem_wrw_workspace_floats(N, OH)
     ws = _ws.get(key)
@@ -89,7 +82,7 @@ def backward_weight(x, dy, gW=None, gb=None, need_db=False):
         directb = gb is not None and gb.dtype == torch.float32 and gb.is_contiguous() and gb.numel() == 64
         db = gb.reshape(-1) if directb else torch.empty(64, dtype=torch.float32, device=x.device)
     rc = lib.dl4j_stem_conv_wrw(_ptr(x), _ptr(dy), _ptr(dW), _ptr(db), _ptr(ws), N, H, W, OH, OW,
-                                c_void_p(_stream()))
+                                _stream())
     if rc == -1:
         return "unsupported"
     native._check(rc, "stem_conv_wrw")

@@ -28,30 +28,13 @@ _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 ACT = {None: 0, "identity": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "gelu": 4,
        "dgelu": 5}                                      # dgelu: out *= gelu'(z), z READ from the ``z`` buffer
 _c = ctypes
-_sig_done = [False]
 _env = os.environ.get("DL4J_AMD_GEMM_CFG")          # "cfg,splits" override for tuning sweeps
 _FORCE_CFG = tuple(int(v) for v in _env.split(",")) if _env else None
 
 
 def _lib():
     from . import native
-    lib = native.load()
-    if not _sig_done[0]:
-        V, I, LL, F = _c.c_void_p, _c.c_int, _c.c_longlong, _c.c_float
-        lib.dl4j_gemm_plan.argtypes = [I, I, I, I, _c.POINTER(I), _c.POINTER(I)]
-        lib.dl4j_gemm_plan.restype = LL
-        lib.dl4j_gemm.argtypes = [I, I, I, I, I, I, V, LL, I, LL, V, LL, I, LL, V, LL, LL, F, F, V, I, I, V, I, I, V, V, I,
-                                  V]
-        lib.dl4j_gemm.restype = I
-        lib.dl4j_gemm_simple.argtypes = [I, I, I, I, I, I, V, LL, LL, LL, V, LL, LL, LL, V, LL, LL, F, F, V, I, I, V, V]
-        lib.dl4j_gemm_simple.restype = I
-        lib.dl4j_gemm_f32_plan.argtypes = [I, I, I, I, _c.POINTER(I), _c.POINTER(I)]
-        lib.dl4j_gemm_f32_plan.restype = LL
-        lib.dl4j_gemm_f32.argtypes = [I, I, I, I, I, I, V, LL, LL, LL, V, LL, LL, LL, V, LL, LL, F, F, V, I, I, V, I, I,
-                                      V, V]
-        lib.dl4j_gemm_f32.restype = I
-        _sig_done[0] = True
-    return lib
+    return native.load()
 
 
 _TUNED = {}                                            # problem key -> (cfg, splits), filled by _autotune
@@ -478,14 +461,11 @@ def native_gelu_(z, dy, out=None):
     """On the in-tree GELU kernel (csrc/activations.hip): dy *= gelu'(z) in place, or with dy None out = gelu(z);
     0 or an error code."""
     from .native import _stream
-    from . import transformer_native as TN
     d = _DT.get(z.dtype)
     dst = dy if dy is not None else out
     if d is None or not (z.is_contiguous() and dst.is_contiguous()) or dst.dtype != z.dtype:
         return -1
-    TN.native.register_sig("dl4j_gelu", [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_longlong,
-                                         _c.c_void_p])
-    return _lib().dl4j_gelu(d, _p(z), _p(dy), _p(dst), z.numel(), _c.c_void_p(_stream()))
+    return _lib().dl4j_gelu(d, _p(z), _p(dy), _p(dst), z.numel(), _stream())
 
 
 def bias_vec(b):

@@ -1,4 +1,9 @@
-"""ctypes bindings of ``libdl4j_amd_kernels.so`` (gfx950 HIP kernels, C ABI) + torch-facing wrappers.
+"""Loader of ``libdl4j_amd_kernels.so`` (gfx950 HIP kernels, C ABI) + torch-facing wrappers.
+
+The ctypes signature of every ``dl4j_*`` entry point comes from the generated C ABI header
+``csrc/include/dl4j_amd.h`` (ops/abi.py), bound once when the library is loaded; nothing here or in the other wrapper
+modules types a signature by hand. To add an entry point: write the ``DL4J_API`` function, run
+``python tools/gen_abi_header.py``, call it.
 
 Every wrapper launches on torch's current HIP stream (so HIP-graph capture and stream ordering work),
 allocates outputs/workspaces through torch's caching allocator, and returns ``None`` when a shape is
@@ -12,9 +17,11 @@ import threading
 import numpy as np
 import torch
 
+from . import abi
 from .build import KERNEL_LIB
 
 _lib = None
+_load_lock = threading.Lock()
 c_void_p, c_int, c_ll, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 
 
@@ -22,50 +29,16 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(KERNEL_LIB):
-        if os.environ.get("DL4J_AMD_AUTOBUILD", "1") == "1":
-            from .build import build_kernels
-            build_kernels(verbose=False)
-        else:
-            raise FileNotFoundError(KERNEL_LIB)
-    lib = ctypes.CDLL(KERNEL_LIB)
-    sigs = {
-        "dl4j_fused_update": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
-                              c_int, c_void_p, c_void_p, c_void_p],
-        "dl4j_update_chunk": [],
-        "dl4j_segdesc_size": [],
-        "dl4j_bn_workspace_floats": [c_ll, c_int],
-        "dl4j_bn_fwd": [c_int, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_float, c_float,
-                        c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-        "dl4j_bn_bwd": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                        c_void_p, c_int, c_void_p, c_void_p, c_void_p],
-        "dl4j_softmax_xent": [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
-                              c_void_p],
-        "dl4j_pool_fwd": [c_int, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p],
-        "dl4j_pool_bwd": [c_int, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p],
-    }
-    for name, args in sigs.items():
-        f = getattr(lib, name)
-        f.argtypes = args
-        f.restype = c_int
-    for name, (args, restype) in _EXTRA_SIGS.items():
-        if hasattr(lib, name):
-            f = getattr(lib, name)
-            f.argtypes = args
-            f.restype = restype
-    _lib = lib
-    return lib
-
-
-_EXTRA_SIGS = {}
-
-
-def register_sig(name, args, restype=c_int):
-    _EXTRA_SIGS[name] = (args, restype)
-    if _lib is not None and hasattr(_lib, name):
-        f = getattr(_lib, name)
-        f.argtypes = args
-        f.restype = restype
+    with _load_lock:
+        if _lib is None:
+            if not os.path.exists(KERNEL_LIB):
+                if os.environ.get("DL4J_AMD_AUTOBUILD", "1") == "1":
+                    from .build import build_kernels
+                    build_kernels(verbose=False)
+                else:
+                    raise FileNotFoundError(KERNEL_LIB)
+            _lib = abi.bind(ctypes.CDLL(KERNEL_LIB), "dl4j_")
+    return _lib
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -304,8 +277,6 @@ def fused_update(plan, params, grad, state, iteration, epoch, div, shadow, write
         if reg_part is None or reg_part.numel() < cache.nblocks or reg_part.device != params.device:
             reg_part = cache.reg_partial = torch.empty(max(cache.nblocks, 1), dtype=torch.float32,
                                                        device=params.device)
-        register_sig("dl4j_fused_update_regpart", [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                   c_int, c_float, c_int, c_void_p, c_void_p, c_void_p])
         rc = lib.dl4j_fused_update_regpart(_ptr(st.dev), _ptr(cache.btab), cache.nblocks, _ptr(params), _ptr(grad),
                                            _ptr(state), _ptr(shadow), sk, 1.0 / div, 1 if write_update else 0,
                                            _ptr(reg_part), _ptr(gn_part), _stream())
@@ -325,7 +296,6 @@ def score_reduce(s, add, scale, reg=None, reg_scale=0.0, out=None):
     """out[0] = (sum(s) + add) * scale + reg[0] * reg_scale on one HIP block (fixed order; csrc/softmax_xent.hip).
     s: contiguous fp32 CUDA tensor; returns ``out`` (a fresh 0-d tensor when not given)."""
     lib = load()
-    register_sig("dl4j_score_reduce", [c_void_p, c_ll, c_float, c_float, c_void_p, c_float, c_void_p, c_void_p])
     if out is None:
         out = torch.empty((), dtype=torch.float32, device=s.device)
     rc = lib.dl4j_score_reduce(_ptr(s), s.numel(), float(add), float(scale), _ptr(reg), float(reg_scale), _ptr(out),
@@ -379,11 +349,6 @@ def bn_fwd(x, gamma, beta, run_mean, run_var, training, decay, eps, relu, residu
     rpp = _tile_rpp(ts, M, C) if training and dt in (1, 2) else None
     if rpp is not None:
         # statistics already reduced per tile by the producing conv kernel's epilogue
-        register_sig("dl4j_bn_fwd_tiles", [c_int, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_ll, c_int,
-                                           c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_float, c_float,
-                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p])
-        register_sig("dl4j_bn_tiles_workspace_floats", [c_ll, c_int])
-        lib.dl4j_bn_tiles_workspace_floats.restype = c_ll
         wst = _ae((lib.dl4j_bn_tiles_workspace_floats(ts[1], C),), torch.float32, x.device)
         rc = lib.dl4j_bn_fwd_tiles(dt, _ptr(xr), _ptr(res), _ptr(y), M, C, _ptr(ts[0]), ts[1], rpp, _ptr(g), _ptr(b),
                                    float(gamma) if g is None else 1.0, float(beta) if b is None else 0.0,
@@ -428,12 +393,7 @@ def _bn_fwd_rbn(lib, x, xr, dt, M, C, gamma, beta, run_mean, run_var, decay, eps
     ts = getattr(x, "_bn_tile_stats", None)
     rpp = _tile_rpp(ts, M, C)
     tiles = rpp is not None
-    register_sig("dl4j_bn_fwd_rbn", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                     c_float, c_float, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_ll, c_int, c_void_p])
     if tiles:
-        register_sig("dl4j_bn_tiles_workspace_floats", [c_ll, c_int])
-        lib.dl4j_bn_tiles_workspace_floats.restype = c_ll
         ws = _ae((lib.dl4j_bn_tiles_workspace_floats(ts[1], C),), torch.float32, x.device)
     else:
         ws = _ae((lib.dl4j_bn_workspace_floats(M, C),), torch.float32, x.device)
@@ -476,7 +436,6 @@ class bnb_armed:
         self.req = req
 
     def __enter__(self):
-        register_sig("dl4j_bnb_arm", [c_void_p, c_void_p, c_void_p, c_int])
         xr, ctx, relu, mask = self.req
         load().dl4j_bnb_arm(_ptr(xr), _ptr(ctx), _ptr(mask), 3 if mask is not None else (2 if relu else 1))
         return self
@@ -518,11 +477,6 @@ def bn_bwd(dy, ctx, dgamma_out=None, dbeta_out=None, rgrads=None):
         rg = rgrads if rgrads is not None else (None, None)
         dg2 = rg[0] if ok(rg[0]) else _ae((C,), torch.float32, x.device)
         db2 = rg[1] if ok(rg[1]) else _ae((C,), torch.float32, x.device)
-        register_sig("dl4j_bn_bwd_rbn_workspace_floats", [c_ll, c_int])
-        lib.dl4j_bn_bwd_rbn_workspace_floats.restype = c_ll
-        register_sig("dl4j_bn_bwd_rbn", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p])
         ws = _ae((lib.dl4j_bn_bwd_rbn_workspace_floats(M, C),), torch.float32, x.device)
         rc = lib.dl4j_bn_bwd_rbn(_dt16(x), _ptr(x), _ptr(res), _ptr(dy), _ptr(dx), _ptr(dres), M, C, _ptr(c),
                                  _ptr(dgamma), _ptr(dbeta), _ptr(rctx), _ptr(dg2), _ptr(db2), _ptr(ws), _ptr(mask),
@@ -534,10 +488,6 @@ def bn_bwd(dy, ctx, dgamma_out=None, dbeta_out=None, rgrads=None):
                     dst.copy_(src.reshape(dst.shape))
         return dx, dgamma, dbeta, dres
     if planes is not None:
-        register_sig("dl4j_bn_bwd_planes_workspace_floats", [c_ll, c_int])
-        lib.dl4j_bn_bwd_planes_workspace_floats.restype = c_ll
-        register_sig("dl4j_bn_bwd_planes", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int,
-                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_void_p])
         P = planes.shape[1]
         ws = _ae((lib.dl4j_bn_bwd_planes_workspace_floats(P, C),), torch.float32, x.device)
         rc = lib.dl4j_bn_bwd_planes(_dt16(x), _ptr(x), _ptr(dy), _ptr(dx), _ptr(dres), _ptr(mask if dres is not None
@@ -571,9 +521,6 @@ def bn_pool_fwd(x, gamma, beta, run_mean, run_var, training, decay, eps, kernel,
     if OH < 1 or OW < 1 or kh * kw > 127:
         return None
     lib = load()
-    register_sig("dl4j_bn_pool_fwd", [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 12 +
-                 [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_ll,
-                  c_int, c_void_p, c_void_p, c_void_p])
     y = _ae((N, C, OH, OW), x.dtype, x.device, channels_last=True)
     am = _ae((N * OH * OW * C,), torch.uint8, x.device) if training else None
     xh = _ae((N, C, OH, OW), x.dtype, x.device, channels_last=True) if training else None
@@ -585,8 +532,6 @@ def bn_pool_fwd(x, gamma, beta, run_mean, run_var, training, decay, eps, kernel,
         ts = None
     nws = lib.dl4j_bn_workspace_floats(M, C)
     if ts is not None:
-        register_sig("dl4j_bn_tiles_workspace_floats", [c_ll, c_int])
-        lib.dl4j_bn_tiles_workspace_floats.restype = c_ll
         nws = max(nws, lib.dl4j_bn_tiles_workspace_floats(ts[1], C))
     ws = _ae((nws,), torch.float32, x.device)
     ctx = _ae((4 * C,), torch.float32, x.device)
@@ -607,7 +552,6 @@ def bn_pool_bwd(dy, ctx, dgamma_out=None, dbeta_out=None):
     N, C, H, W = x.shape
     dy = _rows_like(dy, xh)
     lib = load()
-    register_sig("dl4j_bn_pool_bwd", [c_int] + [c_void_p] * 5 + [c_int] * 12 + [c_void_p] * 4 + [c_void_p])
     dx = _ae(x.shape, x.dtype, x.device, channels_last=True)
     ok = lambda t: t is not None and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C  # noqa
     dgamma = dgamma_out if ok(dgamma_out) else _ae((C,), torch.float32, x.device)
@@ -639,8 +583,6 @@ def softmax_xent(logits, labels, clip_eps, row_mask=None):
         m = row_mask.reshape(-1).to(torch.float32).contiguous()
         if m.numel() != B:
             return None
-        register_sig("dl4j_softmax_xent_masked", [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                                  c_void_p, c_float, c_void_p])
         rc = load().dl4j_softmax_xent_masked(dt, _ptr(logits), _ptr(lab), B, V, _ptr(grad), _ptr(score), _ptr(m),
                                              float(clip_eps or 0.0), _stream())
         _check(rc, "softmax_xent_masked")
@@ -659,8 +601,6 @@ def softmax_xent_strided(logits, y, mb, ys, clip_eps):
     if dt is None or logits.dim() != 2 or logits.stride(1) != 1 or y.dtype != torch.float32 or not y.is_cuda:
         return None
     B, V = logits.shape
-    register_sig("dl4j_softmax_xent_strided", [c_int, c_void_p, c_int, c_void_p, c_ll, c_ll, c_ll, c_int, c_int, c_int,
-                                               c_void_p, c_int, c_void_p, c_float, c_void_p])
     from ..memory import arena
     from .gemm import kz_view
     V8 = (V + 7) // 8 * 8
@@ -724,8 +664,6 @@ def segment_stats(flat, offsets, bins=0):
     fp32/bf16 CUDA tensor, one fused HIP launch for all segments (csrc/stats.hip). ``offsets``: list of nseg+1
     element offsets. Returns (stats [nseg, 5] float32, hist [nseg, bins] int64 or None) on the device."""
     lib = load()
-    register_sig("dl4j_segment_stats", [c_int, c_void_p, c_void_p, c_int, c_ll, c_void_p, c_void_p, c_int,
-                                        c_void_p, c_void_p])
     dt = _dt(flat)
     if dt is None or not flat.is_contiguous():
         raise ValueError("segment_stats needs a contiguous fp32/bf16 tensor")
@@ -739,7 +677,7 @@ def segment_stats(flat, offsets, bins=0):
     hist = torch.empty(nseg, bins, dtype=torch.int32, device=dev) if bins > 0 else None
     maxlen = max(b - a for a, b in zip(offsets[:-1], offsets[1:])) if nseg else 0
     rc = lib.dl4j_segment_stats(dt, _ptr(flat), _ptr(off), nseg, maxlen, _ptr(ws), _ptr(out), bins, _ptr(hist),
-                                c_void_p(_stream()))
+                                _stream())
     _check(rc, "segment_stats")
     return out, (hist.to(torch.int64) if hist is not None else None)
 
@@ -751,13 +689,11 @@ def channel_sum(rows, out=None):
     if dt is None or rows.dim() != 2 or not rows.is_contiguous() or rows.shape[1] == 0:
         return None
     lib = load()
-    register_sig("dl4j_channel_sum", [c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p])
-    register_sig("dl4j_channel_sum_ws_floats", [c_ll, c_int], restype=c_ll)
     if out is None or not (out.is_contiguous() and out.dtype == torch.float32 and out.numel() == rows.shape[1]):
         out = torch.empty(rows.shape[1], dtype=torch.float32, device=rows.device)
     ws = _scratch(lib.dl4j_channel_sum_ws_floats(rows.shape[0], rows.shape[1]), rows.device)
     _check(lib.dl4j_channel_sum(dt, _ptr(rows), rows.shape[0], rows.shape[1], _ptr(out), _ptr(ws),
-                                c_void_p(_stream())), "channel_sum")
+                                _stream()), "channel_sum")
     return out
 
 

@@ -13,28 +13,7 @@ import ctypes
 import torch
 
 from . import native
-from .native import _ptr, _stream, c_int, c_ll, c_void_p
-
-native.register_sig("dl4j_transform", [c_int, c_int, c_void_p, c_void_p, c_ll, ctypes.c_float, ctypes.c_float,
-                                       c_void_p])
-native.register_sig("dl4j_transform_bp", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll, ctypes.c_float, c_void_p])
-native.register_sig("dl4j_binary", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_int, c_void_p])
-native.register_sig("dl4j_reduce_segments", [c_ll, c_ll, c_ll])
-native.register_sig("dl4j_reduce_ws_bytes", [c_ll, c_ll, c_ll], restype=c_ll)
-native.register_sig("dl4j_reduce", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_ll, c_int, c_void_p,
-                                    c_void_p])
-native.register_sig("dl4j_strided_copy", [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_ll, c_void_p])
-native.register_sig("dl4j_strided_copy2", [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_ll, c_void_p])
-native.register_sig("dl4j_col2im", [c_int, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p])
-native.register_sig("dl4j_mergemax", [c_int, c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p])
-native.register_sig("dl4j_mergemax_bp", [c_int, c_void_p, c_void_p, c_void_p, c_int, c_ll, c_void_p])
-native.register_sig("dl4j_fill", [c_void_p, c_ll, ctypes.c_uint, c_void_p])
-native.register_sig("dl4j_axpy", [c_int, c_void_p, c_void_p, c_ll, ctypes.c_float, c_void_p])
-native.register_sig("dl4j_im2col_rows", [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p])
-native.register_sig("dl4j_col2im_rows", [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p])
+from .native import _ptr, _stream
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 CALLS = __import__("collections").Counter()     # kernel launches per entry point (tests check the GPU path ran)

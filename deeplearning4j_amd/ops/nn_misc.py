@@ -15,34 +15,9 @@ import torch.nn.functional as F
 from .dispatch import use_native
 from .fallback import note
 
-c_void_p, c_int, c_ll, c_float, c_ull = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, \
-    ctypes.c_ulonglong
-
-_SIGS = {
-    "dl4j_lrn_fwd": [c_int, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_ll, c_ll, c_ll, c_int, c_float,
-                     c_float, c_float, c_int, c_void_p],
-    "dl4j_lrn_bwd": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_ll, c_ll, c_ll, c_int,
-                     c_float, c_float, c_int, c_void_p],
-    "dl4j_dropout": [c_int, c_void_p, c_void_p, c_ll, c_ull, c_void_p, c_int, c_int, c_float, c_float, c_float,
-                     c_float, c_float, c_void_p],
-    "dl4j_emb_gather": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_ll, c_int, c_void_p],
-    "dl4j_emb_scatter_add": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_ll, c_int, c_void_p],
-    "dl4j_bert_embed_fwd": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_ll, c_ll,
-                            c_int, c_void_p],
-    "dl4j_bert_embed_bwd_pt": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ll, c_ll, c_int, c_ll,
-                               c_ll, c_void_p],
-    "dl4j_dwconv_fwd": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "dl4j_dwconv_bwd_data": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "dl4j_dwconv_bwd_weight": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-}
-
-
 def _lib():
     from . import native
-    lib = native.load()
-    for n, a in _SIGS.items():
-        native.register_sig(n, a)
-    return lib
+    return native.load()
 
 
 def _dt(t):
@@ -50,12 +25,12 @@ def _dt(t):
 
 
 def _p(t):
-    return None if t is None else c_void_p(t.data_ptr())
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _s():
     from .native import _stream
-    return c_void_p(_stream())
+    return _stream()
 
 
 def _check(rc, what):
@@ -156,7 +131,7 @@ def dropout_native(x, mode, stream, bwd, p=1.0, a=1.0, b=0.0, alpha_p=0.0, sd=0.
         return None
     x = _dense(x)
     y = torch.empty_like(x)
-    _check(_lib().dl4j_dropout(_dt(x), _p(x), _p(y), x.numel(), c_ull(stream.seed), _p(stream.offset),
+    _check(_lib().dl4j_dropout(_dt(x), _p(x), _p(y), x.numel(), stream.seed, _p(stream.offset),
                                MODES[mode], int(bwd), float(p), float(a), float(b), float(alpha_p), float(sd),
                                _s()), "dropout")
     return y

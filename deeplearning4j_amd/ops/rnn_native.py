@@ -15,11 +15,6 @@ from . import native, nd4j_kernels
 from ..memory import arena
 from .native import _check, _ptr, _stream, c_int, c_void_p
 
-_SIG_FWD = [c_int] + [c_void_p] * 12 + [c_int, c_int, c_int, c_void_p]
-_SIG_BWD = [c_int, c_void_p, c_int] + [c_void_p] * 11 + [c_int, c_int, c_int, c_int, c_void_p]
-_SIG_PACK = [c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-
-
 _DTC = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
@@ -71,7 +66,6 @@ def pack_rw(RW, H, peephole, need_bwd=True):
     if not RW.is_cuda or not supported(H, dt) or RW.dim() != 2 or RW.shape[0] != H:
         return None
     lib = native.load()
-    native.register_sig("dl4j_lstm_pack_rw", _SIG_PACK)
     fe = 8 if dt in (torch.bfloat16, torch.float16) else 4
     shape = lambda n, k: (n // 16, k // (4 * fe), 4, 16, fe)  # noqa: E731
     fwd = arena.empty(shape(4 * H, H), dt, RW.device)
@@ -83,9 +77,6 @@ def pack_rw(RW, H, peephole, need_bwd=True):
         return None
     _check(rc, "lstm_pack_rw")
     return RWPacks(fwd, bwd, peep, H, dt)
-
-
-_SIG_COOP = [c_void_p] * 14 + [c_int, c_int, c_int, ctypes.c_uint, c_int, c_void_p]
 
 
 _DEV_TAG = 0xFFFFFFFF          # csrc/lstm_coop.hip kDevTag: granule tags tracked on the device (no per-launch memset)
@@ -189,7 +180,6 @@ def _concurrent_streams():
 
 
 def _launch_mode(lib):
-    native.register_sig("dl4j_lstm_coop_launch_mode", [c_int])
     lib.dl4j_lstm_coop_launch_mode(1 if _concurrent_streams() else -1)
     USED_COOP[0] = True
 
@@ -205,9 +195,6 @@ def check_step_guard(device):
         return
     import collections
     lib = native.load()
-    native.register_sig("dl4j_lstm_step_guard", [])
-    native.register_sig("dl4j_lstm_step_guard_reset", [c_void_p])
-    lib.dl4j_lstm_step_guard.restype = c_void_p
     q = _guard.get(device.index)
     if q is None:
         q = _guard[device.index] = collections.deque()
@@ -218,7 +205,7 @@ def check_step_guard(device):
         if int(snap[0]) != 0:
             tripped = True
     if tripped:
-        lib.dl4j_lstm_step_guard_reset(c_void_p(_stream()))
+        lib.dl4j_lstm_step_guard_reset(_stream())
         q.clear()                      # younger snapshots may hold the same (now cleared) trip
         raise CoopTimeoutError("cooperative LSTM kernel: a cross-workgroup hand-off timed out; the fused updater "
                                "skipped the update of every step since (parameters unchanged)")
@@ -254,15 +241,12 @@ def _coop_enabled():
 
 def _fwd_coop(lib, zx, rwt, peep, h0c, c0c, m, out, out16, gates, call, hT, cT, T, mb, H):
     """Cooperative multi-workgroup kernel (csrc/lstm_coop.hip, RW resident in LDS); False if it does not apply."""
-    native.register_sig("dl4j_lstm_fwd_coop", _SIG_COOP)
-    native.register_sig("dl4j_lstm_coop_exch_bytes", [c_int, c_int])
-    lib.dl4j_lstm_coop_exch_bytes.restype = ctypes.c_longlong
     nbytes = lib.dl4j_lstm_coop_exch_bytes(mb, H)
     b, base, reset = _coop_buf("fwd", nbytes, zx.device, T)
     _launch_mode(lib)
     rc = lib.dl4j_lstm_fwd_coop(_ptr(zx), _ptr(rwt), _ptr(peep), _ptr(h0c), _ptr(c0c), _ptr(m), _ptr(out),
                                 _ptr(out16), _ptr(gates), _ptr(call), _ptr(hT), _ptr(cT), _ptr(b.exch), _ptr(b.err), T, mb, H, base, reset,
-                                c_void_p(_stream()))
+                                _stream())
     if rc != 0:
         b.next_tag = None
         return False
@@ -274,20 +258,15 @@ def _fwd_coop(lib, zx, rwt, peep, h0c, c0c, m, out, out16, gates, call, hT, cT, 
 
 last_coop_err = None
 
-_SIG_BWD_COOP = [c_void_p, c_int] + [c_void_p] * 13 + [c_int, c_int, c_int, c_int, ctypes.c_uint, c_int, c_void_p]
-
 
 def _bwd_coop(lib, e, edt, gates, call, c0c, rw, peep, m, dhl, dcl, dz, dh0, dc0, T, mb, H, t_end):
     """Cooperative backward (csrc/lstm_coop.hip: K-split partial dh exchange, RW slice resident in LDS)."""
-    native.register_sig("dl4j_lstm_bwd_coop", _SIG_BWD_COOP)
-    native.register_sig("dl4j_lstm_coop_bwd_exch_bytes", [c_int, c_int])
-    lib.dl4j_lstm_coop_bwd_exch_bytes.restype = ctypes.c_longlong
     nbytes = lib.dl4j_lstm_coop_bwd_exch_bytes(mb, H)
     b, base, reset = _coop_buf("bwd", nbytes, e.device, T)
     _launch_mode(lib)
     rc = lib.dl4j_lstm_bwd_coop(_ptr(e), edt, _ptr(gates), _ptr(call), _ptr(c0c), _ptr(rw), _ptr(peep), _ptr(m), _ptr(dhl),
                                 _ptr(dcl), _ptr(dz), _ptr(dh0), _ptr(dc0), _ptr(b.exch), _ptr(b.err), T, mb, H,
-                                int(t_end), base, reset, c_void_p(_stream()))
+                                int(t_end), base, reset, _stream())
     if rc != 0:
         b.next_tag = None
         return False
@@ -309,7 +288,6 @@ def lstm_seq_fwd(zx, RW, H, peephole, h0=None, c0=None, mask=None, need_cache=Tr
     if H4 != 4 * H or not supported(H, dt) or T < 1 or mb < 1:
         return None
     lib = native.load()
-    native.register_sig("dl4j_lstm_fwd", _SIG_FWD)
     dev = zx.device
     zx = zx.contiguous()
     if packs is not None and packs.dtype == dt and packs.H == H:
@@ -334,7 +312,7 @@ def lstm_seq_fwd(zx, RW, H, peephole, h0=None, c0=None, mask=None, need_cache=Tr
         return out, hT, cT, gates, call, o16
     rc = lib.dl4j_lstm_fwd(_DTC.get(dt, 0), _ptr(zx), _ptr(rwt), _ptr(peep), _ptr(h0c), _ptr(c0c),
                            _ptr(m), _ptr(out), _ptr(o16), _ptr(gates), _ptr(call), _ptr(hT), _ptr(cT), T, mb, H,
-                           c_void_p(_stream()))
+                           _stream())
     if rc == -1:
         return None
     _check(rc, "lstm_fwd")
@@ -349,7 +327,6 @@ def lstm_seq_bwd(eps_tmh, gates, call, c0, RW, H, peephole, mask=None, dh_last=N
     if not supported(H, dt) or t_end >= T:
         return None
     lib = native.load()
-    native.register_sig("dl4j_lstm_bwd", _SIG_BWD)
     dev = eps_tmh.device
     e, edt = _eps_arg(eps_tmh)
     if packs is not None and packs.bwd is not None and packs.dtype == dt and packs.H == H:
@@ -369,7 +346,7 @@ def lstm_seq_bwd(eps_tmh, gates, call, c0, RW, H, peephole, mask=None, dh_last=N
         return dz, dh0, dc0
     rc = lib.dl4j_lstm_bwd(_DTC.get(dt, 0), _ptr(e), edt, _ptr(gates), _ptr(call), _ptr(_f32c(c0)),
                            _ptr(rw), _ptr(peep), _ptr(m), _ptr(_f32c(dh_last)), _ptr(_f32c(dc_last)), _ptr(dz),
-                           _ptr(dh0), _ptr(dc0), T, mb, H, int(t_end), c_void_p(_stream()))
+                           _ptr(dh0), _ptr(dc0), T, mb, H, int(t_end), _stream())
     if rc == -1:
         return None
     _check(rc, "lstm_bwd")
@@ -389,7 +366,6 @@ def lstm_bwd_prep(dz, out, h0, call, c0, peephole, dtype):
     H = G // 4
     R = T * mb
     lib = native.load()
-    native.register_sig("dl4j_lstm_bwd_prep", [c_int] + [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p])
     dzb = torch.empty(R, G, dtype=dtype, device=dz.device)
     hpb = torch.empty(R, H, dtype=dtype, device=dz.device)
     acc = nd4j_kernels.zero_(torch.empty(G + 3 * H, dtype=torch.float32, device=dz.device))   # both accumulators
@@ -433,7 +409,6 @@ def stack2_supported(H, dtype, T):
     if not _stack_enabled() or dtype != torch.bfloat16 or H != 256:
         return False
     lib = native.load()
-    native.register_sig("dl4j_lstm_stack2_max_t", [])
     return 1 <= T <= lib.dl4j_lstm_stack2_max_t()
 
 
@@ -449,10 +424,6 @@ def lstm2_seq_fwd(zx1, packs1, packs2, w2pack, b2, H, h0s, c0s, mask, need_cache
     if not stack2_supported(H, zx1.dtype, T) or H4 != 4 * H:
         return None
     lib = native.load()
-    native.register_sig("dl4j_lstm_fwd_stack2", [c_void_p, c_int, c_int, c_void_p])
-    native.register_sig("dl4j_lstm_stack2_exch_bytes", [c_int, c_int, c_int, c_int])
-    native.register_sig("dl4j_lstm_stack2_struct_bytes", [c_int])
-    lib.dl4j_lstm_stack2_exch_bytes.restype = ctypes.c_longlong
     assert lib.dl4j_lstm_stack2_struct_bytes(0) == ctypes.sizeof(_Stack2Fwd)
     dev = zx1.device
     m = _f32c(mask.reshape(mb, -1)) if mask is not None else None
@@ -479,7 +450,7 @@ def lstm2_seq_fwd(zx1, packs1, packs2, w2pack, b2, H, h0s, c0s, mask, need_cache
                    o16_2=_p(outs[1][5]), gates2=_p(outs[1][3]), call2=_p(outs[1][4]), hT2=_p(outs[1][1]),
                    cT2=_p(outs[1][2]), exch=_p(b.exch), err=_p(b.err), Tn=T, mb=mb, timeout=0, tag_arg=base,
                    exch_words=0)
-    rc = lib.dl4j_lstm_fwd_stack2(ctypes.byref(a), H, reset, c_void_p(_stream()))
+    rc = lib.dl4j_lstm_fwd_stack2(ctypes.byref(a), H, reset, _stream())
     if rc != 0:
         b.next_tag = None
         return None
@@ -497,10 +468,6 @@ def lstm2_seq_bwd(eps2_tmh, cache1, cache2, packs1, packs2, w2pack, H, mask=None
     if not stack2_supported(H, packs1.dtype, T) or t_end >= T:
         return None
     lib = native.load()
-    native.register_sig("dl4j_lstm_bwd_stack2", [c_void_p, c_int, c_int, c_void_p])
-    native.register_sig("dl4j_lstm_stack2_exch_bytes", [c_int, c_int, c_int, c_int])
-    native.register_sig("dl4j_lstm_stack2_struct_bytes", [c_int])
-    lib.dl4j_lstm_stack2_exch_bytes.restype = ctypes.c_longlong
     assert lib.dl4j_lstm_stack2_struct_bytes(1) == ctypes.sizeof(_Stack2Bwd)
     dev = eps2_tmh.device
     e, edt = _eps_arg(eps2_tmh)
@@ -523,7 +490,7 @@ def lstm2_seq_bwd(eps2_tmh, cache1, cache2, packs1, packs2, w2pack, H, mask=None
                    dhl1=_p(dl[0]), dcl1=_p(cl[0]), dhl2=_p(dl[1]), dcl2=_p(cl[1]), dz1=_p(dz[0]), dz2=_p(dz[1]),
                    dh0_1=_p(st[0][0]), dc0_1=_p(st[0][1]), dh0_2=_p(st[1][0]), dc0_2=_p(st[1][1]), exch=_p(b.exch),
                    err=_p(b.err), Tn=T, mb=mb, t_end=int(t_end), timeout=0, tag_arg=base, exch_words=0)
-    rc = lib.dl4j_lstm_bwd_stack2(ctypes.byref(a), H, reset, c_void_p(_stream()))
+    rc = lib.dl4j_lstm_bwd_stack2(ctypes.byref(a), H, reset, _stream())
     if rc != 0:
         b.next_tag = None
         return None

@@ -19,9 +19,6 @@ from ..clustering.vptree import VPTree
 from ..ops import runtime as RT
 import ctypes
 
-RT.register("rt_tsne_row_probs", [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                  ctypes.c_void_p, ctypes.c_int], None)
-
 
 def _prep(x, normalize, usePca, pcaDims=50):
     X = torch.as_tensor(x).double()

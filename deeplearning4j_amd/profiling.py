@@ -111,8 +111,6 @@ def nonfinite_counts(tensors):
     if gpu:
         from .ops import native
         lib = native.load()
-        native.register_sig("dl4j_nonfinite_count", [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_longlong, ctypes.c_void_p])
         arr = (_CheckSeg * len(gpu))()
         maxn = 0
         for j, i in enumerate(gpu):
@@ -124,7 +122,7 @@ def nonfinite_counts(tensors):
         counts = torch.empty(2 * len(gpu), dtype=torch.int64, device=dev)
         rc = lib.dl4j_nonfinite_count(ctypes.cast(arr, ctypes.c_void_p), len(gpu), ctypes.c_void_p(seg_dev.data_ptr()),
                                       ctypes.c_void_p(counts.data_ptr()), maxn,
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                      torch.cuda.current_stream(dev).cuda_stream)
         if rc != 0:
             raise RuntimeError(f"dl4j_nonfinite_count failed ({rc})")
         c = counts.cpu().tolist()                                    # synchronises: panic mode only

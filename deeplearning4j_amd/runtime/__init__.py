@@ -7,7 +7,6 @@ with a ctypes C ABI; framework tensors can live in its memory through DLPack (``
 workspace arenas (memory/workspace.py) get their device buffers.
 """
 import ctypes
-import threading
 
 import torch
 
@@ -29,58 +28,7 @@ class DeviceProps(ctypes.Structure):
         return d
 
 
-_SIGS = {
-    "dl4j_rt_device_count": ([], c_int),
-    "dl4j_rt_device_props": ([c_int, ctypes.POINTER(DeviceProps)], c_int),
-    "dl4j_rt_set_device": ([c_int], c_int),
-    "dl4j_rt_get_device": ([], c_int),
-    "dl4j_rt_device_sync": ([c_int], c_int),
-    "dl4j_rt_mem_info": ([c_int, ctypes.POINTER(c_ll), ctypes.POINTER(c_ll)], c_int),
-    "dl4j_rt_stream_create": ([c_int, c_int, ctypes.POINTER(c_void_p)], c_int),
-    "dl4j_rt_stream_destroy": ([c_void_p], c_int),
-    "dl4j_rt_stream_sync": ([c_void_p], c_int),
-    "dl4j_rt_stream_query": ([c_void_p], c_int),
-    "dl4j_rt_stream_wait_event": ([c_void_p, c_void_p], c_int),
-    "dl4j_rt_event_create": ([c_int, ctypes.POINTER(c_void_p)], c_int),
-    "dl4j_rt_event_destroy": ([c_void_p], c_int),
-    "dl4j_rt_event_record": ([c_void_p, c_void_p], c_int),
-    "dl4j_rt_event_sync": ([c_void_p], c_int),
-    "dl4j_rt_event_query": ([c_void_p], c_int),
-    "dl4j_rt_event_elapsed": ([c_void_p, c_void_p, ctypes.POINTER(c_float)], c_int),
-    "dl4j_rt_capture_begin": ([c_void_p, c_int, c_int], c_int),
-    "dl4j_rt_capture_end": ([c_void_p, c_int, ctypes.POINTER(c_void_p)], c_int),
-    "dl4j_rt_graph_launch": ([c_void_p, c_void_p], c_int),
-    "dl4j_rt_graph_node_count": ([c_void_p], c_ll),
-    "dl4j_rt_graph_destroy": ([c_void_p], c_int),
-    "dl4j_rt_malloc": ([c_int, c_ll, c_void_p, ctypes.POINTER(c_void_p)], c_int),
-    "dl4j_rt_free": ([c_int, c_void_p], c_int),
-    "dl4j_rt_record_stream": ([c_int, c_void_p, c_void_p], c_int),
-    "dl4j_rt_free_pool": ([c_int, c_int], c_int),
-    "dl4j_rt_empty_cache": ([c_int], c_ll),
-    "dl4j_rt_alloc_stats": ([c_int, ctypes.POINTER(c_ll)], c_int),
-    "dl4j_rt_reset_peak": ([c_int], c_int),
-    "dl4j_rt_dlpack_empty": ([c_int, c_int, ctypes.POINTER(c_ll), c_int, c_int, c_void_p, ctypes.POINTER(c_int)],
-                             c_void_p),
-    "dl4j_rt_op_count": ([], c_int),
-    "dl4j_rt_op_info": ([c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p),
-                         ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_void_p)], c_int),
-}
-_lib = None
-_lock = threading.Lock()
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                L = _native.load()
-                for name, (args, res) in _SIGS.items():
-                    f = getattr(L, name)
-                    f.argtypes = args
-                    f.restype = res
-                _lib = L
-    return _lib
+lib = _native.load
 
 
 class EngineError(RuntimeError):

@@ -151,6 +151,45 @@ def test_v3_weight_gradient_every_variant(cuda, case):
     assert torch.equal(again, outs[0])                               # slab reduce: bitwise reproducible
 
 
+def test_wrw_det_r2_path(cuda, monkeypatch):
+    """Deterministic round-2 weight gradient (dl4j_conv_wrw_det: per-split slabs + fixed-order reduce) at the smallest
+    shape with C % 8 == K % 8 == 0 that still has halo rows, against an fp64 CPU weight gradient of the same
+    bf16-rounded operands; two runs into fresh buffers are bitwise equal."""
+    monkeypatch.setenv("DL4J_AMD_DETERMINISTIC", "1")
+    case = (2, 8, 8, 8, 8, 3, 3, (1, 1), (1, 1, 1, 1), (1, 1))
+    N, C, H, W, K, R, S, stride, pad4, dil = case
+    x, w, _ = _data(case)
+    wr = w.cpu().double().requires_grad_(True)
+    yr = F.conv2d(F.pad(x.cpu().double(), (pad4[2], pad4[3], pad4[0], pad4[1])), wr, None, stride, dilation=dil)
+    g = torch.Generator().manual_seed(8)
+    dy = torch.randn(yr.shape, generator=g).cuda().bfloat16().contiguous(memory_format=torch.channels_last)
+    yr.backward(dy.cpu().double())
+    db_ref = dy.cpu().double().sum(dim=(0, 2, 3))
+    geom = (N, H, W, C, K, R, S, stride[0], stride[1], pad4[0], pad4[2], dil[0], dil[1], dy.shape[2], dy.shape[3])
+    outs = []
+    for _ in range(2):
+        dW = torch.zeros(K, C, R, S, device=cuda)
+        db = torch.zeros(K, device=cuda)
+        conv_native._conv2d_wrw_r2(x, dy, geom, dW, db, True, True)
+        torch.cuda.synchronize()
+        outs.append((dW, db))
+    _close(outs[0][0], wr.grad.to(cuda), 1e-2)
+    _close(outs[0][1], db_ref.to(cuda), 1e-3)
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+def test_every_kernel_symbol_bound():
+    """After load, every dl4j_* function of the C ABI header exists on the kernel library with the derived types."""
+    from deeplearning4j_amd.ops import abi
+    lib = native.load()
+    names = [n for n in abi.signatures() if n.startswith("dl4j_")]
+    assert len(names) > 150
+    for name in names:
+        args, res = abi.signatures()[name]
+        f = getattr(lib, name)
+        assert list(f.argtypes) == args and f.restype is res, name
+
+
 HALO_CASES = [
     # the zoo ResNet-50 weight-gradient geometries at a small batch (3x3 halo chunks of 4 / 7 rows, 2 / 4 images)
     (2, 64, 28, 28, 64, 3, 3, (1, 1), (1, 1, 1, 1), (1, 1)),
@@ -204,9 +243,7 @@ def test_halo_in_kernel_tree_reduce(cuda, case, splits):
     node (fan-in 8 default, 2 = deepest tree, 64 = one level) against the separate wrw_halo_reduce launch (fan 0) and
     the fp32 torch weight gradient; weight and bias gradients bitwise reproducible for every fan-in, including single
     split, partial last groups and partial k / c tiles."""
-    import ctypes
     lib = native.load()
-    lib.dl4j_conv_wrw_set_tree.argtypes = [ctypes.c_int]
     N, C, H, W, K, R, S, stride, pad4, dil = case
     x, w, _ = _data(case)
     wr = w.float().requires_grad_(True)

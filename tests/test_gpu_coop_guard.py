@@ -15,8 +15,6 @@ pytestmark = pytest.mark.gpu
 def _set_guard(v):
     from deeplearning4j_amd.ops import native
     lib = native.load()
-    native.register_sig("dl4j_lstm_step_guard", [])
-    lib.dl4j_lstm_step_guard.restype = ctypes.c_void_p
     ptr = lib.dl4j_lstm_step_guard()
     assert ptr
     hip = ctypes.CDLL("libamdhip64.so")

@@ -133,10 +133,8 @@ def test_split_k_deterministic():
 def test_split_k_in_kernel_fixup_matches_reduce(case, monkeypatch):
     """Split-K on the gemm_glds tiles: the tile's last-arriving block sums the slabs in split order inside the kernel
     (dl4j_gemm_set_splitk_fixup(1), opt-in) — bitwise equal to the separate reduce launch, and to the reference."""
-    import ctypes
     from deeplearning4j_amd.ops import native
     lib = native.load()
-    lib.dl4j_gemm_set_splitk_fixup.argtypes = [ctypes.c_int]
     torch.manual_seed(11)
     kw, z = {}, None
     if case == "fp32_dw":

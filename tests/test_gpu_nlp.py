@@ -80,7 +80,6 @@ def test_glove_kernel_matches_cpu(cuda):
     from deeplearning4j_amd.nlp.glove import cooccurrences
     from deeplearning4j_amd.ops import native, runtime as RT
     import ctypes
-    from deeplearning4j_amd.nlp import glove as G  # noqa: F401  (registers signatures)
     rng = np.random.RandomState(0)
     seqs = [rng.randint(0, 30, 20).astype(np.int32) for _ in range(20)]
     ei, ej, ex = cooccurrences(seqs, 3)
@@ -89,9 +88,6 @@ def test_glove_kernel_matches_cpu(cuda):
     b, hW, hb = torch.zeros(V), torch.zeros(V, D), torch.zeros(V)
     Wg, bg, hWg, hbg = (t.clone().to(cuda) for t in (W, b, hW, hb))
     lib = native.load()
-    native.register_sig("dl4j_glove", [ctypes.c_void_p] * 3 + [ctypes.c_longlong] + [ctypes.c_void_p] * 4 +
-                        [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
-                         ctypes.c_int, ctypes.c_void_p])
     rt = RT.load()
     dev_e = [torch.from_numpy(a).to(cuda) for a in (ei, ej, ex)]
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

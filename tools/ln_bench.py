@@ -21,7 +21,6 @@ def main():
     y, mean, rstd = TN.ln_fwd(x, g, b, 1e-12, r)
     ds = torch.empty(N, device=dev)
     L = native.load()
-    L.dl4j_ln_set_config.argtypes = [native.c_int, native.c_int]
     ref = None
     for cap in (512, 256, 128, 64):
         for fold in (1, 0):
