@@ -1,0 +1,291 @@
+// Cached incremental decoding for the causal transformer layers (rnnTimeStep): a key/value cache per layer and an
+// attention kernel from a few new queries to the stored history, for gfx950, bf16 or fp16 in / fp32 accumulate,
+// head dim D in {64, 128}.
+//
+// Cache layout: kv[B, Tcap, 2*E] (E = H*D) in the compute dtype; K of head h at column h*D, V at E + h*D — the fused
+// projection layout of csrc/attention.hip minus the Q block. Tcap is a multiple of 64; rows at or beyond the valid
+// length hold whatever was left there and are never used.
+//
+//  * attn_kv_append_kernel copies the K and V column blocks of qkv[B, Tn, 3E] to rows [pos, pos + Tn) of the cache
+//    (16-byte vectors).
+//  * attn_decode_kernel: queries are the Q columns of qkv[B, Tn, 3E], keys / values rows [0, pos + Tn) of the cache
+//    (the new rows already appended); query i sees keys <= pos + i. Same wave mapping as attn_fwd_kernel: a wave owns
+//    16 queries with transposed scores Sᵀ = K·Qᵀ (v_mfma_f32_16x16x32), exp2-domain online softmax with one (m, l)
+//    per lane, Pᵀ fed from registers into Oᵀ += Vᵀ·Pᵀ. The block stages each 64-key block cooperatively (K row-major,
+//    V transposed), with the next block's global loads in flight during the current block's MFMAs. Waves whose 16
+//    queries all lie beyond Tn only stage (at Tn <= 16 that is three of four; the kernel is bound by the cache read).
+//  * The keys are split: grid (splits, B*H, ceil(Tn/64)); split s covers the contiguous 64-key blocks
+//    [s*nkb/S, (s+1)*nkb/S). One split normalises and writes out directly; several write fp32 partials (running max
+//    m in the exp2 domain, sum l, unnormalised accumulator) to a workspace and attn_decode_combine_kernel merges
+//    them in the fixed order s = 0 .. S-1 — no atomics, bitwise reproducible for a given split count. A split that
+//    is causally empty for a query leaves (-inf, 0, 0) and is skipped by the merge.
+#include "attention_mma.h"
+
+// partial workspace for S splits: acc[((bh*Tn + q)*S + s)*D + d] (16-byte aligned rows), then ml[(bh*Tn + q)*S + s][2]
+// holding (m, l)
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_decode_kernel(const hb* __restrict__ qkv, const hb* __restrict__ kv,
+                                                          hb* __restrict__ out, float* __restrict__ ws, int Tn, int H,
+                                                          int pos, int Tcap, int S, float scale2) {
+  constexpr int KS = D / 32, DT = D / 16;
+  constexpr int LDK = D + 8, LDV = BLK + 8;
+  constexpr int CPR = D / 8, PER = BLK * CPR / 256;              // 16-byte chunks per row / per thread per block
+  __shared__ __attribute__((aligned(16))) hb Ks[BLK * LDK];
+  __shared__ __attribute__((aligned(16))) hb Vt[D * LDV];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, hgrp = lane >> 4;
+  const int split = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh - b * H;
+  const int E = H * D, L = pos + Tn;
+  const long long ld3 = 3LL * E, ld2 = 2LL * E;
+  const hb* qbase = qkv + (long long)b * Tn * ld3 + h * D;
+  const hb* kbase = kv + (long long)b * Tcap * ld2 + h * D;
+  const int q0 = blockIdx.z * BLK;
+  const int qi = q0 + wave * 16 + col;                           // index in the chunk; its position is pos + qi
+  const bool active = q0 + wave * 16 < Tn;                       // wave-uniform: any query of this wave's 16 exists
+  const int qc = min(qi, Tn - 1);
+  V8<hb> qf[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) qf[ks] = ld8(qbase + (long long)qc * ld3 + ks * 32 + 8 * hgrp);
+  f4_t acc[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) acc[dt] = f4_t{0.f, 0.f, 0.f, 0.f};
+  float m = kNegInf, l = 0.f;
+  // this split's key blocks, cut at the last block any query of the tile can see
+  const int nkb = (L + BLK - 1) / BLK;
+  const int kb_lo = (int)((long long)split * nkb / S);
+  const int kb_hi = min((int)((long long)(split + 1) * nkb / S), (pos + min(q0 + BLK, Tn) - 1) / BLK + 1);
+  V8<hb> kr[PER], vr[PER];
+  auto fetch = [&](int kb) {
+#pragma unroll
+    for (int it = 0; it < PER; ++it) {
+      const int i = threadIdx.x + it * 256, r = i / CPR, c = i - r * CPR;
+      const int row = kb * BLK + r;
+      const bool ok = row < L;                                   // rows past the valid length are staged as zeros
+      const hb* src = kbase + (long long)(ok ? row : 0) * ld2 + c * 8;
+      kr[it] = ok ? ld8(src) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+      vr[it] = ok ? ld8(src + E) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+  };
+  if (kb_lo < kb_hi) fetch(kb_lo);
+  for (int kb = kb_lo; kb < kb_hi; ++kb) {
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < PER; ++it) {
+      const int i = threadIdx.x + it * 256, r = i / CPR, c = i - r * CPR;
+      *reinterpret_cast<V8<hb>*>(Ks + r * LDK + c * 8) = kr[it];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) Vt[(c * 8 + k) * LDV + r] = vr[it][k];
+    }
+    __syncthreads();
+    if (kb + 1 < kb_hi) fetch(kb + 1);
+    if (!active) continue;
+    f4_t s[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      s[mt] = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) s[mt] = mma(ld8(Ks + (mt * 16 + col) * LDK + ks * 32 + 8 * hgrp), qf[ks], s[mt]);
+    }
+    float bm = kNegInf;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = kb * BLK + mt * 16 + hgrp * 4 + r;
+        const float v = (key < L && key <= pos + qi) ? s[mt][r] * scale2 : kNegInf;
+        s[mt][r] = v;
+        bm = fmaxf(bm, v);
+      }
+    bm = wmax16(bm);
+    const float mn = fmaxf(m, bm);
+    const float alpha = (mn == kNegInf) ? 1.f : exp2f(m - mn);
+    float ps = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = (mn == kNegInf) ? 0.f : exp2f(s[mt][r] - mn);
+        s[mt][r] = p;
+        ps += p;
+      }
+    l = l * alpha + wsum16(ps);
+    m = mn;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) acc[dt] *= alpha;
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+      const V8<hb> pb = pack2<hb>(s[2 * k2], s[2 * k2 + 1]);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) acc[dt] = mma(ld4x2(Vt + (dt * 16 + col) * LDV + 32 * k2, hgrp), pb, acc[dt]);
+    }
+  }
+  if (qi >= Tn) return;
+  if (S == 1) {
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    hb* orow = out + ((long long)b * Tn + qi) * E + h * D;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      const V4<hb> v{tobf<hb>(acc[dt][0] * inv), tobf<hb>(acc[dt][1] * inv), tobf<hb>(acc[dt][2] * inv), tobf<hb>(acc[dt][3] * inv)};
+      *reinterpret_cast<V4<hb>*>(orow + dt * 16 + hgrp * 4) = v;
+    }
+    return;
+  }
+  const long long slot = ((long long)bh * Tn + qi) * S + split;
+  const long long nslot = (long long)gridDim.y * Tn * S;
+  if (hgrp == 0) {
+    ws[nslot * D + slot * 2] = m;
+    ws[nslot * D + slot * 2 + 1] = l;
+  }
+  float* arow = ws + slot * D;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f4_t*>(arow + dt * 16 + hgrp * 4) = acc[dt];
+}
+
+// out[b, q, h*D + d] = sum_s acc_s[d] 2^(m_s - M) / sum_s l_s 2^(m_s - M), M = max_s m_s, in the order s = 0 .. S-1;
+// one thread per (bh, q, 4 consecutive d)
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_decode_combine_kernel(const float* __restrict__ ws, hb* __restrict__ out,
+                                                                  long long BH, int Tn, int H, int S) {
+  constexpr int DQ = D / 4;
+  const long long nrow = BH * Tn;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nrow * DQ) return;
+  const long long row = i / DQ;                                  // bh*Tn + q
+  const int d4 = (int)(i - row * DQ);
+  const long long bh = row / Tn;
+  const int q = (int)(row - bh * Tn);
+  const int h = (int)(bh % H);
+  const long long b = bh / H;
+  const float* ac = ws + row * S * D + d4 * 4;
+  const float* ml = ws + nrow * S * D + row * S * 2;
+  // the partials are read CH splits at a time, all loads of a chunk issued before their first use: a thread's merge
+  // costs ceil(S / CH) memory round trips, not S. The sums still run in the order s = 0 .. S-1.
+  constexpr int CH = 8;
+  float M = kNegInf;
+  for (int s0 = 0; s0 < S; s0 += CH) {
+    float mv[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) mv[j] = ml[2 * min(s0 + j, S - 1)];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) M = fmaxf(M, mv[j]);
+  }
+  float l = 0.f;
+  f4_t o{0.f, 0.f, 0.f, 0.f};
+  for (int s0 = 0; s0 < S; s0 += CH) {
+    float mv[CH], lv[CH];
+    f4_t av[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      const int s = min(s0 + j, S - 1);
+      mv[j] = ml[2 * s];
+      lv[j] = ml[2 * s + 1];
+      av[j] = *reinterpret_cast<const f4_t*>(ac + (long long)s * D);
+    }
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      if (s0 + j >= S || mv[j] == kNegInf) continue;             // past the end, or a causally empty split
+      const float w = exp2f(mv[j] - M);
+      l += lv[j] * w;
+      o += av[j] * w;
+    }
+  }
+  const float inv = l > 0.f ? 1.f / l : 0.f;
+  const V4<hb> v{tobf<hb>(o[0] * inv), tobf<hb>(o[1] * inv), tobf<hb>(o[2] * inv), tobf<hb>(o[3] * inv)};
+  *reinterpret_cast<V4<hb>*>(out + ((b * Tn + q) * H + h) * D + d4 * 4) = v;
+}
+
+// In 16-byte chunks (EC per E columns): chunk c of the 2E K|V columns of qkv row (b, t) -> kv row (b, pos + t)
+__global__ void __launch_bounds__(256) attn_kv_append_kernel(const uint4* __restrict__ qkv, uint4* __restrict__ kv,
+                                                             long long total, int Tn, int EC, int pos, int Tcap) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % (2 * EC));
+  const long long bt = i / (2 * EC);                             // b*Tn + t
+  const int t = (int)(bt % Tn);
+  const long long b = bt / Tn;
+  kv[(b * Tcap + pos + t) * (2LL * EC) + c] = qkv[bt * (3LL * EC) + EC + c];
+}
+
+// ------------------------------------------------------------------------------------------------ launch
+// Default split count, from the measurements of tools/bench_decode.py --kernel --sweep (profiles/decode_attention.txt):
+// a block's pass over its key blocks is a chain of dependent memory round trips, so short chains on many blocks win
+// until a split is down to one key block (then the merge launch costs more than it saves) or the merge itself, whose
+// cost grows with the split count, shows: two key blocks per split, at most 16 splits. That held from 12 to 384
+// (batch x head) blocks; splitting stops where the unsplit grid alone exceeds the blocks resident at once (4 per
+// compute unit at this kernel's registers for D = 64) — a bound by residency, not measured.
+static constexpr int kDecodeCUs = 256;            // MI355X compute units
+static constexpr int kDecodeResidentPerCU = 4;
+static constexpr int kDecodeMinBlocksPerSplit = 2;
+static constexpr int kDecodeMaxSplits = 16;
+
+static int decode_nkb(int L) { return (L + BLK - 1) / BLK; }
+static int decode_clamp_splits(int splits, int L) { return splits < decode_nkb(L) ? splits : decode_nkb(L); }
+
+template <int D, typename hb>
+static int decode_l(const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H, int pos, int Tcap,
+                    int S, float scale, hipStream_t s) {
+  const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
+  hipLaunchKernelGGL((attn_decode_kernel<D, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv, (hb*)out, ws,
+                     Tn, H, pos, Tcap, S, scale * kLog2e);
+  if (S > 1) {
+    const long long n = (long long)B * H * Tn * (D / 4);
+    hipLaunchKernelGGL((attn_decode_combine_kernel<D, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
+                       (hb*)out, (long long)B * H, Tn, H, S);
+  }
+  return (int)hipGetLastError();
+}
+
+static bool decode_shape_ok(int dt, int B, int Tn, int H, int D, int pos, int Tcap) {
+  if (B < 1 || Tn < 1 || H < 1 || pos < 0 || Tcap < 1 || (dt != 1 && dt != 2) || (D != 64 && D != 128)) return false;
+  if (Tcap % BLK || (long long)pos + Tn > Tcap) return false;
+  if ((long long)B * H > 65535 || (Tn + BLK - 1) / BLK > 65535) return false;   // grid.y / grid.z
+  return true;
+}
+
+// Default split count for keys [0, L) (see the constants above): min(16, key blocks / 2), one split when the
+// (batch x head x query tile) grid fills the device by itself. A pure function of its arguments (no timing), so a
+// run is reproducible across processes.
+DL4J_API int dl4j_attn_decode_splits(int B, int Tn, int H, int D, int L) {
+  if (B < 1 || Tn < 1 || H < 1 || L < 1 || (D != 64 && D != 128)) return 1;
+  const long long base = (long long)B * H * ((Tn + BLK - 1) / BLK);
+  if (base >= (long long)kDecodeCUs * kDecodeResidentPerCU) return 1;
+  int s = decode_nkb(L) / kDecodeMinBlocksPerSplit;
+  if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
+  return s < 1 ? 1 : s;
+}
+
+// fp32 workspace of dl4j_attn_decode_dt for a requested split count (enough for any clamped one); 0 for one split
+DL4J_API long long dl4j_attn_decode_ws_bytes(int B, int Tn, int H, int D, int splits) {
+  if (B < 1 || Tn < 1 || H < 1 || D < 1 || splits <= 1) return 0;
+  return (long long)B * H * Tn * splits * (D + 2) * (long long)sizeof(float);
+}
+
+// dt: 1 = bf16, 2 = fp16. qkv [B,Tn,3*H*D]; kv [B,Tcap,2*H*D]; pos = tokens already in the cache (host integer, the
+// same for every batch row). Copies the K and V columns of qkv to cache rows [pos, pos+Tn).
+// -1 = unsupported shape / dtype, pos + Tn > Tcap, or operands not 16-byte aligned.
+DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, int Tn, int H, int D, int pos, int Tcap,
+                                    hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv) return -1;
+  if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(kv)) & 15) return -1;
+  const int EC = H * D / 8;                                      // 16-byte chunks of E columns
+  const long long total = (long long)B * Tn * 2 * EC;
+  hipLaunchKernelGGL(attn_kv_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const uint4*)qkv,
+                     (uint4*)kv, total, Tn, EC, pos, Tcap);
+  return (int)hipGetLastError();
+}
+
+// out [B,Tn,H*D]; rows [0, pos+Tn) of kv are the keys / values (the new rows already appended), query i sees keys
+// <= pos + i. splits >= 1 is clamped to the number of 64-key blocks; ws: fp32 workspace of
+// dl4j_attn_decode_ws_bytes(..., splits) bytes (may be null for one split). -1 = unsupported shape / dtype.
+DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
+                                 int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv || !out || splits < 1) return -1;
+  if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(kv) | reinterpret_cast<uintptr_t>(out) |
+       reinterpret_cast<uintptr_t>(ws)) & 15)
+    return -1;
+  const int S = decode_clamp_splits(splits, pos + Tn);
+  if (S > 1 && !ws) return -1;
+  if (D == 64) return dt == 1 ? decode_l<64, __bf16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s)
+                              : decode_l<64, _Float16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s);
+  return dt == 1 ? decode_l<128, __bf16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s)
+                 : decode_l<128, _Float16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s);
+}

@@ -173,20 +173,21 @@ __global__ __launch_bounds__(256) void emb_scatter_kernel(const T* __restrict__ 
   }
 }
 
-// BERT input embedding: e[r, :] = Wword[idx[r], :] + Wpos[r % T, :] + Wtype[0, :] for r = b*T + t, summed in fp32
-// and rounded once (three gathers and two adds of the imported graph in one pass). Rows are 16-byte vectors.
+// BERT input embedding: e[r, :] = Wword[idx[r], :] + Wpos[pos0 + r % T, :] + Wtype[0, :] for r = b*T + t, summed in
+// fp32 and rounded once (three gathers and two adds of the imported graph in one pass). Rows are 16-byte vectors.
+// pos0: position of the chunk's first token (0 for a whole sequence, the tokens already seen in rnnTimeStep).
 template <typename T>
 __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const T* __restrict__ Ww, const T* __restrict__ Wp,
                                                              const T* __restrict__ Wt,
                                                              const long long* __restrict__ idx, T* __restrict__ out,
                                                              int rows, int Tn, int E, long long sw, long long sp,
-                                                             int V) {
+                                                             int V, int pos0) {
   const int lane = threadIdx.x & 63;
   for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {
     const long long k = idx[r];
     const bool ok = k >= 0 && k < V;
     const T* a = Ww + (ok ? k : 0) * sw;
-    const T* p = Wp + (long long)(r % Tn) * sp;
+    const T* p = Wp + (long long)(pos0 + r % Tn) * sp;
     T* dst = out + (long long)r * E;
     for (int c = lane * 8; c < E; c += 512) {
       float va[8], vp[8], vt[8];
@@ -386,16 +387,23 @@ DL4J_API int dl4j_emb_scatter_add(int dt, const void* g, const long long* idx, f
 }
 
 // Wword / Wpos: row strides sw / sp with unit column stride; Wtype row 0 contiguous; E % 8 == 0, 16-byte aligned.
-DL4J_API int dl4j_bert_embed_fwd(int dt, const void* Ww, const void* Wp, const void* Wt, const long long* idx,
-                                 void* out, int rows, int Tn, int E, long long sw, long long sp, int V,
-                                 hipStream_t s) {
+// Positions pos0 .. pos0 + Tn - 1 (the caller checks them against Wpos' rows).
+DL4J_API int dl4j_bert_embed_fwd_pos(int dt, const void* Ww, const void* Wp, const void* Wt, const long long* idx,
+                                     void* out, int rows, int Tn, int E, long long sw, long long sp, int V, int pos0,
+                                     hipStream_t s) {
   if (rows <= 0) return 0;
-  if (Tn <= 0 || E % 8 || sw % 8 || sp % 8) return -1;
+  if (Tn <= 0 || pos0 < 0 || E % 8 || sw % 8 || sp % 8) return -1;
   for (const void* q : {Ww, Wp, Wt, (const void*)out})
     if (reinterpret_cast<uintptr_t>(q) & 15) return -1;
   DISPATCH_T(dt, hipLaunchKernelGGL(bert_embed_fwd_kernel<T>, dim3(grid_for(rows, 4)), dim3(256), 0, s, (const T*)Ww,
-                                    (const T*)Wp, (const T*)Wt, idx, (T*)out, rows, Tn, E, sw, sp, V));
+                                    (const T*)Wp, (const T*)Wt, idx, (T*)out, rows, Tn, E, sw, sp, V, pos0));
   return (int)HIP_LAUNCH_CHECK();
+}
+
+DL4J_API int dl4j_bert_embed_fwd(int dt, const void* Ww, const void* Wp, const void* Wt, const long long* idx,
+                                 void* out, int rows, int Tn, int E, long long sw, long long sp, int V,
+                                 hipStream_t s) {
+  return dl4j_bert_embed_fwd_pos(dt, Ww, Wp, Wt, idx, out, rows, Tn, E, sw, sp, V, 0, s);
 }
 
 // de [B*T, E] contiguous; gpos [Tmax, E] and gtype [ntype, E] fp32 views with element strides (row, col).

@@ -123,6 +123,38 @@ DL4J_API int dl4j_softmax_xent_masked(int dtype, const void* z, const float* y, 
   return softmax_xent_launch(dtype, z, y, B, V, grad, score, nullptr, clip_eps, rmask, s);
 }
 
+// ------------------------------------------------------------------------------------------------ softmax rows
+// p[row, :] = softmax(z[row, :]) in fp32 from the 16-bit (or fp32) logits, rounded once on the store: the output
+// layer's activation in an inference time step (rnnTimeStep), so a generation step stays on in-tree kernels. Same
+// row reduction as softmax_xent_kernel; logits rows have leading dimension ldz, p is contiguous.
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_rows_kernel(const T* __restrict__ z, int ldz, T* __restrict__ p, int V) {
+  __shared__ float red[16];
+  const long long row = blockIdx.x;
+  const T* zr = z + row * ldz;
+  float m = -INFINITY;
+  for (int j = threadIdx.x; j < V; j += blockDim.x) m = fmaxf(m, ld1<T>(zr + j));
+  m = block_reduce<true>(m, red);
+  float s = 0.f;
+  for (int j = threadIdx.x; j < V; j += blockDim.x) s += __expf(ld1<T>(zr + j) - m);
+  s = block_reduce<false>(s, red);
+  const float inv = 1.f / s;
+  for (int j = threadIdx.x; j < V; j += blockDim.x) st1<T>(p + row * V + j, __expf(ld1<T>(zr + j) - m) * inv);
+}
+
+// z [B, V] rows with leading dimension ldz >= V; p [B, V] contiguous, same dtype. -1 = unsupported dtype / shape.
+DL4J_API int dl4j_softmax_rows(int dtype, const void* z, int ldz, void* p, int B, int V, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (V <= 0 || ldz < V || !z || !p) return -1;
+#define SMR(T) hipLaunchKernelGGL(softmax_rows_kernel<T>, dim3(B), dim3(256), 0, s, (const T*)z, ldz, (T*)p, V)
+  if (dtype == 1) SMR(bf16);
+  else if (dtype == 2) SMR(f16);
+  else if (dtype == 0) SMR(float);
+  else return -1;
+#undef SMR
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ score scalar
 // out[0] = (sum_{i<n} s[i] + add) * scale + (reg ? reg[0] * reg_scale : 0), one 256-thread block, fixed summation
 // order (bitwise reproducible). The training score on the device without library reduce / elementwise kernels:

@@ -936,3 +936,47 @@ class BertBase(ZooModel):
         net = ComputationGraph(self.conf())
         net.init(device=device)
         return net
+
+
+# ------------------------------------------------------------------------------------------------ TextGenerationTransformer
+class TextGenerationTransformer(ZooModel):
+    """Causal transformer language model, the counterpart of ``TextGenerationLSTM`` (new relative to the reference
+    zoo): BertEmbeddingLayer -> N causal TransformerEncoderLayer -> RnnOutputLayer (softmax, MCXENT). Input = token
+    ids [mb, T]; output = next-token distribution [mb, numLabels, T]. ``numLabels`` is the vocabulary size.
+
+    Generation goes through ``rnnTimeStep`` as for the LSTM model: after ``rnnClearPreviousState()`` feed the prompt
+    and then one token at a time; every block keeps a key/value cache, so a step costs one pass over the cache
+    instead of recomputing the prefix."""
+    DEFAULT_SHAPE = [128]
+
+    def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
+                 maxPositions=512, learningRate=1e-3, **kw):
+        super().__init__(numLabels, seed, inputShape, **kw)
+        self.hidden, self.layers, self.heads = hidden, layers, heads
+        self.ffn = int(ffn) if ffn else 4 * hidden
+        self.maxPositions, self.learningRate = maxPositions, learningRate
+
+    def graphBuilder(self):
+        from ..nn.conf import BertEmbeddingLayer, TransformerEncoderLayer
+        g = (self._builder().updater(Adam(self.learningRate)).weightInit(NormalDistribution(0.0, 0.02))
+             .graphBuilder())
+        g.addInputs("tokens")
+        g.addLayer("embeddings", BertEmbeddingLayer.Builder().nIn(self.numLabels).nOut(self.hidden)
+                   .maxPositions(self.maxPositions).inputLength(self.inputShape[0]).build(), "tokens")
+        prev = "embeddings"
+        for i in range(self.layers):
+            g.addLayer(f"decoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
+                       .nHeads(self.heads).ffnSize(self.ffn).causal(True).build(), prev)
+            prev = f"decoder_{i}"
+        g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
+                   .nIn(self.hidden).nOut(self.numLabels).build(), prev)
+        g.setOutputs("output")
+        return g
+
+    def conf(self):
+        return self.graphBuilder().build()
+
+    def init(self, device=None):
+        net = ComputationGraph(self.conf())
+        net.init(device=device)
+        return net

@@ -14,15 +14,17 @@ hand-derived backward (no torch.autograd):
 Feature masks [mb, T] mask padded keys; masked query rows produce zeros.
 ``attentionDropout`` (a DROP probability, training only): the keep mask is generated inside the flash kernels from
 the layer's PhiloxStream and regenerated in the backward; the explicit path takes its mask from ``dropoutKeep``.
+``rnnTimeStep`` on a causal layer appends the chunk's K / V to a per-layer cache and attends over it
+(``KVCacheState`` in transformer.py, csrc/attention_decode.hip).
 """
 import torch
 
 from .base import LayerImpl, bias_grad_, matmul, weight_grad_
-from .transformer import DropoutSites
+from .transformer import DropoutSites, KVCacheState
 from ...ops.gemm import mmul
 
 
-class SelfAttentionLayerImpl(DropoutSites, LayerImpl):
+class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
     def type(self):
         return "RECURRENT"
 
@@ -83,6 +85,29 @@ class SelfAttentionLayerImpl(DropoutSites, LayerImpl):
             self._c = (X, qkv, actx, o2, m, mb, T)
         self._z = z
         return self.conf.activation.getActivation(z, training) if self.conf.activation is not None else z
+
+    def rnnTimeStep(self, x, mask=None):
+        """One chunk [mb, nIn, Tn] (or one step [mb, nIn]) of a causal layer continuing the cached keys / values; a
+        bidirectional layer cannot stream and runs ``activate`` on the chunk."""
+        if not self.conf.causal:
+            return self.activate(x, False)
+        self.training = False
+        one = x.dim() == 2
+        if one:
+            x = x.unsqueeze(2)
+        self._check_state_mb(x)
+        mb, nIn, T = x.shape
+        H, hs, d = self._dims()
+        dt = self.W("Wq").dtype
+        X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
+        qkv = torch.empty(mb * T, 3 * d, dtype=dt, device=x.device)
+        for i, (wk, bk) in enumerate((("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
+            mmul(X, self.W(wk), out=qkv[:, i * d:(i + 1) * d], bias=self.Wbias(bk).reshape(-1))
+        o = self.cachedAttention(qkv.reshape(mb, T, 3 * d), H, "SelfAttentionLayer rnnTimeStep")
+        Y = matmul(o.reshape(mb * T, d), self.W("Wo"), bias=self.Wbias("bo"))
+        z = Y.reshape(mb, T, -1).permute(0, 2, 1)
+        y = self.conf.activation.getActivation(z, False) if self.conf.activation is not None else z
+        return y[:, :, 0] if one else y
 
     def backpropGradient(self, eps, **kw):
         X, qkv, actx, o2, m, mb, T = self._c

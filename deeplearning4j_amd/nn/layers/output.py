@@ -213,6 +213,27 @@ class RnnOutputLayerImpl(BaseOutputLayerImpl):
     def _eps_from2d(self, e):
         return _2d_to_rnn(e, self._mb) if self.input.dim() == 3 else e
 
+    def rnnTimeStep(self, x, mask=None):
+        """``activate(x, False)`` for one chunk of a generation loop. 16-bit softmax outputs on the GPU take the
+        in-tree row-softmax kernel (fp32 arithmetic, one rounding, as the activation's own path), so a cached
+        decoding step launches no library kernel; everything else is ``activate`` itself."""
+        from ... import ops
+        if not (x.is_cuda and self.has_params and isinstance(self.conf.activation, ActivationSoftmax) and
+                self.W("W").dtype in (torch.bfloat16, torch.float16) and ops.use_native(x, "softmax")):
+            return self.activate(x, False)
+        self.training = False
+        x = self.applyDropOutIfNecessary(x, False)
+        self.input = x
+        self.maskArray = None
+        self._x2 = self._in2d(x)
+        self._z = z = self.preOutput2d(self._x2)
+        self._cache = None
+        from ...ops import native
+        p = native.softmax_rows(z)
+        if p is None:
+            p = self.conf.activation.getActivation(z, False)
+        return self._out_from2d(p)
+
     def computeScoreForExamples(self, fullNetworkL1=0.0, fullNetworkL2=0.0):
         s, _ = self._loss_and_grad()
         if self.input.dim() == 3:

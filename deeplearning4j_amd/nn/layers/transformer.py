@@ -22,6 +22,11 @@ launch of the Philox dropout kernel in backward mode (it regenerates the mask), 
 the column sum of ds∘D by the column-sum kernel — the dropout is NOT fused into the LayerNorm backward kernels.
 Each layer owns one PhiloxStream advanced once per training forward; its sites use keys derived from the layer's
 seed. Off the kernels (CPU, fp32 / fp64, other head sizes) the masks come from ``dropoutKeep``.
+
+Generation (``rnnTimeStep``): a causal block keeps a key/value cache (``KVCacheState``): the new chunk is projected,
+its K / V appended, its queries attend over the cache (csrc/attention_decode.hip, or the torch reference off the
+kernels) and the rest of the block runs as in the inference forward; the embedding layer continues its positions.
+A bidirectional block cannot stream and runs ``activate`` on the chunk.
 """
 import math
 
@@ -226,13 +231,91 @@ def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx):
     return TN.attention_bwd_explicit(ctx[1], dctx.reshape(B, T, -1), qkv.dtype).reshape(B * T, -1)
 
 
+# ------------------------------------------------------------------------------------------------ cached decoding
+class KVCacheState:
+    """rnnTimeStep state of a causal attention layer: one key/value cache ``kv [mb, Tcap, 2E]`` in the compute dtype
+    (K of head h at column h*D, V at E + h*D; the layout of csrc/attention_decode.hip) and the number of valid rows.
+    Tcap is a multiple of 64 and grows geometrically, so a steady-state step neither allocates nor copies. The stored
+    state handed out / taken in is ``{"kv": [mb, L, 2E]}`` trimmed to the valid length."""
+    _kv = None
+    _kv_len = 0
+
+    def rnnClearPreviousState(self):
+        self._kv = None
+        self._kv_len = 0
+
+    def rnnGetPreviousState(self):
+        if self._kv is None:
+            return {}
+        return {"kv": self._kv[:, :self._kv_len].clone()}
+
+    def rnnSetPreviousState(self, state):
+        kv = state.get("kv") if state else None
+        self.rnnClearPreviousState()
+        if kv is None:
+            return
+        mb, L, E2 = kv.shape
+        self._kv_reserve(mb, E2, L, kv.dtype, kv.device)
+        self._kv[:, :L] = kv
+        self._kv_len = L
+
+    def _check_state_mb(self, x):
+        """rnnTimeStep continues the stored cache, so the minibatch size cannot change between calls without
+        rnnClearPreviousState() (same rule and wording as BaseRecurrentImpl._check_state_mb)."""
+        if self._kv is not None and self._kv.shape[0] != x.shape[0]:
+            from ...exceptions import DL4JInvalidInputException
+            raise DL4JInvalidInputException(
+                f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): minibatch size {x.shape[0]} differs "
+                f"from the stored state's {self._kv.shape[0]}; call rnnClearPreviousState() before changing it")
+
+    def _kv_reserve(self, mb, E2, need, dtype, device):
+        """Make room for ``need`` rows: capacity is a multiple of 64 and at least doubles when it has to grow."""
+        kv = self._kv
+        if kv is not None and kv.shape[1] >= need and kv.dtype == dtype and kv.device == device:
+            return
+        cap = -(-max(int(need), 1) // 64) * 64
+        if kv is not None:
+            cap = max(cap, 2 * kv.shape[1])
+        new = torch.empty(mb, cap, E2, dtype=dtype, device=device)
+        if kv is not None and self._kv_len:
+            new[:, :self._kv_len] = kv[:, :self._kv_len].to(dtype)
+        self._kv = new
+
+    def cachedAttention(self, qkv, H, what="rnnTimeStep"):
+        """Causal attention of the chunk qkv [mb, Tn, 3E] over everything seen since rnnClearPreviousState(): its K / V
+        are appended to the cache, its queries attend over the cache. -> [mb, Tn, E]. The decode kernels on a GPU in
+        bf16 / fp16 with head size 64 / 128 (the causal flash forward for a prompt of >= 64 tokens into an empty
+        cache), else the torch reference, counted as a fallback on a GPU."""
+        from ...ops import transformer_native as TN
+        mb, Tn, E3 = qkv.shape
+        E = E3 // 3
+        pos = self._kv_len
+        self._kv_reserve(mb, 2 * E, pos + Tn, qkv.dtype, qkv.device)
+        kv = self._kv
+        out = None
+        if _native(qkv, "attention") and qkv.is_contiguous() and TN.attn_decode_supported(qkv, kv, H):
+            if TN.attn_kv_append(qkv, kv, H, pos) is not None:
+                if pos == 0 and Tn >= 64:
+                    out = TN.attn_fwd(qkv, H, None, True)[0]
+                else:
+                    out = TN.attn_decode(qkv, kv, H, pos)
+        if out is None:
+            if qkv.is_cuda:
+                from ...ops import fallback
+                fallback.record("attention", f"{what} head size {E // H} / dtype {qkv.dtype}: torch reference path")
+            kv[:, pos:pos + Tn] = qkv[:, :, E:]
+            out = TN.attention_decode_reference(qkv[:, :, :E], kv[:, :pos + Tn, :E], kv[:, :pos + Tn, E:], H, pos)
+        self._kv_len = pos + Tn
+        return out
+
+
 def _token_major(x):
     """[mb, E, T] (possibly a permuted view of token-major memory) -> contiguous [mb*T, E] (no copy when it is)."""
     mb, E, T = x.shape
     return x.permute(0, 2, 1).reshape(mb * T, E)
 
 
-class TransformerEncoderLayerImpl(DropoutSites, LayerImpl):
+class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
     def type(self):
         return "RECURRENT"
 
@@ -263,6 +346,30 @@ class TransformerEncoderLayerImpl(DropoutSites, LayerImpl):
             self._c = (xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m, d1, d2)
         self.input = x
         return y.reshape(B, T, E).permute(0, 2, 1)
+
+    def rnnTimeStep(self, x, mask=None):
+        """One chunk [mb, E, Tn] (or one step [mb, E]) of a causal block continuing the cached keys / values: the
+        inference forward of ``activate`` with the attention taken over the cache. A bidirectional block cannot
+        stream and runs ``activate`` on the chunk."""
+        c = self.conf
+        if not c.causal:
+            return self.activate(x, False)
+        self.training = False
+        one = x.dim() == 2
+        if one:
+            x = x.unsqueeze(2)
+        self._check_state_mb(x)
+        B, E, T = x.shape
+        xt = _token_major(x).to(self.W("Wqkv").dtype)
+        qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads).reshape(B * T, -1)
+        a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
+        h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
+        f = matmul(h1, self.W("W1"), bias=self.Wbias("b1"), act="gelu")
+        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        y, _ = _ln_fwd(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps)
+        y = y.reshape(B, T, E).permute(0, 2, 1)
+        return y[:, :, 0] if one else y
 
     def backpropGradient(self, eps, **kw):
         c = self.conf
@@ -317,10 +424,7 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         B, T = idx.shape
         dt = self.W("Wword").dtype
         from ...ops import nn_misc
-        e = nn_misc.bert_embed_forward(self.W("Wword"), self.W("Wpos"), self.W("Wtype"), idx) if idx.is_cuda else None
-        if e is None:
-            e = self.W("Wword")[idx.reshape(-1)] + self.W("Wpos")[:T].repeat(B, 1) + self.W("Wtype")[0].reshape(1, -1)
-            e = e.to(dt).contiguous()
+        e = self._embed(idx, 0)
         y, ln = _ln_fwd(e, None, self.params["lng"], self.params["lnb"], c.layerNormEps)
         dctx = None
         if training and float(c.hiddenDropout) > 0.0:           # drop(LN(emb)): after the LayerNorm, its own launch
@@ -365,6 +469,54 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         gt[0] = de.sum(0)
         copy_grad_(g["Wtype"], gt)
         return self.make_gradient(), None
+
+    def _embed(self, idx, pos):
+        """[B*T, E] = Wword[idx] + Wpos[pos .. pos+T-1] + Wtype[0] in the compute dtype (in-tree kernel on a GPU)."""
+        from ...ops import nn_misc
+        B, T = idx.shape
+        e = nn_misc.bert_embed_forward(self.W("Wword"), self.W("Wpos"), self.W("Wtype"), idx, pos) if idx.is_cuda \
+            else None
+        if e is None:
+            e = self.W("Wword")[idx.reshape(-1)] + self.W("Wpos")[pos:pos + T].repeat(B, 1) + \
+                self.W("Wtype")[0].reshape(1, -1)
+            e = e.to(self.W("Wword").dtype).contiguous()
+        return e
+
+    # rnnTimeStep state: the number of tokens seen so far (and the minibatch size they were seen with)
+    _seen = None
+
+    def rnnClearPreviousState(self):
+        self._seen = None
+
+    def rnnGetPreviousState(self):
+        return {} if self._seen is None else {"pos": self._seen[0], "mb": self._seen[1]}
+
+    def rnnSetPreviousState(self, state):
+        self._seen = (int(state["pos"]), int(state["mb"])) if state and "pos" in state else None
+
+    def rnnTimeStep(self, x, mask=None):
+        """Token ids [mb, Tn] (or [mb, 1, Tn]) embedded at positions pos .. pos+Tn-1, pos = the tokens seen since
+        rnnClearPreviousState()."""
+        from ...exceptions import DL4JInvalidInputException
+        if x.dim() == 3:
+            x = x[:, 0, :]
+        idx = x.long()
+        B, T = idx.shape
+        pos, mb = self._seen if self._seen is not None else (0, B)
+        if mb != B:
+            raise DL4JInvalidInputException(
+                f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): minibatch size {B} differs "
+                f"from the stored state's {mb}; call rnnClearPreviousState() before changing it")
+        maxp = self.W("Wpos").shape[0]
+        if pos + T > maxp:
+            raise DL4JInvalidInputException(
+                f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): {pos} tokens seen + {T} new exceed "
+                f"maxPositions {maxp}; call rnnClearPreviousState() to start a new sequence")
+        self.training = False
+        e = self._embed(idx, pos)
+        y, _ = _ln_fwd(e, None, self.params["lng"], self.params["lnb"], self.conf.layerNormEps)
+        self._seen = (pos + T, B)
+        return y.reshape(B, T, -1).permute(0, 2, 1)
 
     def feedForwardMaskArray(self, mask, state, mb):
         self.maskArray = mask

@@ -593,6 +593,21 @@ def softmax_xent(logits, labels, clip_eps, row_mask=None):
     return score, grad, None
 
 
+def softmax_rows(logits):
+    """Row softmax of ``logits`` [B, V] (unit column stride; fp32 arithmetic, one rounding to the logits' dtype) on the
+    in-tree kernel; None when it does not take the operand."""
+    dt = _dt16(logits)
+    if dt is None or logits.dim() != 2 or logits.stride(1) != 1 or not logits.is_cuda:
+        return None
+    B, V = logits.shape
+    out = torch.empty((B, V), dtype=logits.dtype, device=logits.device)
+    rc = load().dl4j_softmax_rows(dt, _ptr(logits), logits.stride(0) if B > 1 else V, _ptr(out), B, V, _stream())
+    if rc == -1:
+        return None
+    _check(rc, "softmax_rows")
+    return out
+
+
 def softmax_xent_strided(logits, y, mb, ys, clip_eps):
     """Fused softmax + MCXENT over the rows of ``logits`` [B, V] (unit column stride) with labels read in place from
     fp32 ``y`` at strides ys = (per-example, per-time-step, per-class) for row r = t*mb + b. Returns (score [B] fp32,

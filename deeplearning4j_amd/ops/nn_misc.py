@@ -175,19 +175,20 @@ def embedding_backward_(dW, idx, g):
     return dW
 
 
-def bert_embed_forward(Ww, Wp, Wt, idx):
-    """[B*T, E] = Wword[idx] + Wpos[t] + Wtype[0] for token ids ``idx`` [B, T] in one HIP pass (fp32 sum, one rounding);
-    None when the kernel does not take these operands (the caller sums with torch)."""
+def bert_embed_forward(Ww, Wp, Wt, idx, pos=0):
+    """[B*T, E] = Wword[idx] + Wpos[pos + t] + Wtype[0] for token ids ``idx`` [B, T] in one HIP pass (fp32 sum, one
+    rounding); ``pos``: position of the first token (rnnTimeStep continues a sequence). None when the kernel does not
+    take these operands (the caller sums with torch)."""
     B, T = idx.shape
     E = Ww.shape[1]
     if not (use_native(Ww, "embedding") and _dt(Ww) is not None and Ww.dtype == Wp.dtype == Wt.dtype and
             Ww.dim() == Wp.dim() == Wt.dim() == 2 and Ww.stride(1) == Wp.stride(1) == Wt.stride(1) == 1 and
-            Wp.shape[0] >= T and Wp.shape[1] == Wt.shape[1] == E):
+            pos >= 0 and Wp.shape[0] >= pos + T and Wp.shape[1] == Wt.shape[1] == E):
         return None
     fi = idx.reshape(-1).to(torch.int64).contiguous()
     out = torch.empty((B * T, E), dtype=Ww.dtype, device=Ww.device)
-    rc = _lib().dl4j_bert_embed_fwd(_dt(Ww), _p(Ww), _p(Wp), _p(Wt), _p(fi), _p(out), B * T, T, E, Ww.stride(0),
-                                    Wp.stride(0), Ww.shape[0], _s())
+    rc = _lib().dl4j_bert_embed_fwd_pos(_dt(Ww), _p(Ww), _p(Wp), _p(Wt), _p(fi), _p(out), B * T, T, E, Ww.stride(0),
+                                        Wp.stride(0), Ww.shape[0], int(pos), _s())
     return out if rc == 0 else None
 
 

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Cached decoding measurements (csrc/attention_decode.hip, rnnTimeStep of the causal transformer layers).
+
+  --kernel  GPU time of ``attn_decode`` for one new token (Tn = 1) over a history of L keys, L in {128, 1024, 4096},
+            (B, H, D) in {(1, 12, 64), (32, 12, 64)}, bf16: once with splits = 1 and once with the default split
+            count, in microseconds and as achieved read bandwidth of the cache (2 * L * E * 2 bytes per batch row).
+            Every configuration is timed ``--passes`` times, alternating, so the log shows its own run-to-run spread.
+            ``--sweep`` adds explicit split counts (for choosing the default).
+  --model   tokens/s of ``TextGenerationTransformer(hidden=768, layers=12, heads=12)`` in bf16 at prefix lengths 128
+            and 1024, for each minibatch size of ``--batch``: cached ``rnnTimeStep`` one token at a time against ``output()`` on the whole prefix per token
+            (the only correct way without the cache). Host clock around work that ends in a device synchronise.
+
+Usage: python tools/bench_decode.py --kernel --model [--out profiles/decode_attention.txt]"""
+import argparse
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+from deeplearning4j_amd.ops import transformer_native as TN  # noqa: E402
+from deeplearning4j_amd.ops.timing import gpu_time  # noqa: E402
+
+_out = None
+
+
+def say(s=""):
+    print(s, flush=True)
+    if _out is not None:
+        _out.write(s + "\n")
+        _out.flush()
+
+
+def kernel_mode(passes, sweep, reps):
+    dev = torch.device("cuda", 0)
+    dt = torch.bfloat16
+    say(f"== attn_decode, Tn = 1, bf16, GPU time per call (mean of {reps} back-to-back launches), {passes} passes")
+    say("   bandwidth = 2*L*E*2 bytes per batch row / time; a cache that fits the last-level caches is re-read from them")
+    for B, H, D in ((1, 12, 64), (32, 12, 64)):
+        E = H * D
+        for L in (128, 1024, 4096):
+            pos = L - 1
+            g = torch.Generator().manual_seed(L + B)
+            qkv = (torch.randn(B, 1, 3 * E, generator=g) * 0.8).to(dt).to(dev)
+            kv = (torch.randn(B, (L + 63) // 64 * 64, 2 * E, generator=g) * 0.8).to(dt).to(dev)
+            assert TN.attn_kv_append(qkv, kv, H, pos) is kv
+            default = TN.attn_decode_splits(B, 1, H, D, L)
+            cands = [("splits=1", 1), (f"default={default}", default)]
+            if sweep:
+                cands += [(f"splits={s}", s) for s in (2, 4, 8, 16, 32, 64) if s <= (L + 63) // 64 and s != default]
+            ref = TN.attn_decode(qkv, kv, H, pos, splits=1).float()
+            times = {name: [] for name, _ in cands}
+            for _ in range(passes):
+                for name, s in cands:
+                    times[name].append(gpu_time(lambda: TN.attn_decode(qkv, kv, H, pos, splits=s), reps=reps,
+                                                warmup=3) * 1e3)
+            nbytes = 2.0 * L * E * 2 * B
+            for name, s in cands:
+                t = sorted(times[name])
+                med = t[len(t) // 2]
+                diff = (TN.attn_decode(qkv, kv, H, pos, splits=s).float() - ref).abs().max().item()
+                say(f"B={B:2d} H={H} D={D} L={L:4d} {name:12s}: " + " ".join(f"{v:7.2f}" for v in times[name]) +
+                    f" us  median {med:7.2f} us  {nbytes / med / 1e3:7.1f} GB/s  (max diff vs splits=1 {diff:.1e})")
+    say()
+
+
+def _sync_time(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def model_mode(batches, n_cached, n_full):
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    dev = torch.device("cuda", 0)
+    V = 77
+    net = TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=768, layers=12, heads=12, maxPositions=2048,
+                                    dataType=DataType.BFLOAT16).init(device=dev)
+    for batch in batches:
+        _model_rows(net, V, dev, batch, n_cached, n_full)
+
+
+def _model_rows(net, V, dev, batch, n_cached, n_full):
+    say(f"== TextGenerationTransformer(hidden=768, layers=12, heads=12) bf16, batch {batch}: generated tokens/s")
+    for P in (128, 1024):
+        x = torch.randint(0, V, (batch, P + max(n_cached, n_full) + 4), generator=torch.Generator().manual_seed(P)).to(dev)
+
+        def cached(n, warm):
+            net.rnnClearPreviousState()
+            net.rnnTimeStep(x[:, :P - warm])                                   # the prompt
+            for t in range(P - warm, P):
+                net.rnnTimeStep(x[:, t:t + 1])                                 # warm the single-token shapes
+            last = [None]
+
+            def run():
+                for t in range(P, P + n):
+                    last[0] = net.rnnTimeStep(x[:, t:t + 1])[0]
+            return _sync_time(run), last[0]
+
+        def full(n):
+            last = [None]
+
+            def run():
+                for t in range(P, P + n):
+                    last[0] = net.output(x[:, :t + 1])[0][:, :, -1:]
+            return _sync_time(run), last[0]
+
+        cached(2, 2)
+        full(n_full)                                                           # warm-up of both paths: every prefix
+                                                                               # length is a GEMM shape of its own
+        tc, yc = cached(n_cached, 2)
+        tf, yf = full(n_full)
+        _, yc_at = cached(n_full, 2)                                           # same last position as the full run
+        agree = (yc_at - yf).abs().max().item()
+        rc, rf = batch * n_cached / tc, batch * n_full / tf
+        say(f"prefix {P:4d}: cached rnnTimeStep {rc:9.1f} tok/s ({tc / n_cached * 1e3:7.2f} ms/step, {n_cached} steps)"
+            f" | output() on the prefix {rf:9.1f} tok/s ({tf / n_full * 1e3:7.2f} ms/step, {n_full} steps)"
+            f" | factor {rc / rf:6.2f}x | max |p_cached - p_full| {agree:.2e}")
+    say()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--model", action="store_true")
+    ap.add_argument("--sweep", action="store_true", help="--kernel: also time explicit split counts")
+    ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--batch", default="1,32", help="--model: minibatch sizes, comma separated")
+    ap.add_argument("--cached-steps", type=int, default=64)
+    ap.add_argument("--full-steps", type=int, default=16)
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    a = ap.parse_args()
+    if not (a.kernel or a.model):
+        ap.error("give --kernel and / or --model")
+    if not torch.cuda.is_available():
+        sys.exit("bench_decode.py measures on the GPU; no device found")
+    global _out
+    if a.out:
+        _out = open(a.out, "w")
+    say(f"# tools/bench_decode.py {' '.join(sys.argv[1:])}   ({torch.cuda.get_device_name(0)})")
+    if a.kernel:
+        kernel_mode(a.passes, a.sweep, a.reps)
+    if a.model:
+        model_mode([int(b) for b in a.batch.split(",")], a.cached_steps, a.full_steps)
+    if _out is not None:
+        _out.close()
+
+
+if __name__ == "__main__":
+    main()
