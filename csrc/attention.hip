@@ -21,31 +21,6 @@
 // Softmax runs in the exp2 domain: s2 = q·k · scale·log2(e); lse2 = m2 + log2(l) is saved for the backward.
 #include "attention_mma.h"
 
-// cooperative block loads: rows [r0, r0+64) of a [T, ld] matrix slice (D columns at col0) into LDS
-template <int D, typename hb>
-__device__ __forceinline__ void stage_rows(hb* dst, int dld, const hb* src, long long src_ld, int r0, int T) {
-  constexpr int CPR = D / 8;                                  // 16-byte chunks per row
-  for (int i = threadIdx.x; i < BLK * CPR; i += blockDim.x) {
-    const int r = i / CPR, c = i - r * CPR;
-    V8<hb> v;
-    if (r0 + r < T) v = *reinterpret_cast<const V8<hb>*>(src + (long long)(r0 + r) * src_ld + c * 8);
-    else v = V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-    *reinterpret_cast<V8<hb>*>(dst + r * dld + c * 8) = v;
-  }
-}
-template <int D, typename hb>
-__device__ __forceinline__ void stage_rows_t(hb* dst, int dld, const hb* src, long long src_ld, int r0, int T) {
-  constexpr int CPR = D / 8;                                  // transposed: dst[d][row]
-  for (int i = threadIdx.x; i < BLK * CPR; i += blockDim.x) {
-    const int r = i % BLK, c = i / BLK;
-    V8<hb> v;
-    if (r0 + r < T) v = *reinterpret_cast<const V8<hb>*>(src + (long long)(r0 + r) * src_ld + c * 8);
-    else v = V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dst[(c * 8 + k) * dld + r] = v[k];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ dropout mask
 // Attention-probability dropout (DROP = true instances of the three kernels below; the DROP = false instances are
 // the kernels without it, no run-time branch). The keep mask is never stored: it is a pure function of

@@ -1,6 +1,7 @@
-// Fragment helpers shared by the attention kernels (csrc/attention.hip, csrc/attention_decode.hip): the
-// v_mfma_f32_16x16x32_{bf16,f16} wrappers, the LDS / register fragment loads that match its operand layout, and
-// the cross-group reductions of the transposed-score online softmax.
+// Fragment helpers shared by the attention kernels (csrc/attention.hip, csrc/attention_cross.hip,
+// csrc/attention_decode.hip): the v_mfma_f32_16x16x32_{bf16,f16} wrappers, the LDS / register fragment loads that
+// match its operand layout, the cross-group reductions of the transposed-score online softmax, and the cooperative
+// 64-row block loads into LDS.
 #pragma once
 #include "common.h"
 
@@ -41,4 +42,29 @@ __device__ __forceinline__ float wmax16(float v) {            // max over the 4 
 __device__ __forceinline__ float wsum16(float v) {
   v += __shfl_xor(v, 16, 64);
   return v + __shfl_xor(v, 32, 64);
+}
+
+// cooperative block loads: rows [r0, r0+64) of a [T, ld] matrix slice (D columns at col0) into LDS
+template <int D, typename hb>
+__device__ __forceinline__ void stage_rows(hb* dst, int dld, const hb* src, long long src_ld, int r0, int T) {
+  constexpr int CPR = D / 8;                                  // 16-byte chunks per row
+  for (int i = threadIdx.x; i < BLK * CPR; i += blockDim.x) {
+    const int r = i / CPR, c = i - r * CPR;
+    V8<hb> v;
+    if (r0 + r < T) v = *reinterpret_cast<const V8<hb>*>(src + (long long)(r0 + r) * src_ld + c * 8);
+    else v = V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+    *reinterpret_cast<V8<hb>*>(dst + r * dld + c * 8) = v;
+  }
+}
+template <int D, typename hb>
+__device__ __forceinline__ void stage_rows_t(hb* dst, int dld, const hb* src, long long src_ld, int r0, int T) {
+  constexpr int CPR = D / 8;                                  // transposed: dst[d][row]
+  for (int i = threadIdx.x; i < BLK * CPR; i += blockDim.x) {
+    const int r = i % BLK, c = i / BLK;
+    V8<hb> v;
+    if (r0 + r < T) v = *reinterpret_cast<const V8<hb>*>(src + (long long)(r0 + r) * src_ld + c * 8);
+    else v = V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dst[(c * 8 + k) * dld + r] = v[k];
+  }
 }

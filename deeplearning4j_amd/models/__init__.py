@@ -3,5 +3,5 @@ from .labels import (BaseLabels, ClassPrediction, COCOLabels, DarknetLabels, Ima
                      adler32_file)
 from .zoo import (ZOO, AlexNet, BertBase, Darknet19, FaceNetNN4Small2, GoogLeNet, InceptionResNetV1, LeNet, ResNet50,  # noqa
                   ModelMetaData, ModelSelector, PretrainedType, SimpleCNN, TextGenerationLSTM, TextGenerationTransformer,
-                  TinyYOLO, VGG16, VGG19,
+                  TinyYOLO, TransformerSeq2Seq, VGG16, VGG19,
                   YOLO2, ZooModel, ZooType)

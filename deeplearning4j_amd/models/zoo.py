@@ -980,3 +980,64 @@ class TextGenerationTransformer(ZooModel):
         net = ComputationGraph(self.conf())
         net.init(device=device)
         return net
+
+
+# ------------------------------------------------------------------------------------------------ TransformerSeq2Seq
+class TransformerSeq2Seq(ZooModel):
+    """Encoder-decoder transformer for sequence-to-sequence tasks (translation, summarisation; new relative to the
+    reference zoo). Inputs ``"source"`` and ``"target"`` token ids [mb, Ts] / [mb, Tt]:
+      source -> BertEmbeddingLayer -> N bidirectional TransformerEncoderLayer                      (the memory)
+      target -> BertEmbeddingLayer -> N TransformerDecoderLayer(stream, memory) -> RnnOutputLayer (softmax, MCXENT)
+    Output = next-token distribution [mb, numLabels, Tt]. ``numLabels`` is the target vocabulary size,
+    ``sourceVocabSize`` the source's (default: the same). ``inputShape = [sourceLen, targetLen]``. Source padding goes
+    in as the first feature mask (``fit(..., featureMaskArrays=[srcMask, None])``): it masks the encoder's keys and is
+    the key-padding mask of every decoder block's cross-attention.
+
+    Generation: ``rnnClearPreviousState()``, ``rnnTimeStep(source, firstTargetTokens, masks=[srcMask, None])`` and
+    then ``rnnTimeStep(None, nextToken)`` per token: the encoder runs once, every decoder block keeps the memory's
+    key/value projection and its own self-attention cache."""
+    DEFAULT_SHAPE = [128, 128]
+
+    def __init__(self, numLabels=77, seed=12345, inputShape=None, sourceVocabSize=None, hidden=256, layers=4, heads=4,
+                 ffn=None, maxPositions=512, learningRate=1e-3, hiddenDropout=0.0, attentionDropout=0.0, **kw):
+        super().__init__(numLabels, seed, inputShape, **kw)
+        self.sourceVocabSize = int(sourceVocabSize) if sourceVocabSize else numLabels
+        self.hidden, self.layers, self.heads = hidden, layers, heads
+        self.ffn = int(ffn) if ffn else 4 * hidden
+        self.maxPositions, self.learningRate = maxPositions, learningRate
+        self.hiddenDropout, self.attentionDropout = hiddenDropout, attentionDropout
+
+    def graphBuilder(self):
+        from ..nn.conf import BertEmbeddingLayer, TransformerDecoderLayer, TransformerEncoderLayer
+        Ts, Tt = (list(self.inputShape) + list(self.inputShape))[:2]
+        g = (self._builder().updater(Adam(self.learningRate)).weightInit(NormalDistribution(0.0, 0.02))
+             .graphBuilder())
+        g.addInputs("source", "target")
+        g.addLayer("source_embeddings", BertEmbeddingLayer.Builder().nIn(self.sourceVocabSize).nOut(self.hidden)
+                   .maxPositions(self.maxPositions).inputLength(Ts).hiddenDropout(self.hiddenDropout).build(), "source")
+        mem = "source_embeddings"
+        for i in range(self.layers):
+            g.addLayer(f"encoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
+                       .nHeads(self.heads).ffnSize(self.ffn).hiddenDropout(self.hiddenDropout)
+                       .attentionDropout(self.attentionDropout).build(), mem)
+            mem = f"encoder_{i}"
+        g.addLayer("target_embeddings", BertEmbeddingLayer.Builder().nIn(self.numLabels).nOut(self.hidden)
+                   .maxPositions(self.maxPositions).inputLength(Tt).hiddenDropout(self.hiddenDropout).build(), "target")
+        prev = "target_embeddings"
+        for i in range(self.layers):
+            g.addLayer(f"decoder_{i}", TransformerDecoderLayer.Builder().nIn(self.hidden).nInMemory(self.hidden)
+                       .nOut(self.hidden).nHeads(self.heads).ffnSize(self.ffn).hiddenDropout(self.hiddenDropout)
+                       .attentionDropout(self.attentionDropout).build(), prev, mem)
+            prev = f"decoder_{i}"
+        g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
+                   .nIn(self.hidden).nOut(self.numLabels).build(), prev)
+        g.setOutputs("output")
+        return g
+
+    def conf(self):
+        return self.graphBuilder().build()
+
+    def init(self, device=None):
+        net = ComputationGraph(self.conf())
+        net.init(device=device)
+        return net

@@ -428,6 +428,8 @@ class LayerVertex(GraphVertex):
         t = inputTypes[0]
         if self.preProcessor is not None:
             t = self.preProcessor.getOutputType(t)
+        if getattr(self.layerConf, "N_INPUTS", 1) == 2:
+            return self.layerConf.getOutputType(layerIndex, t, inputTypes[1])
         return self.layerConf.getOutputType(layerIndex, t)
 
 

@@ -1481,6 +1481,96 @@ class TransformerEncoderLayer(FeedForwardLayer):
         return key.startswith("b") or key in ("ln1b", "ln2b")
 
 
+class _TwoInputLayer(FeedForwardLayer):
+    """A layer that takes two activations in a ComputationGraph (``N_INPUTS = 2``): its own stream [mb, nIn, Tq]
+    first, a memory [mb, nInMemory, Tk] second. The graph gives it no merge vertex, calls
+    ``activate(x, training, mask, memory=..., memoryMask=...)`` and takes a pair of epsilons from
+    ``backpropGradient``. The output is recurrent with the first input's length."""
+    N_INPUTS = 2
+    FIELDS = {"nInMemory": 0}
+
+    def getOutputType(self, layerIndex, inputType, memoryType=None):
+        T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
+        return InputType.recurrent(self.nOut, T)
+
+    def setNIn(self, inputType, override=False, memoryType=None):
+        if not self.nIn or override:
+            self.nIn = inputType.size
+        if memoryType is not None and (not self.nInMemory or override):
+            self.nInMemory = memoryType.size
+
+    def getPreProcessorForInputType(self, inputType):
+        return None
+
+
+class CrossAttentionLayer(_TwoInputLayer):
+    """Multi-head cross attention, the counterpart of ``SelfAttentionLayer`` for two sequences: the queries come from
+    the first input [mb, nIn, Tq], the keys and values from the second, the memory [mb, nInMemory, Tk]. The first
+    input's feature mask zeroes masked query rows; the memory's mask is the key-padding mask. There is no causal flag
+    (it has no meaning across two sequences) and no attention dropout. Graph-only: ``MultiLayerNetwork`` refuses it."""
+    FIELDS = {"nHeads": 1, "headSize": 0}
+    RUNTIME = "deeplearning4j_amd.nn.layers.attention:CrossAttentionLayerImpl"
+
+    def setNIn(self, inputType, override=False, memoryType=None):
+        super().setNIn(inputType, override, memoryType)
+        if not self.nOut:
+            self.nOut = self.nIn
+
+    def param_specs(self):
+        hs = self.headSize or (self.nOut // self.nHeads)
+        d = self.nHeads * hs
+        nm = self.nInMemory or self.nIn
+        return [ParamSpec("Wq", [self.nIn, d], "c", "weight", self.nIn, d),
+                ParamSpec("Wkv", [nm, 2 * d], "c", "weight", nm, d),
+                ParamSpec("Wo", [d, self.nOut], "c", "weight", d, self.nOut),
+                ParamSpec("bq", [1, d], "c", "bias"), ParamSpec("bkv", [1, 2 * d], "c", "bias"),
+                ParamSpec("bo", [1, self.nOut], "c", "bias")]
+
+    def is_bias(self, key):
+        return key.startswith("b")
+
+
+class TransformerDecoderLayer(_TwoInputLayer):
+    """One post-LN transformer decoder block of an encoder-decoder transformer: causal self-attention (the flash
+    kernels of the encoder block) -> LayerNorm(+residual) -> cross-attention over the encoder memory
+    (csrc/attention_cross.hip) -> LayerNorm(+residual) -> FFN (GELU) -> LayerNorm(+residual). First input: the
+    decoder stream [mb, nIn, Tq]; second input: the memory [mb, nInMemory, Tk], whose feature mask is the
+    key-padding mask of the cross-attention.
+
+    ``hiddenDropout`` / ``attentionDropout``: DROP probabilities in [0, 1), training only, 0.0 = off (the convention
+    of ``TransformerEncoderLayer``). ``hiddenDropout`` applies at all three LayerNorm sites; ``attentionDropout``
+    applies to the SELF-attention probabilities only: the cross-attention site has no probability dropout."""
+    FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "hiddenDropout": 0.0, "attentionDropout": 0.0}
+    RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerDecoderLayerImpl"
+
+    def _post_init(self):
+        super()._post_init()
+        _check_drop_prob(self, "hiddenDropout")
+        _check_drop_prob(self, "attentionDropout")
+
+    def setNIn(self, inputType, override=False, memoryType=None):
+        super().setNIn(inputType, override, memoryType)
+        self.nOut = self.nIn
+
+    def param_specs(self):
+        E, F = self.nIn, self.ffnSize
+        M = self.nInMemory or E
+        one, zero = dict(value=1.0), dict(value=0.0)
+        return [ParamSpec("Wqkv", [E, 3 * E], "c", "weight", E, E), ParamSpec("bqkv", [1, 3 * E], "c", "bias"),
+                ParamSpec("Wo", [E, E], "c", "weight", E, E), ParamSpec("bo", [1, E], "c", "bias"),
+                ParamSpec("ln1g", [1, E], "c", "const", **one), ParamSpec("ln1b", [1, E], "c", "const", **zero),
+                ParamSpec("Wq2", [E, E], "c", "weight", E, E), ParamSpec("bq2", [1, E], "c", "bias"),
+                ParamSpec("Wkv2", [M, 2 * E], "c", "weight", M, E), ParamSpec("bkv2", [1, 2 * E], "c", "bias"),
+                ParamSpec("Wo2", [E, E], "c", "weight", E, E), ParamSpec("bo2", [1, E], "c", "bias"),
+                ParamSpec("ln2g", [1, E], "c", "const", **one), ParamSpec("ln2b", [1, E], "c", "const", **zero),
+                ParamSpec("W1", [E, F], "c", "weight", E, F), ParamSpec("b1", [1, F], "c", "bias"),
+                ParamSpec("W2", [F, E], "c", "weight", F, E), ParamSpec("b2", [1, E], "c", "bias"),
+                ParamSpec("ln3g", [1, E], "c", "const", **one), ParamSpec("ln3b", [1, E], "c", "const", **zero)]
+
+    def is_bias(self, key):
+        return key.startswith("b") or key in ("ln1b", "ln2b", "ln3b")
+
+
 class BertEmbeddingLayer(FeedForwardLayer):
     """Token ids [mb, T] -> LayerNorm(word + position + token-type(0) embeddings) as [mb, nOut, T]
     (nIn = vocabulary size). ``hiddenDropout``: DROP probability in [0, 1) applied after the LayerNorm in training

@@ -252,8 +252,9 @@ def _updater_state(lc):
     return n
 
 
-def layer_memory_report(lc, inputType, outputType, name=None, compute_bytes=None):
-    """Estimate one layer's memory. ``compute_bytes``: element size of a reduced-precision compute shadow."""
+def layer_memory_report(lc, inputType, outputType, name=None, compute_bytes=None, memoryType=None):
+    """Estimate one layer's memory. ``compute_bytes``: element size of a reduced-precision compute shadow.
+    ``memoryType``: the second input's type of a two-input layer (CrossAttentionLayer, TransformerDecoderLayer)."""
     t = type(lc).__name__
     base = lc.underlying if getattr(lc, "underlying", None) is not None and t in ("FrozenLayer",) else lc
     bt = type(base).__name__
@@ -281,6 +282,18 @@ def layer_memory_report(lc, inputType, outputType, name=None, compute_bytes=None
     elif bt == "SelfAttentionLayer":
         T = getattr(inputType, "timeSeriesLength", 1) or 1
         wvi = wvt = 3 * outE + getattr(base, "nHeads", 1) * T * T
+    elif bt in ("CrossAttentionLayer", "TransformerDecoderLayer"):
+        # q / context / output rows of the own stream, the memory's kv projection; the flash kernels keep lse only
+        Tq = max(getattr(inputType, "timeSeriesLength", 1) or 1, 1)
+        Tk = max(getattr(memoryType, "timeSeriesLength", 1) or 1, 1)
+        E = getattr(base, "nOut", 0) or 0
+        H = getattr(base, "nHeads", 1)
+        wvi = 3 * Tq * E + 2 * Tk * E
+        wvt = wvi + H * Tq
+        if bt == "TransformerDecoderLayer":
+            wvi += 4 * Tq * E + Tq * base.ffnSize
+            wvt += 9 * Tq * E + 2 * Tq * base.ffnSize + H * Tq
+        cache_var = inE + (memoryType.arrayElementsPerExample() if memoryType is not None else 0)
     if compute_bytes:
         wfi += nparams * compute_bytes // 4
         wft += nparams * compute_bytes // 4
@@ -320,10 +333,11 @@ def cg_memory_report(conf, inputTypes=None):
         out = v.getOutputType(i, *ins)
         types[name] = out
         if isinstance(v, LayerVertex):
-            t = ins[0] if len(ins) == 1 else out
+            two = getattr(v.layerConf, "N_INPUTS", 1) == 2
+            t = ins[0] if len(ins) == 1 or two else out
             if v.preProcessor is not None:
                 t = v.preProcessor.getOutputType(t)
-            reps[name] = layer_memory_report(v.layerConf, t, out, name)
+            reps[name] = layer_memory_report(v.layerConf, t, out, name, memoryType=ins[1] if two else None)
         else:
             reps[name] = LayerMemoryReport(name, type(v).__name__, ins[0] if ins else None, out)
     return NetworkMemoryReport(reps, "ComputationGraph", "ComputationGraph", its)

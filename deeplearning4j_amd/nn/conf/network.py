@@ -378,6 +378,12 @@ class ListBuilder:
             raise IllegalStateException(f"Invalid configuration: layer indices must be contiguous from 0: got "
                                         f"{sorted(self._layers)}")
         confs = [copy.deepcopy(self._layers[i]) for i in range(n)]
+        for i, c in enumerate(confs):
+            if getattr(c, "N_INPUTS", 1) != 1:
+                from ...exceptions import DL4JInvalidConfigException
+                raise DL4JInvalidConfigException(
+                    f"Invalid configuration: layer {i} ({type(c).__name__}) takes {c.N_INPUTS} inputs and cannot be "
+                    "part of a MultiLayerNetwork; use a ComputationGraph")
         g = self._g
         for c in confs:
             c.applyGlobal(g)
@@ -522,6 +528,11 @@ class MultiLayerConfiguration(_Counters, Config):
         return from_json(d) if is_dl4j_format(d) else _decode(d)
 
 
+def _two_input(vertex):
+    """A LayerVertex whose layer takes two activations unconcatenated (``N_INPUTS = 2``, e.g. CrossAttentionLayer)."""
+    return isinstance(vertex, LayerVertex) and getattr(vertex.layerConf, "N_INPUTS", 1) == 2
+
+
 class GraphBuilder:
     def __init__(self, g):
         self._g = g
@@ -629,6 +640,8 @@ class GraphBuilder:
             ins = self._vertexInputs.get(name, [])
             if len(ins) < 2 or type(self._vertices[name]).__name__ not in self._SINGLE_INPUT:
                 continue
+            if _two_input(self._vertices[name]):
+                continue                      # takes its two activations unconcatenated (checked in build())
             mname = f"{name}-merge"
             self._vertices[mname] = MergeVertex()
             self._vertexInputs[mname] = list(ins)
@@ -667,6 +680,19 @@ class GraphBuilder:
                 raise DL4JInvalidConfigException(
                     f"Invalid configuration: disconnected vertices found - {dis} are not connected to the network "
                     "output; use .allowDisconnected(True) to build it anyway")
+        for v, vx in self._vertices.items():
+            if not _two_input(vx):
+                continue
+            from ...exceptions import DL4JInvalidConfigException
+            kind = type(vx.layerConf).__name__
+            if len(self._vertexInputs[v]) != 2:
+                raise DL4JInvalidConfigException(
+                    f"Invalid configuration: layer {v!r} ({kind}) takes exactly two inputs (its own stream, then the "
+                    f"memory), got {len(self._vertexInputs[v])}: {self._vertexInputs[v]}")
+            if self._bpType == BackpropType.TruncatedBPTT:
+                raise DL4JInvalidConfigException(
+                    f"Invalid configuration: layer {v!r} ({kind}) attends over a whole second sequence and cannot be "
+                    "trained with truncated BPTT; use BackpropType.Standard")
         self._add_merge_vertices()
         conf = ComputationGraphConfiguration(
             vertices={k: self._vertices[k] for k in self._order}, vertexInputs=dict(self._vertexInputs),
@@ -749,7 +775,13 @@ class ComputationGraphConfiguration(_Counters, Config):
                 continue
             v = self.vertices[name]
             ins = [types[x] for x in self.vertexInputs[name]]
-            if isinstance(v, LayerVertex):
+            if _two_input(v):
+                t = ins[0]
+                if v.preProcessor is not None:
+                    t = v.preProcessor.getOutputType(t)
+                v.layerConf.setNIn(t, False, memoryType=ins[1])
+                types[name] = v.layerConf.getOutputType(i, t, ins[1])
+            elif isinstance(v, LayerVertex):
                 t = ins[0]
                 if len(ins) > 1:
                     from .graph import MergeVertex
@@ -781,8 +813,10 @@ class ComputationGraphConfiguration(_Counters, Config):
         return from_json(d) if is_dl4j_format(d) else _decode(d)
 
     def toYaml(self):
+        # the JSON's key order, not a sorted one: the order of the vertices is part of the configuration (it breaks
+        # ties of the topological order, hence the layout of the flat parameters)
         import yaml
-        return yaml.safe_dump(json.loads(self.toJson()), sort_keys=True)
+        return yaml.safe_dump(json.loads(self.toJson()), sort_keys=False)
 
     @staticmethod
     def fromYaml(s):

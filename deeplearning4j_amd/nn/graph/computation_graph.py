@@ -40,6 +40,17 @@ def _shares_storage(a, b):
 
 
 
+def _memory_3d(mem, mask, mb):
+    """The memory of a two-input layer in recurrent format: a feed-forward activation [Tk*mb, M] (a DenseLayer behind
+    an RnnToFeedForwardPreProcessor) and its per-row mask go back to [mb, M, Tk] / [mb, Tk].
+    -> (memory, mask, whether it was converted)."""
+    if mem is None or mem.dim() != 2:
+        return mem, mask, False
+    from ..conf.preprocessors import FeedForwardToRnnPreProcessor
+    pp = FeedForwardToRnnPreProcessor()
+    return pp.preProcess(mem, mb, False), pp.feedForwardMaskArray(mask, None, mb)[0], True
+
+
 def _out_dtype(t):
     """16-bit activations come back as fp32 (the reference's output dtype); fp32/fp64 graphs keep theirs."""
     return t.float() if t.dtype in (torch.bfloat16, torch.float16) else t
@@ -315,8 +326,9 @@ class ComputationGraph(BaseNetwork):
             ms = [amask.get(i) for i in self.vertex_inputs[name]]
             active[name] = any(active.get(i, True) for i in self.vertex_inputs[name])
             if isinstance(v, LayerVertex):
-                x = ins[0] if len(ins) == 1 else torch.cat(ins, dim=1)
-                if len(ins) > 1:
+                two = getattr(v.layerConf, "N_INPUTS", 1) == 2      # own stream + memory, unconcatenated
+                x = ins[0] if len(ins) == 1 or two else torch.cat(ins, dim=1)
+                if len(ins) > 1 and not two:
                     self._ctx[name] = ("merge", [t.shape[1] for t in ins])
                 mask = ms[0] if ms else None
                 if v.preProcessor is not None:
@@ -336,7 +348,14 @@ class ComputationGraph(BaseNetwork):
                 tok = _prof.layer_begin("fwd", name, layer) if _prof.ACTIVE else None
                 if not active[name] and hasattr(layer, "setLabels"):
                     mask = None             # a passed-through feature mask does not mask an output layer
-                if stored_state and hasattr(layer, "tBpttStateMap"):
+                if two:
+                    # the first input's mask is the layer's (query) mask and its outgoing mask, the second's the
+                    # key-padding mask of the memory
+                    mem, mmask, ff = _memory_3d(ins[1], ms[1], mb)
+                    if ff:
+                        self._ctx[name] = ("memory_ff",)
+                    out = layer.activate(x, train, mask, memory=mem, memoryMask=mmask)
+                elif stored_state and hasattr(layer, "tBpttStateMap"):
                     out = layer.activate(x, train, mask, stored_state=True, store_last_for_tbptt=store_last_for_tbptt)
                 else:
                     out = layer.activate(x, train, mask)
@@ -449,10 +468,19 @@ class ComputationGraph(BaseNetwork):
                         layer.dresidual = None
                 if e is None or not self._need_input_grad[name]:
                     continue
+                if isinstance(e, tuple) and self._ctx.get(name) == ("memory_ff",):
+                    from ..conf.preprocessors import FeedForwardToRnnPreProcessor
+                    e = (e[0], FeedForwardToRnnPreProcessor().backprop(e[1], self._mb))
                 if v.preProcessor is not None:
-                    e = v.preProcessor.backprop(e, self._mb)
+                    e = (v.preProcessor.backprop(e[0], self._mb),) + tuple(e[1:]) if isinstance(e, tuple) else \
+                        v.preProcessor.backprop(e, self._mb)
                 ins = self.vertex_inputs[name]
-                if len(ins) > 1:
+                if isinstance(e, tuple):
+                    # a two-input layer hands back (eps of its own stream, eps of the memory); the memory's sums over
+                    # every layer that reads it
+                    for i, p in zip(ins, e):
+                        add(i, p)
+                elif len(ins) > 1:
                     parts = torch.split(e, self._ctx[name][1], dim=1)
                     for i, p in zip(ins, parts):
                         add(i, p)
@@ -671,31 +699,65 @@ class ComputationGraph(BaseNetwork):
         return list(evals)
 
     # ------------------------------------------------------------------------------ rnn
-    def rnnTimeStep(self, *inputs):
-        inputs = self._prep_inputs(list(inputs))
-        mb = inputs[0].shape[0]          # a FF->RNN preprocessor reshapes [mb*T, n] rows back by the INPUT minibatch
+    def rnnTimeStep(self, *inputs, masks=None):
+        """One step / chunk per network input. An input may be ``None`` (e.g. the source of an encoder-decoder model
+        after the first call): ``None`` propagates through every vertex whose inputs are all ``None``, which is not
+        run, and a two-input layer whose memory is ``None`` uses the memory projection it stored. ``masks``: optional
+        feature masks, one per network input (``None`` entries allowed), e.g. the source padding of the first call;
+        a mask follows its activation as in ``feedForward`` and reaches a two-input layer as its key-padding mask."""
+        given = [i for i, x in enumerate(inputs) if x is not None]
+        if not given:
+            raise DL4JInvalidInputException("rnnTimeStep needs at least one input that is not None")
+        prepped = self._prep_inputs([inputs[i] for i in given])
+        inputs = list(inputs)
+        for i, x in zip(given, prepped):
+            inputs[i] = x
+        mb = inputs[given[0]].shape[0]   # a FF->RNN preprocessor reshapes [mb*T, n] rows back by the INPUT minibatch
         acts = {n: inputs[i] for i, n in enumerate(self.conf.networkInputs)}
+        mm = {n: self._to_dev(masks[i]) for i, n in enumerate(self.conf.networkInputs)
+              if masks is not None and i < len(masks) and masks[i] is not None and inputs[i] is not None}
         with torch.no_grad():
             for name in self.topo:
                 v = self.conf.vertices[name]
                 if name in self._passthrough:
                     acts[name] = acts[self._passthrough[name]]
+                    mm[name] = mm.get(self._passthrough[name])
                     continue
                 ins = [acts[i] for i in self.vertex_inputs[name]]
+                if all(t is None for t in ins):
+                    acts[name] = None
+                    continue
+                ms = [mm.get(i) for i in self.vertex_inputs[name]]
+                two = isinstance(v, LayerVertex) and getattr(v.layerConf, "N_INPUTS", 1) == 2
+                if any(t is None for t in ins) and not (two and ins[0] is not None):
+                    raise DL4JInvalidInputException(
+                        f"rnnTimeStep: vertex {name!r} has inputs {self.vertex_inputs[name]} of which only some are "
+                        "None; only the memory of a two-input layer may be left out")
                 if isinstance(v, LayerVertex):
-                    x = ins[0] if len(ins) == 1 else torch.cat(ins, 1)
+                    x = ins[0] if len(ins) == 1 or two else torch.cat(ins, 1)
                     if v.preProcessor is not None:
                         x = v.preProcessor.preProcess(x, mb, False)
                     layer = self.layers_by_name[name]
                     if name in self._residual_of:
                         layer.residual = acts[self._residual_of[name]]
-                    if hasattr(layer, "rnnTimeStep"):
-                        acts[name] = layer.rnnTimeStep(x)
+                    mask = ms[0]
+                    if mask is not None and v.preProcessor is not None:
+                        mask, _ = v.preProcessor.feedForwardMaskArray(mask, None, mb)
+                    if two:
+                        mem, mmask, _ = _memory_3d(ins[1], ms[1], mb)
+                        acts[name] = layer.rnnTimeStep(x, mask, memory=mem, memoryMask=mmask)
+                    elif hasattr(layer, "rnnTimeStep"):
+                        acts[name] = layer.rnnTimeStep(x) if mask is None else layer.rnnTimeStep(x, mask)
                     else:
-                        acts[name] = layer.activate(x, False)
+                        acts[name] = layer.activate(x, False) if mask is None else layer.activate(x, False, mask)
+                    if mask is not None:
+                        mm[name], _ = layer.feedForwardMaskArray(mask, None, mb)
                 else:
-                    acts[name], _ = v.forward(ins, False, None)
-        return [_out_dtype(acts[o]) for o in self.outputs]
+                    has_mask = any(m is not None for m in ms)
+                    acts[name], _ = v.forward(ins, False, ms if has_mask else None)
+                    if has_mask:
+                        mm[name] = v.feedForwardMask(ms)
+        return [None if acts[o] is None else _out_dtype(acts[o]) for o in self.outputs]
 
     def rnnClearPreviousState(self):
         for l in self.layers_by_name.values():

@@ -16,11 +16,16 @@ Feature masks [mb, T] mask padded keys; masked query rows produce zeros.
 the layer's PhiloxStream and regenerated in the backward; the explicit path takes its mask from ``dropoutKeep``.
 ``rnnTimeStep`` on a causal layer appends the chunk's K / V to a per-layer cache and attends over it
 (``KVCacheState`` in transformer.py, csrc/attention_decode.hip).
+
+``CrossAttentionLayerImpl`` is the two-sequence counterpart (a two-input graph layer): Q = X Wq + bq from its own
+stream [mb, nIn, Tq], KV = M Wkv + bkv from the memory [mb, nInMemory, Tk] in one GEMM straight into the
+kv [mb, Tk, 2d] layout of csrc/attention_cross.hip; backward dWo, dbo, dO = dY Wo^T, (dQ, dKV) from the cross
+backward kernels, dWq / dWkv and their biases, dX = dQ Wq^T, dM = dKV Wkv^T, returned as the pair (dX, dM).
 """
 import torch
 
 from .base import LayerImpl, bias_grad_, matmul, weight_grad_
-from .transformer import DropoutSites, KVCacheState
+from .transformer import DropoutSites, KVCacheState, MemoryKVState, _cross_bwd, _cross_fwd, _memory_mask
 from ...ops.gemm import mmul
 
 
@@ -138,3 +143,91 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         self._c = None
         eps_prev = dX.reshape(mb, T, -1).permute(0, 2, 1)
         return self.make_gradient(), eps_prev
+
+
+class CrossAttentionLayerImpl(MemoryKVState, LayerImpl):
+    def type(self):
+        return "RECURRENT"
+
+    def _dims(self):
+        c = self.conf
+        hs = c.headSize or (c.nOut // c.nHeads)
+        return c.nHeads, hs, c.nHeads * hs
+
+    def _forward(self, X, kv, mb, T, Tk, mm, m, what):
+        H, hs, d = self._dims()
+        q = matmul(X, self.W("Wq"), bias=self.Wbias("bq"))
+        o2, cctx = _cross_fwd(q, kv, mb, T, Tk, H, mm, what)
+        Y = matmul(o2, self.W("Wo"), bias=self.Wbias("bo"))
+        if m is not None:
+            Y = Y * m.reshape(mb * T, 1).to(Y.dtype)
+        return q, o2, cctx, Y.reshape(mb, T, -1).permute(0, 2, 1)
+
+    def activate(self, x, training=False, mask=None, memory=None, memoryMask=None, **kw):
+        if memory is None:
+            from ...exceptions import DL4JInvalidInputException
+            raise DL4JInvalidInputException(
+                f"layer {self.index} ({type(self.conf).__name__}) takes two inputs: its own stream and a memory")
+        self.training = training
+        mb, nIn, T = x.shape
+        Tk = memory.shape[2]
+        dt = self.W("Wq").dtype
+        X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
+        M = memory.permute(0, 2, 1).reshape(mb * Tk, memory.shape[1]).to(dt).contiguous()
+        kv = matmul(M, self.W("Wkv"), bias=self.Wbias("bkv")).reshape(mb, Tk, -1)
+        m = mask.reshape(mb, T) if mask is not None else None
+        mm = _memory_mask(memoryMask, mb, Tk)
+        q, o2, cctx, z = self._forward(X, kv, mb, T, Tk, mm, m, "CrossAttentionLayer")
+        self.input = x
+        self.maskArray = mask
+        if training:
+            self._c = (X, M, q, kv, cctx, o2, m, mm, mb, T, Tk)
+        self._z = z
+        return self.conf.activation.getActivation(z, training) if self.conf.activation is not None else z
+
+    def backpropGradient(self, eps, **kw):
+        X, M, q, kv, cctx, o2, m, mm, mb, T, Tk = self._c
+        self._c = None
+        H, hs, d = self._dims()
+        dz = self.conf.activation.backprop(self._z, eps.to(self._z.dtype)) if self.conf.activation is not None \
+            else eps
+        dt = X.dtype
+        dY = dz.permute(0, 2, 1).reshape(mb * T, -1).to(dt)
+        if m is not None:
+            dY = dY * m.reshape(mb * T, 1).to(dt)
+        dY = dY.contiguous()
+        weight_grad_(self.grads["Wo"], o2.t(), dY)
+        bias_grad_(self.grads["bo"], dY)
+        dO = matmul(dY, self.W("Wo").t())
+        dq, dkv = _cross_bwd(dO, q, kv, mb, T, Tk, H, mm, cctx)
+        weight_grad_(self.grads["Wq"], X.t(), dq)
+        bias_grad_(self.grads["bq"], dq)
+        weight_grad_(self.grads["Wkv"], M.t(), dkv)
+        bias_grad_(self.grads["bkv"], dkv)
+        dX = matmul(dq, self.W("Wq").t())
+        dM = matmul(dkv, self.W("Wkv").t())
+        return self.make_gradient(), (dX.reshape(mb, T, -1).permute(0, 2, 1), dM.reshape(mb, Tk, -1).permute(0, 2, 1))
+
+    def rnnTimeStep(self, x, mask=None, memory=None, memoryMask=None):
+        """One chunk [mb, nIn, Tn] (or one step [mb, nIn]) attending over the stored memory projection, which is
+        computed when ``memory`` is given and reused while it is None."""
+        self.training = False
+        one = x.dim() == 2
+        if one:
+            x = x.unsqueeze(2)
+        mb, nIn, T = x.shape
+        kv, Tk, mm = self.memoryProject(x, memory, memoryMask, "Wkv", "bkv")
+        X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(self.W("Wq").dtype).contiguous()
+        m = mask.reshape(mb, T) if mask is not None else None
+        z = self._forward(X, kv, mb, T, Tk, mm, m, "CrossAttentionLayer rnnTimeStep")[3]
+        y = self.conf.activation.getActivation(z, False) if self.conf.activation is not None else z
+        return y[:, :, 0] if one else y
+
+    def rnnClearPreviousState(self):
+        self.memoryClear()
+
+    def rnnGetPreviousState(self):
+        return self.memoryGet()
+
+    def rnnSetPreviousState(self, state):
+        self.memorySet(state)

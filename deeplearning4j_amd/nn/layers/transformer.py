@@ -27,6 +27,11 @@ Generation (``rnnTimeStep``): a causal block keeps a key/value cache (``KVCacheS
 its K / V appended, its queries attend over the cache (csrc/attention_decode.hip, or the torch reference off the
 kernels) and the rest of the block runs as in the inference forward; the embedding layer continues its positions.
 A bidirectional block cannot stream and runs ``activate`` on the chunk.
+
+Decoder block (``TransformerDecoderLayerImpl``, a two-input graph layer: decoder stream + encoder memory): causal
+self-attention as above, then cross-attention of q2 = h1·Wq2 over kv2 = memory·Wkv2 (one GEMM straight into the
+kv [mb, Tk, 2E] layout of csrc/attention_cross.hip), then the FFN, each followed by LayerNorm(+residual). Its
+``rnnTimeStep`` keeps kv2 and the memory's mask (``MemoryKVState``) next to the self-attention cache.
 """
 import math
 
@@ -353,7 +358,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         stream and runs ``activate`` on the chunk."""
         c = self.conf
         if not c.causal:
-            return self.activate(x, False)
+            return self.activate(x, False, mask)
         self.training = False
         one = x.dim() == 2
         if one:
@@ -410,6 +415,231 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         dx = mmul(dqkv, self.W("Wqkv").t(), out=ds1, beta=1.0)
         E = dx.shape[1]
         return self.make_gradient(), dx.reshape(B, T, E).permute(0, 2, 1)
+
+
+# ------------------------------------------------------------------------------------------------ cross attention
+def _cross_fwd(q, kv, B, Tq, Tk, H, kmask, what="cross attention"):
+    """Attention of q [B*Tq, E] over rows [0, Tk) of kv [B, TkCap, 2E] (csrc/attention_cross.hip on a GPU in bf16 /
+    fp16 with head size 64 / 128, else the explicit torch path, counted as a fallback on a GPU).
+    -> (out [B*Tq, E], ctx for _cross_bwd)."""
+    from ...ops import transformer_native as TN
+    q3 = q.reshape(B, Tq, -1)
+    if _native(q3, "attention") and TN.cross_attn_supported(q3, kv, H):
+        r = TN.cross_attn_fwd(q3, kv, H, Tk, kmask)
+        if r is not None:
+            return r[0].reshape(B * Tq, -1), ("native", r[0], r[1])
+    if q.is_cuda:
+        from ...ops import fallback
+        fallback.record("attention", f"{what} head size {q3.shape[-1] // H} / dtype {q.dtype}: explicit torch path")
+    o, ctx = TN.cross_attention_fwd_explicit(q3, kv[:, :Tk], H, kmask)
+    return o.reshape(B * Tq, -1), ("explicit", ctx)
+
+
+def _cross_bwd(dctx, q, kv, B, Tq, Tk, H, kmask, ctx):
+    """-> (dq [B*Tq, E], dkv [B*Tk, 2E])."""
+    from ...ops import transformer_native as TN
+    if ctx[0] == "native":
+        dq, dkv = TN.cross_attn_bwd(q.reshape(B, Tq, -1), kv, ctx[1], ctx[2], dctx.reshape(B, Tq, -1), H, kmask, Tk=Tk)
+    else:
+        dq, dkv = TN.cross_attention_bwd_explicit(ctx[1], dctx.reshape(B, Tq, -1), q.dtype)
+    return dq.reshape(B * Tq, -1), dkv.reshape(B * Tk, -1)
+
+
+def _memory_mask(memoryMask, B, Tk):
+    """The key-padding mask as the cross kernels take it: fp32 [B, Tk] contiguous, or None."""
+    return None if memoryMask is None else memoryMask.reshape(B, Tk).to(torch.float32).contiguous()
+
+
+class MemoryKVState:
+    """rnnTimeStep state of a layer that attends over a memory: the memory's projection ``kv [mb, Tk, 2E]`` (the
+    layout of csrc/attention_cross.hip) and its key-padding mask, computed on the first call after
+    rnnClearPreviousState() that carries a memory and kept for the later steps, which pass ``memory=None``. Handed out
+    / taken in as ``{"mem_kv": [mb, Tk, 2E], "mem_mask": [mb, Tk] or absent}``."""
+    _mem_kv = None
+    _mem_mask = None
+
+    def memoryClear(self):
+        self._mem_kv = self._mem_mask = None
+
+    def memoryGet(self):
+        if self._mem_kv is None:
+            return {}
+        st = {"mem_kv": self._mem_kv.clone()}
+        if self._mem_mask is not None:
+            st["mem_mask"] = self._mem_mask.clone()
+        return st
+
+    def memorySet(self, state):
+        self.memoryClear()
+        kv = state.get("mem_kv") if state else None
+        if kv is None:
+            return
+        self._mem_kv = kv.contiguous().clone()
+        m = state.get("mem_mask")
+        self._mem_mask = None if m is None else _memory_mask(m, kv.shape[0], kv.shape[1]).clone()
+
+    def memoryProject(self, x, memory, memoryMask, wkey, bkey):
+        """The stored projection for a step on x [mb, E, Tn]: projected now when ``memory`` [mb, M, Tk] is given
+        (one GEMM straight into the kv layout), else the one kept from an earlier call. -> (kv, Tk, mask)."""
+        from ...exceptions import DL4JInvalidInputException
+        who = f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__})"
+        if memory is not None:
+            mb, M, Tk = memory.shape
+            mt = _token_major(memory).to(self.W(wkey).dtype)
+            self._mem_kv = matmul(mt, self.W(wkey), bias=self.Wbias(bkey)).reshape(mb, Tk, -1)
+            self._mem_mask = _memory_mask(memoryMask, mb, Tk)
+        elif self._mem_kv is None:
+            raise DL4JInvalidInputException(
+                f"{who}: no memory given and none stored; pass the memory on the first call after "
+                "rnnClearPreviousState()")
+        if self._mem_kv.shape[0] != x.shape[0]:
+            raise DL4JInvalidInputException(
+                f"{who}: minibatch size {x.shape[0]} differs from the stored memory's {self._mem_kv.shape[0]}; call "
+                "rnnClearPreviousState() before changing it")
+        return self._mem_kv, self._mem_kv.shape[1], self._mem_mask
+
+
+class TransformerDecoderLayerImpl(MemoryKVState, KVCacheState, DropoutSites, LayerImpl):
+    """Post-LN decoder block (conf: TransformerDecoderLayer), token-major like the encoder block:
+      qkv = x·Wqkv + b;  h1 = LN(drop(causal_attention(qkv)·Wo + bo) + x)            self-attention (csrc/attention.hip)
+      q2 = h1·Wq2 + b;  kv2 = mem·Wkv2 + b;  h2 = LN(drop(cross(q2, kv2)·Wo2 + bo2) + h1)   (csrc/attention_cross.hip)
+      y  = LN(drop(gelu(h2·W1 + b1)·W2 + b2) + h2)
+    The backward is written out by hand with the encoder block's pieces; it returns (dx, dmemory)."""
+    SITES = DropoutSites.SITES + ("hidden3",)
+
+    def type(self):
+        return "RECURRENT"
+
+    def activate(self, x, training=False, mask=None, memory=None, memoryMask=None, **kw):
+        c = self.conf
+        if memory is None:
+            from ...exceptions import DL4JInvalidInputException
+            raise DL4JInvalidInputException(
+                f"layer {self.index} ({type(c).__name__}) takes two inputs: its own stream and a memory")
+        self.training = training
+        B, E, T = x.shape
+        Tk = memory.shape[2]
+        H = c.nHeads
+        dt = self.W("Wqkv").dtype
+        xt = _token_major(x).to(dt)
+        mt = _token_major(memory).to(dt)
+        m = mask.reshape(B, T) if mask is not None else None
+        mm = _memory_mask(memoryMask, B, Tk)
+        pa, ph = (float(c.attentionDropout), float(c.hiddenDropout)) if training else (0.0, 0.0)
+        if pa > 0.0 or ph > 0.0:
+            self.dropoutBegin(x.device)
+        eps = c.layerNormEps
+        P = self.params
+        qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        ctx1, actx = _attn_fwd(qkv, B, T, H, m, True, pa, self)
+        a = matmul(ctx1, self.W("Wo"), bias=self.Wbias("bo"))
+        h1, ln1, a, d1 = _ln_fwd_drop(a, xt, P["ln1g"], P["ln1b"], eps, ph, self, "hidden1")
+        q2 = matmul(h1, self.W("Wq2"), bias=self.Wbias("bq2"))
+        kv2 = matmul(mt, self.W("Wkv2"), bias=self.Wbias("bkv2")).reshape(B, Tk, -1)
+        ctx2, cctx = _cross_fwd(q2, kv2, B, T, Tk, H, mm, "TransformerDecoderLayer")
+        cc = matmul(ctx2, self.W("Wo2"), bias=self.Wbias("bo2"))
+        h2, ln2, cc, d2 = _ln_fwd_drop(cc, h1, P["ln2g"], P["ln2b"], eps, ph, self, "hidden2")
+        z1 = torch.empty(h2.shape[0], self.W("W1").shape[1], dtype=h2.dtype, device=h2.device)
+        f = matmul(h2, self.W("W1"), bias=self.Wbias("b1"), act="gelu", z=z1)
+        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        y, ln3, f2, d3 = _ln_fwd_drop(f2, h2, P["ln3g"], P["ln3b"], eps, ph, self, "hidden3")
+        self.maskArray = mask
+        if training:
+            self._c = (xt, mt, qkv, actx, ctx1, a, ln1, h1, q2, kv2, cctx, ctx2, cc, ln2, h2, z1, f, f2, ln3, B, T, Tk,
+                       m, mm, d1, d2, d3)
+        self.input = x
+        return y.reshape(B, T, E).permute(0, 2, 1)
+
+    def backpropGradient(self, eps, **kw):
+        c = self.conf
+        (xt, mt, qkv, actx, ctx1, a, ln1, h1, q2, kv2, cctx, ctx2, cc, ln2, h2, z1, f, f2, ln3, B, T, Tk, m, mm, d1, d2,
+         d3) = self._c
+        self._c = None
+        g = self.grads
+        P = self.params
+        H = c.nHeads
+        dy = _token_major(eps).to(xt.dtype)
+
+        def site(d, x, res, gk, bk, ln, bias, dctx):
+            # (residual gradient, producer gradient): one tensor without hidden dropout, whose column sums (the
+            # producer's bias gradient) come out of the LayerNorm backward launch; with it the producer's is ds∘D
+            if dctx is None:
+                ds = _ln_bwd(d, x, res, P[gk], ln, g[gk], g[bk], g[bias])
+                return ds, ds
+            ds = _ln_bwd(d, x, res, P[gk], ln, g[gk], g[bk])
+            dp = _drop_bwd(ds, dctx)
+            _bsum(g[bias], dp)
+            return ds, dp
+
+        ds3, df2 = site(dy, f2, h2, "ln3g", "ln3b", ln3, "b2", d3)
+        _wgrad(g["W2"], f, df2)
+        if _native(df2, "gemm") and z1.dtype == df2.dtype:
+            dz1 = mmul(df2, self.W("W2").t(), act="dgelu", z=z1)
+        else:
+            dz1 = _gelu_bwd(z1, matmul(df2, self.W("W2").t()))
+        _wgrad(g["W1"], h2, dz1)
+        _bsum(g["b1"], dz1)
+        dh2 = mmul(dz1, self.W("W1").t(), out=ds3, beta=1.0)          # residual gradient summed in place
+        ds2, dcc = site(dh2, cc, h1, "ln2g", "ln2b", ln2, "bo2", d2)
+        _wgrad(g["Wo2"], ctx2, dcc)
+        dctx2 = matmul(dcc, self.W("Wo2").t())
+        dq2, dkv2 = _cross_bwd(dctx2, q2, kv2, B, T, Tk, H, mm, cctx)
+        _wgrad(g["Wq2"], h1, dq2)
+        _bsum(g["bq2"], dq2)
+        _wgrad(g["Wkv2"], mt, dkv2)
+        _bsum(g["bkv2"], dkv2)
+        dmem = matmul(dkv2, self.W("Wkv2").t())
+        dh1 = mmul(dq2, self.W("Wq2").t(), out=ds2, beta=1.0)
+        ds1, da = site(dh1, a, xt, "ln1g", "ln1b", ln1, "bo", d1)
+        _wgrad(g["Wo"], ctx1, da)
+        dctx1 = matmul(da, self.W("Wo").t())
+        dqkv = _attn_bwd(dctx1, qkv, B, T, H, m, True, actx)
+        _wgrad(g["Wqkv"], xt, dqkv)
+        _bsum(g["bqkv"], dqkv)
+        dx = mmul(dqkv, self.W("Wqkv").t(), out=ds1, beta=1.0)
+        E = dx.shape[1]
+        return self.make_gradient(), (dx.reshape(B, T, E).permute(0, 2, 1),
+                                      dmem.reshape(B, Tk, -1).permute(0, 2, 1))
+
+    def rnnTimeStep(self, x, mask=None, memory=None, memoryMask=None):
+        """One chunk [mb, E, Tn] (or one step [mb, E]): the self-attention continues its key/value cache, the
+        cross-attention runs the forward kernel (Tq = Tn) over the stored memory projection, which is computed when
+        ``memory`` is given and reused while it is None."""
+        c = self.conf
+        self.training = False
+        one = x.dim() == 2
+        if one:
+            x = x.unsqueeze(2)
+        self._check_state_mb(x)
+        B, E, T = x.shape
+        H = c.nHeads
+        P = self.params
+        kv2, Tk, mm = self.memoryProject(x, memory, memoryMask, "Wkv2", "bkv2")
+        xt = _token_major(x).to(self.W("Wqkv").dtype)
+        qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        ctx1 = self.cachedAttention(qkv.reshape(B, T, -1), H).reshape(B * T, -1)
+        a = matmul(ctx1, self.W("Wo"), bias=self.Wbias("bo"))
+        h1, _ = _ln_fwd(a, xt, P["ln1g"], P["ln1b"], c.layerNormEps)
+        q2 = matmul(h1, self.W("Wq2"), bias=self.Wbias("bq2"))
+        ctx2, _ = _cross_fwd(q2, kv2, B, T, Tk, H, mm, "TransformerDecoderLayer rnnTimeStep")
+        cc = matmul(ctx2, self.W("Wo2"), bias=self.Wbias("bo2"))
+        h2, _ = _ln_fwd(cc, h1, P["ln2g"], P["ln2b"], c.layerNormEps)
+        f = matmul(h2, self.W("W1"), bias=self.Wbias("b1"), act="gelu")
+        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        y, _ = _ln_fwd(f2, h2, P["ln3g"], P["ln3b"], c.layerNormEps)
+        y = y.reshape(B, T, E).permute(0, 2, 1)
+        return y[:, :, 0] if one else y
+
+    def rnnClearPreviousState(self):
+        KVCacheState.rnnClearPreviousState(self)
+        self.memoryClear()
+
+    def rnnGetPreviousState(self):
+        return dict(KVCacheState.rnnGetPreviousState(self), **self.memoryGet())
+
+    def rnnSetPreviousState(self, state):
+        KVCacheState.rnnSetPreviousState(self, state)
+        self.memorySet(state)
 
 
 class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):

@@ -34,6 +34,12 @@ class MultiLayerNetwork(BaseNetwork):
             return
         parameters = parameters if parameters is not None else self._init_params
         validate_network_conf(self.conf.confs)
+        for i, c in enumerate(self.conf.confs):
+            if getattr(c, "N_INPUTS", 1) != 1:         # a hand-built configuration; ListBuilder.build refuses it too
+                from ..exceptions import DL4JInvalidConfigException
+                raise DL4JInvalidConfigException(
+                    f"Invalid configuration: layer {i} ({type(c).__name__}) takes {c.N_INPUTS} inputs and cannot be "
+                    "part of a MultiLayerNetwork; use a ComputationGraph")
         self.layers = [c.instantiate(index=i, net=self) for i, c in enumerate(self.conf.confs)]
         self._setup_flat([(i, self.conf.confs[i].layerName, l) for i, l in enumerate(self.layers)], parameters,
                          cloneParametersArray, device)
