@@ -355,7 +355,16 @@ class SimpleCNN(ZooModel):
 
 # ---------------------------------------------------------------------------------- TextGenerationLSTM
 class TextGenerationLSTM(ZooModel):
+    """Character-level LSTM language model. Input = one-hot characters [mb, nChars, T]; output = next-character
+    distribution [mb, numLabels, T]. ``TextGenerationLSTM.generate(net, prompt, ...)`` generates from a prompt of
+    character ids (greedy, sampling or beam search; the one-hot inputs are built on the device)."""
     DEFAULT_SHAPE = [1, 77]   # [mb-agnostic, totalUniqueCharacters]
+
+    @staticmethod
+    def generate(net, prompt, **cfg):
+        """``net.generate`` for this model: ``prompt`` [mb, Tp] character ids, fed one-hot; ``cfg``: GenerationConfig
+        fields (maxNewTokens, doSample, temperature, topK, topP, numBeams, eosToken, seed, ...)."""
+        return net.generate(prompt, inputEncoding="onehot", **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, tbptt=50, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
@@ -944,10 +953,19 @@ class TextGenerationTransformer(ZooModel):
     zoo): BertEmbeddingLayer -> N causal TransformerEncoderLayer -> RnnOutputLayer (softmax, MCXENT). Input = token
     ids [mb, T]; output = next-token distribution [mb, numLabels, T]. ``numLabels`` is the vocabulary size.
 
-    Generation goes through ``rnnTimeStep`` as for the LSTM model: after ``rnnClearPreviousState()`` feed the prompt
-    and then one token at a time; every block keeps a key/value cache, so a step costs one pass over the cache
-    instead of recomputing the prefix."""
+    Generation: ``TextGenerationTransformer.generate(net, prompt, maxNewTokens=..., ...)`` (``net.generate``): greedy,
+    temperature / top-k / top-p sampling or beam search, with the token choice, the beam selection and the cache
+    reordering on the device (csrc/generation.hip). It goes through ``rnnTimeStep``: the prompt in one call, then one
+    token per call; every block keeps a key/value cache, so a step costs one pass over the cache instead of
+    recomputing the prefix. The loop can also be written by hand on ``rnnTimeStep`` as for the LSTM model."""
     DEFAULT_SHAPE = [128]
+
+    @staticmethod
+    def generate(net, prompt, **cfg):
+        """``net.generate`` for this model: ``prompt`` [mb, Tp] token ids of one common length; ``cfg``:
+        GenerationConfig fields (maxNewTokens, doSample, temperature, topK, topP, numBeams, eosToken, seed, ...).
+        -> GenerationResult(tokens, lengths, scores)."""
+        return net.generate(prompt, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
                  maxPositions=512, learningRate=1e-3, **kw):
@@ -993,10 +1011,20 @@ class TransformerSeq2Seq(ZooModel):
     in as the first feature mask (``fit(..., featureMaskArrays=[srcMask, None])``): it masks the encoder's keys and is
     the key-padding mask of every decoder block's cross-attention.
 
-    Generation: ``rnnClearPreviousState()``, ``rnnTimeStep(source, firstTargetTokens, masks=[srcMask, None])`` and
-    then ``rnnTimeStep(None, nextToken)`` per token: the encoder runs once, every decoder block keeps the memory's
-    key/value projection and its own self-attention cache."""
+    Generation: ``TransformerSeq2Seq.generate(net, source, start, sourceMask=None, maxNewTokens=..., ...)``: greedy,
+    sampling or beam search on the device (``net.generate``). Underneath: ``rnnClearPreviousState()``,
+    ``rnnTimeStep(source, firstTargetTokens, masks=[srcMask, None])`` and then ``rnnTimeStep(None, nextToken)`` per
+    token: the encoder runs once (for beam search once per example, not per beam), every decoder block keeps the
+    memory's key/value projection and its own self-attention cache."""
     DEFAULT_SHAPE = [128, 128]
+
+    @staticmethod
+    def generate(net, source, start, sourceMask=None, **cfg):
+        """``net.generate`` for this model: ``source`` [mb, Ts] ids, ``start`` [mb, Tp] the first target tokens (e.g.
+        one begin-of-sequence id per row), ``sourceMask`` [mb, Ts] the source padding; ``cfg``: GenerationConfig
+        fields. -> GenerationResult(tokens, lengths, scores)."""
+        masks = None if sourceMask is None else [sourceMask, None]
+        return net.generate(start, others={"source": source}, masks=masks, tokenInput="target", **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, sourceVocabSize=None, hidden=256, layers=4, heads=4,
                  ffn=None, maxPositions=512, learningRate=1e-3, hiddenDropout=0.0, attentionDropout=0.0, **kw):

@@ -705,6 +705,10 @@ class ComputationGraph(BaseNetwork):
         run, and a two-input layer whose memory is ``None`` uses the memory projection it stored. ``masks``: optional
         feature masks, one per network input (``None`` entries allowed), e.g. the source padding of the first call;
         a mask follows its activation as in ``feedForward`` and reaches a two-input layer as its key-padding mask."""
+        return [None if t is None else _out_dtype(t) for t in self._rnn_time_step_raw(*inputs, masks=masks)]
+
+    def _rnn_time_step_raw(self, *inputs, masks=None):
+        """rnnTimeStep with the outputs left in the compute dtype (what generate() reads: no fp32 copy per step)."""
         given = [i for i, x in enumerate(inputs) if x is not None]
         if not given:
             raise DL4JInvalidInputException("rnnTimeStep needs at least one input that is not None")
@@ -757,12 +761,29 @@ class ComputationGraph(BaseNetwork):
                     acts[name], _ = v.forward(ins, False, ms if has_mask else None)
                     if has_mask:
                         mm[name] = v.feedForwardMask(ms)
-        return [None if acts[o] is None else _out_dtype(acts[o]) for o in self.outputs]
+        return [acts[o] for o in self.outputs]
 
     def rnnClearPreviousState(self):
         for l in self.layers_by_name.values():
             if hasattr(l, "rnnClearPreviousState"):
                 l.rnnClearPreviousState()
+
+    def rnnReorderState(self, parents, groupSize=None):
+        """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32
+        [mbNew] on the network's device; mbNew may differ from the stored minibatch size). ``groupSize``: the caller
+        promises parents[i] // groupSize == i // groupSize, so state that is equal within a group (the memory
+        projection of a two-input layer) does not move."""
+        parents = torch.as_tensor(parents, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        for l in self.layers_by_name.values():
+            if hasattr(l, "rnnReorderState"):
+                l.rnnReorderState(parents, groupSize)
+
+    def generate(self, prompt, config=None, others=None, masks=None, **configFields):
+        """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py); ``others``
+        maps the remaining network inputs to their arrays for the first call, ``masks`` as in rnnTimeStep.
+        -> GenerationResult(tokens [mb, maxNewTokens], lengths [mb], scores [mb])."""
+        from ..generation import generate
+        return generate(self, prompt, config, others, masks, **configFields)
 
     def rnnGetPreviousState(self, layerName):
         """Stored rnnTimeStep state of one recurrent layer (reference ComputationGraph.rnnGetPreviousState,

@@ -226,6 +226,9 @@ class CrossAttentionLayerImpl(MemoryKVState, LayerImpl):
     def rnnClearPreviousState(self):
         self.memoryClear()
 
+    def rnnReorderState(self, parents, groupSize=None):
+        self.memoryReorder(parents, groupSize)
+
     def rnnGetPreviousState(self):
         return self.memoryGet()
 

@@ -91,5 +91,9 @@ class MaskZeroLayerImpl(LayerImpl):
         if hasattr(self.inner, "rnnClearPreviousState"):
             self.inner.rnnClearPreviousState()
 
+    def rnnReorderState(self, parents, groupSize=None):
+        if hasattr(self.inner, "rnnReorderState"):
+            self.inner.rnnReorderState(parents, groupSize)
+
 
 _ = torch

@@ -272,6 +272,12 @@ class BaseRecurrentImpl(LayerImpl):
                 f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): minibatch size {x.shape[0]} differs "
                 f"from the stored state's {h.shape[0]}; call rnnClearPreviousState() before changing it")
 
+    def rnnReorderState(self, parents, groupSize=None):
+        """Row i of every stored step-state tensor becomes the old row ``parents[i]`` (index_select)."""
+        idx = parents.to(torch.int64)
+        self.stateMap = {k: (v.index_select(0, idx.to(v.device)) if torch.is_tensor(v) else v)
+                         for k, v in self.stateMap.items()}
+
     def rnnGetPreviousState(self):
         return dict(self.stateMap)
 
@@ -588,6 +594,11 @@ class BidirectionalImpl(BaseRecurrentImpl):
         self.fwd.rnnClearPreviousState() if hasattr(self.fwd, "rnnClearPreviousState") else None
         self.bwd.rnnClearPreviousState() if hasattr(self.bwd, "rnnClearPreviousState") else None
 
+    def rnnReorderState(self, parents, groupSize=None):
+        for inner in (self.fwd, self.bwd):
+            if hasattr(inner, "rnnReorderState"):
+                inner.rnnReorderState(parents, groupSize)
+
 
 class LastTimeStepImpl(LayerImpl):
     def __init__(self, conf, index=0, net=None):
@@ -628,3 +639,7 @@ class LastTimeStepImpl(LayerImpl):
     def rnnClearPreviousState(self):
         if hasattr(self.inner, "rnnClearPreviousState"):
             self.inner.rnnClearPreviousState()
+
+    def rnnReorderState(self, parents, groupSize=None):
+        if hasattr(self.inner, "rnnReorderState"):
+            self.inner.rnnReorderState(parents, groupSize)

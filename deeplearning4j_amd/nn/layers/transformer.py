@@ -244,10 +244,27 @@ class KVCacheState:
     state handed out / taken in is ``{"kv": [mb, L, 2E]}`` trimmed to the valid length."""
     _kv = None
     _kv_len = 0
+    _kv_alt = None      # rnnReorderState's second buffer (same shape as _kv, or None): the two are swapped per call
 
     def rnnClearPreviousState(self):
-        self._kv = None
+        self._kv = self._kv_alt = None
         self._kv_len = 0
+
+    def rnnReorderState(self, parents, groupSize=None):
+        """Row i of the cache becomes the old row ``parents[i]`` (int32 device tensor [mbNew]; mbNew may differ from
+        the stored minibatch size). The valid rows are gathered into a second buffer of the same capacity
+        (csrc/generation.hip; never in place) and the two swap, so a steady-state call allocates nothing."""
+        kv = self._kv
+        if kv is None:
+            return
+        from ...ops import generation_native as GN
+        shape = (int(parents.numel()), kv.shape[1], kv.shape[2])
+        alt = self._kv_alt
+        if alt is None or tuple(alt.shape) != shape or alt.dtype != kv.dtype or alt.device != kv.device:
+            alt = torch.empty(shape, dtype=kv.dtype, device=kv.device)
+        GN.cache_gather(kv, alt, parents, self._kv_len)
+        self._kv_alt = kv if tuple(kv.shape) == shape else None
+        self._kv = alt
 
     def rnnGetPreviousState(self):
         if self._kv is None:
@@ -285,6 +302,7 @@ class KVCacheState:
         if kv is not None and self._kv_len:
             new[:, :self._kv_len] = kv[:, :self._kv_len].to(dtype)
         self._kv = new
+        self._kv_alt = None         # the second buffer follows the new capacity at the next rnnReorderState
 
     def cachedAttention(self, qkv, H, what="rnnTimeStep"):
         """Causal attention of the chunk qkv [mb, Tn, 3E] over everything seen since rnnClearPreviousState(): its K / V
@@ -478,6 +496,20 @@ class MemoryKVState:
         m = state.get("mem_mask")
         self._mem_mask = None if m is None else _memory_mask(m, kv.shape[0], kv.shape[1]).clone()
 
+    def memoryReorder(self, parents, groupSize=None):
+        """Row i of the stored projection and mask becomes the old row ``parents[i]``. With ``groupSize`` the caller
+        promises parents[i] // groupSize == i // groupSize over an unchanged number of rows: the rows of a group
+        hold the same memory, so nothing moves."""
+        kv = self._mem_kv
+        if kv is None or (groupSize is not None and kv.shape[0] == parents.numel()):
+            return
+        from ...ops import generation_native as GN
+        kv = kv.contiguous()
+        new = torch.empty((int(parents.numel()),) + tuple(kv.shape[1:]), dtype=kv.dtype, device=kv.device)
+        self._mem_kv = GN.cache_gather(kv, new, parents, kv.shape[1])
+        if self._mem_mask is not None:
+            self._mem_mask = self._mem_mask.index_select(0, parents.to(torch.int64)).contiguous()
+
     def memoryProject(self, x, memory, memoryMask, wkey, bkey):
         """The stored projection for a step on x [mb, E, Tn]: projected now when ``memory`` [mb, M, Tk] is given
         (one GEMM straight into the kv layout), else the one kept from an earlier call. -> (kv, Tk, mask)."""
@@ -634,6 +666,10 @@ class TransformerDecoderLayerImpl(MemoryKVState, KVCacheState, DropoutSites, Lay
         KVCacheState.rnnClearPreviousState(self)
         self.memoryClear()
 
+    def rnnReorderState(self, parents, groupSize=None):
+        KVCacheState.rnnReorderState(self, parents, groupSize)
+        self.memoryReorder(parents, groupSize)
+
     def rnnGetPreviousState(self):
         return dict(KVCacheState.rnnGetPreviousState(self), **self.memoryGet())
 
@@ -717,6 +753,10 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
 
     def rnnClearPreviousState(self):
         self._seen = None
+
+    def rnnReorderState(self, parents, groupSize=None):
+        if self._seen is not None:
+            self._seen = (self._seen[0], int(parents.numel()))
 
     def rnnGetPreviousState(self):
         return {} if self._seen is None else {"pos": self._seen[0], "mb": self._seen[1]}

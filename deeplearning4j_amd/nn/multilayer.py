@@ -433,6 +433,11 @@ class MultiLayerNetwork(BaseNetwork):
 
     # ------------------------------------------------------------------------------ rnn
     def rnnTimeStep(self, x):
+        x = self._rnn_time_step_raw(x)
+        return x.float() if x.dtype in (torch.bfloat16, torch.float16) else x
+
+    def _rnn_time_step_raw(self, x):
+        """rnnTimeStep with the output left in the compute dtype (what generate() reads: no fp32 copy per step)."""
         x = self._to_dev(x, self._feat_dtype())
         mb = x.shape[0]
         with torch.no_grad():
@@ -443,12 +448,27 @@ class MultiLayerNetwork(BaseNetwork):
                     x = layer.rnnTimeStep(x)
                 else:
                     x = layer.activate(x, False)
-        return x.float() if x.dtype in (torch.bfloat16, torch.float16) else x
+        return x
 
     def rnnClearPreviousState(self):
         for l in self.layers:
             if hasattr(l, "rnnClearPreviousState"):
                 l.rnnClearPreviousState()
+
+    def rnnReorderState(self, parents, groupSize=None):
+        """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32
+        [mbNew] on the network's device; mbNew may differ from the stored minibatch size). ``groupSize``: the caller
+        promises parents[i] // groupSize == i // groupSize, so state that is equal within a group does not move."""
+        parents = torch.as_tensor(parents, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        for l in self.layers:
+            if hasattr(l, "rnnReorderState"):
+                l.rnnReorderState(parents, groupSize)
+
+    def generate(self, prompt, config=None, others=None, masks=None, **configFields):
+        """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py).
+        -> GenerationResult(tokens [mb, maxNewTokens], lengths [mb], scores [mb])."""
+        from .generation import generate
+        return generate(self, prompt, config, others, masks, **configFields)
 
     def rnnGetPreviousState(self, layer):
         return self.layers[layer].rnnGetPreviousState()

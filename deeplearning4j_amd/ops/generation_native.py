@@ -1,0 +1,310 @@
+"""Token generation ops: the ctypes wrappers of csrc/generation.hip (row sampler, beam-search step, key/value-cache
+row gather), a torch implementation of each with the same semantics for tensors the kernels do not take (CPU, fp64;
+counted through ``ops.fallback`` on a GPU), and the host oracles the tests compare both against.
+
+The semantics (weights, top-k / top-p thresholds with ties kept, the Philox draw, the beam total order) are written
+out at the top of csrc/generation.hip."""
+import torch
+
+from . import fallback, native
+from .dispatch import use_native
+from .native import _check, _ptr, _stream
+from .transformer_native import philox4x32_10
+
+PHILOX_TAG = 0x47454E53
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_NEG_INF = float("-inf")
+
+
+def _kernel_ok(p):
+    return use_native(p, "generation") and p.dtype in _DT and p.dim() == 2 and p.is_contiguous() and \
+        p.numel() < 2 ** 31
+
+
+# ------------------------------------------------------------------------------------------------ oracles (host)
+def sample_uniform(seed, offset, rows):
+    """The sampler's uniforms for rows 0 .. rows-1 at counter value ``offset``: fp32 [rows] in [0, 1), 24 bits of
+    word 0 of philox4x32_10({row, 0, PHILOX_TAG, offset mod 2^32}, {seed low, seed high})."""
+    key = (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+    off = int(offset) & 0xFFFFFFFF
+    return torch.tensor([(philox4x32_10((r, 0, PHILOX_TAG, off), key)[0] >> 8) / 16777216.0 for r in range(int(rows))],
+                        dtype=torch.float32)
+
+
+def sample_kept_set(p, temperature=1.0, topK=0, topP=1.0):
+    """fp64 oracle of the sampler's kept set for probabilities p [R, V] (any float dtype; the values as stored).
+    -> (keep bool [R, V], w fp64 [R, V] weights relative to the row maximum, margin fp64 [R]): ``margin`` is the
+    distance of topP * M from the nearest achievable kept mass (inf when top-p is off) — a row whose margin is small
+    against its kept mass sits on a top-p boundary that fp32 sums may resolve either way."""
+    x = torch.nan_to_num(p.detach().cpu().to(torch.float64), nan=0.0).clamp_min(0.0)
+    R, V = x.shape
+    mx = x.max(dim=1, keepdim=True).values
+    w = torch.where(x > 0, torch.exp((torch.log(x) - torch.log(mx)) / float(temperature)), torch.zeros_like(x))
+    w = torch.nan_to_num(w, nan=0.0)
+    keep = torch.ones(R, V, dtype=torch.bool)
+    k = int(topK)
+    if 1 <= k < V:
+        kth = torch.topk(x, k, dim=1).values[:, -1:]
+        keep &= x >= kth
+    margin = torch.full((R,), float("inf"), dtype=torch.float64)
+    if float(topP) < 1.0:
+        for r in range(R):
+            xs, order = torch.sort(torch.where(keep[r], x[r], torch.full_like(x[r], -1.0)), descending=True)
+            ws = torch.where(xs >= 0, w[r][order], torch.zeros_like(xs))
+            c = torch.cumsum(ws, 0)
+            target = float(topP) * float(c[-1])
+            last = torch.ones(V, dtype=torch.bool)               # last position of each run of equal values
+            last[:-1] = xs[:-1] != xs[1:]
+            valid = last & (xs >= 0)
+            masses = c[valid]
+            j = int(torch.nonzero(masses >= target)[0]) if bool((masses >= target).any()) else masses.numel() - 1
+            t = xs[valid][j]
+            keep[r] &= x[r] >= t
+            margin[r] = (masses - target).abs().min()
+    return keep, w, margin
+
+
+def beam_step_reference(p, score, finished, length, eosToken=-1, padToken=0):
+    """fp64 oracle of one beam-search step. p [B*W, V], score [B, W], finished [B, W], length [B, W].
+    -> (parent int32 [B, W] as global rows, token int64 [B, W], score fp64 [B, W], finished uint8 [B, W],
+    length int32 [B, W]), best first under (score descending, flat index w*V + v ascending)."""
+    import numpy as np
+    B, W = score.shape
+    V = p.shape[1]
+    x = torch.nan_to_num(p.detach().cpu().to(torch.float64), nan=0.0).clamp_min(0.0).reshape(B, W, V).numpy()
+    sc = score.detach().cpu().to(torch.float64).numpy()
+    fin = finished.detach().cpu().numpy().astype(bool)
+    ln = length.detach().cpu().numpy()
+    eos = -1 if eosToken is None else int(eosToken)
+    out = [np.zeros((B, W), dt) for dt in (np.int32, np.int64, np.float64, np.uint8, np.int32)]
+    for b in range(B):
+        cs, ci = [], []
+        for w in range(W):
+            if fin[b, w]:
+                cs.append(np.array([sc[b, w]]))
+                ci.append(np.array([w * V + min(max(int(padToken), 0), V - 1)]))
+            else:
+                with np.errstate(divide="ignore"):
+                    cs.append(sc[b, w] + np.log(x[b, w]))
+                ci.append(w * V + np.arange(V))
+        cs, ci = np.concatenate(cs), np.concatenate(ci)
+        order = np.lexsort((ci, -cs))[:W]
+        for j, o in enumerate(order):
+            w, v = divmod(int(ci[o]), V)
+            t = int(padToken) if fin[b, w] else v
+            out[0][b, j] = b * W + w
+            out[1][b, j] = t
+            out[2][b, j] = cs[o]
+            out[3][b, j] = 1 if (fin[b, w] or (eos >= 0 and t == eos)) else 0
+            out[4][b, j] = ln[b, w] + (0 if fin[b, w] else 1)
+    return tuple(torch.from_numpy(a) for a in out)
+
+
+# ------------------------------------------------------------------------------------------------ torch paths
+def _count(finished, count):
+    if count is not None:
+        count.copy_((finished == 0).sum().to(count.dtype).reshape(count.shape))
+
+
+def sample_rows_torch(p, temperature=1.0, topK=0, topP=1.0, greedy=False, rng=None, finished=None, eosToken=-1,
+                      padToken=0, count=None, advance=False):
+    """Torch implementation of the row sampler (sums in fp64). Reads the counter of ``rng`` on the host."""
+    R, V = p.shape
+    x = torch.nan_to_num(p.float(), nan=0.0).clamp_min(0.0)
+    rows = torch.arange(R, device=p.device)
+    if greedy:
+        tok = torch.argmax(x, dim=1)
+        u = torch.zeros(R, dtype=torch.float32, device=p.device)
+    else:
+        mx = x.max(dim=1, keepdim=True).values
+        w = torch.where(x > 0, torch.exp2((torch.log2(x) - torch.log2(mx)) / float(temperature)), torch.zeros_like(x))
+        w = torch.nan_to_num(w, nan=0.0).double()
+        keep = torch.ones_like(x, dtype=torch.bool)
+        k = int(topK)
+        if 1 <= k < V:
+            keep &= x >= torch.topk(x, k, dim=1).values[:, -1:]
+        if float(topP) < 1.0:
+            xs, order = torch.sort(torch.where(keep, x, torch.full_like(x, -1.0)), dim=1, descending=True, stable=True)
+            c = torch.cumsum(torch.where(xs >= 0, torch.gather(w, 1, order), torch.zeros_like(w)), 1)
+            hit = (c >= float(topP) * c[:, -1:]) & (xs >= 0)
+            j = torch.where(hit.any(1), hit.int().argmax(1), (xs >= 0).sum(1) - 1)
+            keep &= x >= torch.gather(xs, 1, j.reshape(R, 1))
+        wk = torch.where(keep, w, torch.zeros_like(w))
+        cdf = torch.cumsum(wk, 1)
+        u = sample_uniform(rng.seed, int(rng.offset.item()), R).to(p.device)
+        target = u.double().reshape(R, 1) * cdf[:, -1:]
+        pos = wk > 0
+        hit = (cdf > target) & pos
+        lastpos = (V - 1) - pos.flip(1).int().argmax(1)
+        tok = torch.where(hit.any(1), hit.int().argmax(1), lastpos)
+        dead = ~pos.any(1)                                       # an all-zero row: its argmax (index 0)
+        tok = torch.where(dead, torch.zeros_like(tok), tok)
+        u = torch.where(dead, torch.zeros_like(u), u)
+        if advance:
+            rng.advance()
+    logp = torch.log(x[rows, tok])
+    if finished is not None:
+        done = finished != 0
+        tok = torch.where(done, torch.full_like(tok, int(padToken)), tok)
+        logp = torch.where(done, torch.zeros_like(logp), logp)
+        u = torch.where(done, torch.zeros_like(u), u)
+        if eosToken is not None and int(eosToken) >= 0:
+            finished |= (tok == int(eosToken)).to(finished.dtype) & (~done).to(finished.dtype)
+        _count(finished, count)
+    return tok.to(torch.int64), logp.float(), u
+
+
+def beam_step_torch(p, score, finished, length, eosToken=-1, padToken=0, count=None):
+    """Torch implementation of the beam step; updates score / finished / length in place like the kernel.
+    -> (parent int32 [B, W], token int64 [B, W])."""
+    B, W = score.shape
+    V = p.shape[1]
+    x = torch.nan_to_num(p.float(), nan=0.0).clamp_min(0.0).reshape(B, W, V)
+    fin = (finished != 0).reshape(B, W, 1)
+    pad = min(max(int(padToken), 0), V - 1)
+    cols = torch.arange(V, device=p.device).reshape(1, 1, V)
+    cand = torch.where(fin, score.reshape(B, W, 1).expand(B, W, V), score.reshape(B, W, 1) + torch.log(x))
+    valid = (~fin) | (cols == pad)
+    cand = torch.where(valid, cand, torch.full_like(cand, _NEG_INF)).reshape(B, W * V)
+    s1, o1 = torch.sort(cand, dim=1, descending=True, stable=True)
+    v1 = torch.gather(valid.reshape(B, W * V), 1, o1)
+    _, o2 = torch.sort((~v1).to(torch.int8), dim=1, stable=True)          # real candidates first, order kept
+    top = o2[:, :W]
+    idx = torch.gather(o1, 1, top)
+    news = torch.gather(s1, 1, top)
+    w = idx // V
+    v = idx - w * V
+    pf = torch.gather(finished.reshape(B, W) != 0, 1, w)
+    tok = torch.where(pf, torch.full_like(v, int(padToken)), v)
+    newf = pf | ((tok == int(eosToken)) if eosToken is not None and int(eosToken) >= 0 else torch.zeros_like(pf))
+    newl = torch.gather(length.reshape(B, W), 1, w) + (~pf).to(length.dtype)
+    parent = (torch.arange(B, device=p.device).reshape(B, 1) * W + w).to(torch.int32)
+    score.copy_(news)
+    finished.copy_(newf.to(finished.dtype))
+    length.copy_(newl)
+    _count(finished, count)
+    return parent, tok.to(torch.int64)
+
+
+def cache_gather_torch(src, dst, parent, L):
+    """dst[i, :L] = src[parent[i], :L] by index_select."""
+    dst[:, :L] = src.index_select(0, parent.to(torch.int64))[:, :L]
+    return dst
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+def sample_rows_native(p, temperature=1.0, topK=0, topP=1.0, greedy=False, rng=None, finished=None, eosToken=-1,
+                       padToken=0, count=None, want_u=False, out=None, advance=False):
+    """Row sampler on csrc/generation.hip; None when the kernel refuses. ``out``: optional (tok, logp) to write."""
+    R, V = p.shape
+    if out is None:
+        tok = torch.empty(R, dtype=torch.int64, device=p.device)
+        logp = torch.empty(R, dtype=torch.float32, device=p.device)
+    else:
+        tok, logp = out
+    u = torch.empty(R, dtype=torch.float32, device=p.device) if want_u else None
+    rc = native.load().dl4j_gen_sample_dt(
+        _DT[p.dtype], _ptr(p), R, V, float(temperature), int(topK), float(topP), int(bool(greedy)),
+        0 if rng is None else rng.seed, None if rng is None else _ptr(rng.offset), int(bool(advance)), _ptr(tok),
+        _ptr(logp), _ptr(u),
+        _ptr(finished), -1 if eosToken is None else int(eosToken), int(padToken), _ptr(count), _stream())
+    if rc == -1:
+        return None
+    _check(rc, "gen_sample")
+    return tok, logp, u
+
+
+def beam_step_native(p, score, finished, length, eosToken=-1, padToken=0, count=None, out=None):
+    """Beam step on csrc/generation.hip; None when the kernel refuses. ``out``: optional (parent, token)."""
+    B, W = score.shape
+    if out is None:
+        parent = torch.empty(B, W, dtype=torch.int32, device=p.device)
+        token = torch.empty(B, W, dtype=torch.int64, device=p.device)
+    else:
+        parent, token = out
+    rc = native.load().dl4j_gen_beam_step_dt(
+        _DT[p.dtype], _ptr(p), B, W, p.shape[1], _ptr(score), _ptr(finished), _ptr(length), _ptr(parent), _ptr(token),
+        -1 if eosToken is None else int(eosToken), int(padToken), _ptr(count), _stream())
+    if rc == -1:
+        return None
+    _check(rc, "gen_beam_step")
+    return parent, token
+
+
+def cache_gather_native(src, dst, parent, L):
+    """dst[i, :L] = src[parent[i], :L] on csrc/generation.hip (src [mbS, TcapS, C], dst [mbD, TcapD, C], parent int32
+    [mbD] on the device). -> dst, or None (nothing written) when the kernel refuses: not contiguous, not 16-byte
+    aligned, a row that is no multiple of 16 bytes, src and dst the same buffer."""
+    if not (src.is_cuda and dst.is_cuda and parent.is_cuda and src.dim() == 3 and dst.dim() == 3 and
+            src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous() and
+            parent.dtype == torch.int32 and parent.is_contiguous() and parent.numel() == dst.shape[0] and
+            src.shape[2] == dst.shape[2] and src.element_size() in (2, 4)):
+        return None
+    rc = native.load().dl4j_gen_cache_gather(_ptr(src), _ptr(dst), _ptr(parent), src.shape[0], dst.shape[0],
+                                             src.shape[1], dst.shape[1], int(L), src.shape[2], src.element_size(),
+                                             _stream())
+    if rc == -1:
+        return None
+    _check(rc, "gen_cache_gather")
+    return dst
+
+
+# ------------------------------------------------------------------------------------------------ dispatch
+def sample_rows(p, temperature=1.0, topK=0, topP=1.0, greedy=False, rng=None, finished=None, eosToken=-1,
+                padToken=0, count=None, out=None, advance=False):
+    """One token per row of the probabilities p [R, V] -> (tok int64 [R], logp fp32 [R]). ``finished`` (uint8 [R]) is
+    updated in place and ``count`` (int32 [1]) receives the number of unfinished rows; ``advance`` bumps the counter
+    of ``rng`` after the draw (on the device)."""
+    if _kernel_ok(p):
+        r = sample_rows_native(p, temperature, topK, topP, greedy, rng, finished, eosToken, padToken, count, out=out,
+                               advance=advance)
+        if r is not None:
+            return r[0], r[1]
+    fallback.note(p, "generation", f"sampler on {p.dtype}: torch path")
+    tok, logp, _ = sample_rows_torch(p, temperature, topK, topP, greedy, rng, finished, eosToken, padToken, count,
+                                     advance)
+    if out is not None:
+        out[0].copy_(tok)
+        out[1].copy_(logp)
+        return out
+    return tok, logp
+
+
+def beam_step(p, score, finished, length, eosToken=-1, padToken=0, count=None, out=None):
+    """One beam-search step -> (parent int32 [B, W], token int64 [B, W]); score / finished / length in place."""
+    if _kernel_ok(p) and 1 <= score.shape[1] <= 16:
+        r = beam_step_native(p, score, finished, length, eosToken, padToken, count, out=out)
+        if r is not None:
+            return r
+    fallback.note(p, "generation", f"beam step on {p.dtype}: torch path")
+    return beam_step_torch(p, score, finished, length, eosToken, padToken, count)
+
+
+def cache_gather(src, dst, parent, L):
+    """dst[i, :L] = src[parent[i], :L]; the kernel where it takes the operands, else index_select."""
+    if use_native(src, "generation") and cache_gather_native(src, dst, parent, L) is not None:
+        return dst
+    fallback.note(src, "generation", f"cache gather on {src.dtype} {tuple(src.shape)}: index_select")
+    return cache_gather_torch(src, dst, parent, L)
+
+
+def beam_backtrack(toks, parents, best, W):
+    """The token sequence of each example's chosen beam: toks [N, mb*W] int64 and parents [N, mb*W] int32 as the beam
+    steps wrote them, best [mb] (the final beam per example) -> [mb, N] int64. One kernel launch on the GPU."""
+    N, rows = toks.shape
+    mb = rows // W
+    best = best.to(torch.int64).contiguous()
+    out = torch.empty(mb, N, dtype=torch.int64, device=toks.device)
+    if use_native(toks, "generation") and toks.is_contiguous() and parents.is_contiguous() and \
+            parents.dtype == torch.int32:
+        rc = native.load().dl4j_gen_beam_backtrack(_ptr(toks), _ptr(parents), _ptr(best), _ptr(out), mb, W, N,
+                                                   _stream())
+        if rc != -1:
+            _check(rc, "gen_beam_backtrack")
+            return out
+    fallback.note(toks, "generation", "beam backtrack: torch path")
+    r = torch.arange(mb, device=toks.device) * W + best
+    for t in range(N - 1, -1, -1):
+        out[:, t] = toks[t][r]
+        r = parents[t][r].to(torch.int64)
+    return out
