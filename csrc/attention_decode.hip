@@ -9,17 +9,18 @@
 //  * attn_kv_append_kernel copies the K and V column blocks of qkv[B, Tn, 3E] to rows [pos, pos + Tn) of the cache
 //    (16-byte vectors).
 //  * attn_decode_kernel: queries are the Q columns of qkv[B, Tn, 3E], keys / values rows [0, pos + Tn) of the cache
-//    (the new rows already appended); query i sees keys <= pos + i. Same wave mapping as attn_fwd_kernel: a wave owns
-//    16 queries with transposed scores Sᵀ = K·Qᵀ (v_mfma_f32_16x16x32), exp2-domain online softmax with one (m, l)
-//    per lane, Pᵀ fed from registers into Oᵀ += Vᵀ·Pᵀ. The block stages each 64-key block cooperatively (K row-major,
-//    V transposed), with the next block's global loads in flight during the current block's MFMAs. Waves whose 16
-//    queries all lie beyond Tn only stage (at Tn <= 16 that is three of four; the kernel is bound by the cache read).
+//    (the new rows already appended); query i sees keys <= pos + i. The wave mapping and the per-block arithmetic
+//    are the forward ones of csrc/attention_body.h, written out here: built from that header's inner-step helpers the
+//    kernel computes the same bits but measures 1-2 % slower at a 128-key history (profiles/attention_unify.txt).
+//    The block stages each 64-key block cooperatively (K row-major, V transposed), with the next block's global loads
+//    in flight during the current block's MFMAs. Waves whose 16 queries all lie beyond Tn only stage (at Tn <= 16 that is three
+//    of four; the kernel is bound by the cache read).
 //  * The keys are split: grid (splits, B*H, ceil(Tn/64)); split s covers the contiguous 64-key blocks
 //    [s*nkb/S, (s+1)*nkb/S). One split normalises and writes out directly; several write fp32 partials (running max
 //    m in the exp2 domain, sum l, unnormalised accumulator) to a workspace and attn_decode_combine_kernel merges
 //    them in the fixed order s = 0 .. S-1 — no atomics, bitwise reproducible for a given split count. A split that
 //    is causally empty for a query leaves (-inf, 0, 0) and is skipped by the merge.
-#include "attention_mma.h"
+#include "attention_body.h"
 
 // partial workspace for S splits: acc[((bh*Tn + q)*S + s)*D + d] (16-byte aligned rows), then ml[(bh*Tn + q)*S + s][2]
 // holding (m, l)
@@ -220,20 +221,6 @@ static constexpr int kDecodeMaxSplits = 16;
 static int decode_nkb(int L) { return (L + BLK - 1) / BLK; }
 static int decode_clamp_splits(int splits, int L) { return splits < decode_nkb(L) ? splits : decode_nkb(L); }
 
-template <int D, typename hb>
-static int decode_l(const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H, int pos, int Tcap,
-                    int S, float scale, hipStream_t s) {
-  const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
-  hipLaunchKernelGGL((attn_decode_kernel<D, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv, (hb*)out, ws,
-                     Tn, H, pos, Tcap, S, scale * kLog2e);
-  if (S > 1) {
-    const long long n = (long long)B * H * Tn * (D / 4);
-    hipLaunchKernelGGL((attn_decode_combine_kernel<D, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
-                       (hb*)out, (long long)B * H, Tn, H, S);
-  }
-  return (int)hipGetLastError();
-}
-
 static bool decode_shape_ok(int dt, int B, int Tn, int H, int D, int pos, int Tcap) {
   if (B < 1 || Tn < 1 || H < 1 || pos < 0 || Tcap < 1 || (dt != 1 && dt != 2) || (D != 64 && D != 128)) return false;
   if (Tcap % BLK || (long long)pos + Tn > Tcap) return false;
@@ -265,7 +252,7 @@ DL4J_API long long dl4j_attn_decode_ws_bytes(int B, int Tn, int H, int D, int sp
 DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, int Tn, int H, int D, int pos, int Tcap,
                                     hipStream_t s) {
   if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv) return -1;
-  if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(kv)) & 15) return -1;
+  if (!attn_aligned16({qkv, kv})) return -1;
   const int EC = H * D / 8;                                      // 16-byte chunks of E columns
   const long long total = (long long)B * Tn * 2 * EC;
   hipLaunchKernelGGL(attn_kv_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const uint4*)qkv,
@@ -279,13 +266,20 @@ DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, in
 DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
                                  int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
   if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv || !out || splits < 1) return -1;
-  if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(kv) | reinterpret_cast<uintptr_t>(out) |
-       reinterpret_cast<uintptr_t>(ws)) & 15)
-    return -1;
+  if (!attn_aligned16({qkv, kv, out, ws})) return -1;
   const int S = decode_clamp_splits(splits, pos + Tn);
   if (S > 1 && !ws) return -1;
-  if (D == 64) return dt == 1 ? decode_l<64, __bf16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s)
-                              : decode_l<64, _Float16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s);
-  return dt == 1 ? decode_l<128, __bf16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s)
-                 : decode_l<128, _Float16>(qkv, kv, out, ws, B, Tn, H, pos, Tcap, S, scale, s);
+  return attn_dispatch(dt, D, [&](auto d, auto e) {
+    constexpr int DD = decltype(d)::value;
+    using hb = typename decltype(e)::type;
+    const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
+    hipLaunchKernelGGL((attn_decode_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv, (hb*)out,
+                       ws, Tn, H, pos, Tcap, S, scale * kLog2e);
+    if (S > 1) {
+      const long long n = (long long)B * H * Tn * (DD / 4);
+      hipLaunchKernelGGL((attn_decode_combine_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
+                         (hb*)out, (long long)B * H, Tn, H, S);
+    }
+    return (int)hipGetLastError();
+  });
 }

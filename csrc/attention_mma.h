@@ -1,7 +1,6 @@
-// Fragment helpers shared by the attention kernels (csrc/attention.hip, csrc/attention_cross.hip,
-// csrc/attention_decode.hip): the v_mfma_f32_16x16x32_{bf16,f16} wrappers, the LDS / register fragment loads that
-// match its operand layout, the cross-group reductions of the transposed-score online softmax, and the cooperative
-// 64-row block loads into LDS.
+// Fragment helpers of the attention kernel bodies (csrc/attention_body.h): the v_mfma_f32_16x16x32_{bf16,f16}
+// wrappers, the LDS / register fragment loads that match its operand layout, the cross-group reductions of the
+// transposed-score online softmax, and the cooperative 64-row block loads into LDS.
 #pragma once
 #include "common.h"
 

@@ -150,6 +150,26 @@ def test_forward_and_backward_are_bitwise_reproducible():
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("T", [1, 65, 130])                  # one row; one past a block edge; two blocks and a tail
+@pytest.mark.parametrize("B,H,D", [(2, 2, 64), (1, 3, 128)])
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_cross_equals_self_attention_bitwise_at_equal_lengths(B, H, D, T, masked, dt):
+    """The self and the cross kernels run one body (csrc/attention_body.h): at Tq = Tk = T with the same key-padding
+    mask, non-causal and without dropout, they give the same bits on q | kv = qkv."""
+    q, kv, dout = (t.to(DEV) for t in _operands(B, T, T, H, D, dt, seed=4))
+    qkv = torch.cat([q, kv], 2).contiguous()
+    md = _ragged(B, T).to(DEV) if masked else None
+    E = H * D
+    out, lse = TN.cross_attn_fwd(q, kv, H, kmask=md)
+    s_out, s_lse = TN.attn_fwd(qkv, H, mask=md)
+    assert torch.equal(out, s_out) and torch.equal(lse, s_lse)
+    dq, dkv = TN.cross_attn_bwd(q, kv, out, lse, dout, H, kmask=md)
+    dqkv = TN.attn_bwd(qkv, s_out, s_lse, dout, H, mask=md)
+    assert torch.equal(dq, dqkv[..., :E])
+    assert torch.equal(dkv, dqkv[..., E:])
+
+
 # ------------------------------------------------------------------------------------------------ layer / network
 EH, NH, FF, TS, TT, MB, V = 128, 2, 256, 70, 66, 3, 11
 
