@@ -596,35 +596,10 @@ static unsigned* bn_ticket_slot() {
   return base[dev] + 32 * k;
 }
 
-// DL4J_AMD_BN_FOLD=0: the previous separate launches (bn_reduce_rows + bn_finalize / bn_bwd_finalize) for A/B runs.
-static bool bn_fold_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DL4J_AMD_BN_FOLD");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-static inline void bn_reduce_stage(float*& p1, float*& p2, int& nblk, int C, float* q, hipStream_t s);
-
 // Launches bn_fold over `nrows` partial rows; q: >= 2*ceil(nrows/32)*C floats of workspace.
 template <typename T, int SRC, int FIN>
 static int bn_fold_launch(const float* p1, const float* p2, long long nrows, int C, float* q, BnFin f,
                           hipStream_t s) {
-  if (SRC == 0 && !bn_fold_enabled() && nrows <= 0x7fffffff) {
-    float* a = const_cast<float*>(p1);
-    float* b = const_cast<float*>(p2);
-    int n = (int)nrows;
-    bn_reduce_stage(a, b, n, C, q, s);
-    if (FIN == 0)
-      hipLaunchKernelGGL(bn_finalize<T>, dim3((C + 63) / 64), dim3(256), 0, s, a, b, n, C, f.M, (const T*)f.x, f.gamma,
-                         f.beta, f.gconst, f.bconst, f.run_mean, f.run_var, f.decay, f.eps, 1, f.ctx);
-    else
-      hipLaunchKernelGGL(bn_bwd_finalize, dim3((C + 63) / 64), dim3(256), 0, s, a, b, n, C, f.M, f.dbeta, f.dgamma,
-                         f.cdb, f.cdg);
-    return 0;
-  }
   // many partial rows (the conv epilogues' 64-row tile partials): 128 rows per block keeps the reducer's serial pass
   // short (stage-1 ResNet-50 tiles: 6272 partials -> 49 folded rows instead of 196)
   // (bn_bwd_partial's <= 2048 block rows fold faster 32 to a block: measured 0.56 vs 0.66 ms/step)
@@ -869,20 +844,10 @@ static int bn_fwd_tiles_impl(const T* xb, const T* res, T* y, long long M, int C
                              int rpp, const float* gamma, const float* beta, float gconst, float bconst,
                              float* run_mean, float* run_var, float decay, float eps, int relu, float* ws,
                              float* ctx_out, unsigned char* mask, hipStream_t s, const float* rctx = nullptr) {
-  const long long S = (P + 31) / 32;
   BnFin f{M, xb, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out,
           nullptr, nullptr, nullptr, nullptr, nullptr, rpp};
-  int rc;
-  if (bn_fold_enabled()) {
-    // one launch: tile re-centring + fold + finalize
-    rc = bn_fold_launch<T, 1, 0>(tstats, nullptr, P, C, ws, f, s);
-  } else {
-    float* p1 = ws;
-    float* p2 = ws + S * C;
-    hipLaunchKernelGGL(bn_tiles_reduce<T>, dim3((C + 63) / 64, (unsigned)S), dim3(256), 0, s, tstats, P, C, M, xb, p1,
-                       p2, rpp);
-    rc = bn_fold_launch<T, 0, 0>(p1, p2, S, C, p2 + S * C, f, s);
-  }
+  // one launch: tile re-centring + fold + finalize
+  const int rc = bn_fold_launch<T, 1, 0>(tstats, nullptr, P, C, ws, f, s);
   if (rc) return rc;
   if (!y) return (int)hipGetLastError();              // statistics only (a shortcut BN folded into its consumer)
   if (rctx && res)

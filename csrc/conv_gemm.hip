@@ -189,7 +189,6 @@ __global__ __launch_bounds__(WGM* WGN * 64, 2) void conv_glds(GemmArgs g, ConvA 
   static_assert(RPP >= 64 && RPP % 64 == 0, "epilogue pass too small");
   const int h = lane >> 5;
   EpiOut o;
-  o.coh = false;
   o.raw = false;
   o.dt = g.out_dt;
   o.dst = reinterpret_cast<char*>(g.C);
@@ -359,14 +358,6 @@ DL4J_API int dl4j_conv_fwd_v3(int dt, const void* X, const void* Wkrsc, const fl
 // ==================================================================================================================
 namespace {
 
-// division by a runtime-uniform divisor via multiply-high (valid for n < 2^31)
-struct FastDiv {
-  unsigned d, mul, shr;
-};
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d == 1 ? n : (__umulhi(n, f.mul) >> f.shr);
-}
-
 struct WrwGeom {
   const void* X;        // NHWC input
   const void* dY;       // NHWC output gradient
@@ -392,15 +383,6 @@ __device__ __forceinline__ typename MfmaT<DT>::v8 frag_tr_asm(const char* T, int
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=&v"(f.lo) : "v"(a0));
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=&v"(f.hi) : "v"(a1));
   return __builtin_bit_cast(v8, f);
-}
-
-template <int N> __device__ __forceinline__ void wait_lgkm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-  else static_assert(N < 0, "unsupported lgkmcnt");
 }
 
 template <int DT, int BM, int BN, int WGM, int WGN, int STAGES>
@@ -578,7 +560,6 @@ __global__ __launch_bounds__(WGM* WGN * 64, 2) void conv_wrw_glds(GemmArgs g, Wr
   static_assert(RPP >= 32, "epilogue pass too small");
   const int h = lane >> 5;
   EpiOut o;
-  o.coh = false;
   o.raw = true;
   o.dt = 0;
   o.dst = reinterpret_cast<char*>(g.ws + (long long)split * g.M * g.N);
@@ -667,18 +648,6 @@ int launch_wrw(int v, const GemmArgs& g, const WrwGeom& wg, int splits, hipStrea
   return (int)hipGetLastError();
 }
 
-static inline FastDiv make_fd(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d == 1) { f.mul = 0; f.shr = 0; return f; }
-  unsigned l = 0;
-  while ((1u << l) < d) ++l;
-  const unsigned p = 31 + l;
-  f.mul = (unsigned)(((1ull << p) + d - 1) / d);
-  f.shr = p - 32;
-  return f;
-}
-
 // pixel splits: ~2 blocks per CU in total, every split >= 4 K-steps (256 pixels)
 int wrw_splits(long long M, int tiles, int want) {
   int sp = want > 0 ? want : (int)((512 + tiles - 1) / tiles);
@@ -735,7 +704,7 @@ DL4J_API int dl4j_conv_wrw_v3(int dt, const void* X, const void* dY, float* dW, 
   wg.N = N; wg.H = H; wg.W = W; wg.C = C; wg.OH = OH; wg.OW = OW; wg.K = K;
   wg.R = R; wg.S = S; wg.sh = sh; wg.sw = sw; wg.ph = ph; wg.pw = pw; wg.dh = dh; wg.dw = dw;
   wg.M = (int)M; wg.RSC = RSC; wg.mps = mps;
-  wg.fOW = make_fd((unsigned)OW); wg.fOH = make_fd((unsigned)OH);
+  wg.fOW = make_fastdiv((unsigned)OW); wg.fOH = make_fastdiv((unsigned)OH);
   wg.partb = db ? ws + (long long)sp * K * RSC : nullptr;
   int e = dt == 1 ? launch_wrw<1>(variant, g, wg, sp, s) : launch_wrw<2>(variant, g, wg, sp, s);
   if (e) return e;

@@ -43,16 +43,6 @@ struct HaloFwd {
 
 inline int halo_slot_bytes(int hrows) { return ((hrows + 7) / 8) * 1024; }
 
-template <int N> __device__ __forceinline__ void lgkm_wait_h() {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-  __builtin_amdgcn_s_waitcnt((7 << 4) | (N << 8) | 15 | (3 << 14));   // lgkmcnt(N), vmcnt / expcnt: no wait
-}
-
-template <int N> __device__ __forceinline__ void wait_vm_h() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-
 // S ring slots, XI = DMA pieces (8 halo rows) per chunk
 template <int DT, int S, int XI>
 __global__ __launch_bounds__(320, 1) void conv_halo3x3(HaloFwd a) {
@@ -121,12 +111,12 @@ __global__ __launch_bounds__(320, 1) void conv_halo3x3(HaloFwd a) {
     for (int i = 0; i < D; ++i) issue(i);
 #pragma unroll 1
     for (int i = 0; i < nloc; ++i) {
-      wait_vm_h<(D - 1) * XI>();                   // chunk i (and the weights) landed
+      wait_vm_nb<(D - 1) * XI>();                  // chunk i (and the weights) landed
       raw_barrier();                               // B1(i)
       issue(i + D);                                // into the slot chunk i-1 used (read before B1(i))
       raw_barrier();                               // B2(i): the consumers' epilogue image
     }
-    wait_vm_h<0>();
+    wait_vm_nb<0>();
     return;
   }
 
@@ -181,7 +171,7 @@ __global__ __launch_bounds__(320, 1) void conv_halo3x3(HaloFwd a) {
       constexpr int u = decltype(U_)::value;
       if constexpr (u + PD < NU) reads(IC<u + PD>{});
       constexpr int ahead = (u + PD < NU ? PD : NU - 1 - u) * 3;   // reads issued after unit u's
-      lgkm_wait_h<ahead>();
+      wait_lgkm_nb<ahead>();
       __builtin_amdgcn_sched_barrier(0);
       acc[0] = MfmaT<DT>::mma(fb0[u % NB], fa[u % NB], acc[0]);
       acc[1] = MfmaT<DT>::mma(fb1[u % NB], fa[u % NB], acc[1]);

@@ -12,18 +12,22 @@
 //         network's flat fp32 gradient in DL4J's [K][C][R][S] order; conv-bias gradient fused as column sums)
 //
 // GEMM core: 256 threads = 4 waves in a 2x2 arrangement, block tile 128(n) x 128(m) x 32(k), each wave a
-// 64x64 sub-tile = 2x2 v_mfma_f32_32x32x16_bf16 accumulators. Operand tiles are register-staged into a
-// double-buffered LDS ring (global loads for step k+1 are issued before the MFMAs of step k). K-contiguous
-// tiles use an XOR chunk swizzle so every ds_read_b128 lane group hits 16 distinct bank slots; the WRW tiles
-// (m-contiguous) are read with ds_read_b64_tr_b16 (hardware transpose) from rows padded to 320 B, which makes
-// the 4 rows of each half-wave read land on disjoint banks. Block ids are remapped so that consecutive tiles
-// (sharing the weight panel) run on the same XCD (T1).
-#include "common.h"
+// 64x64 sub-tile = 2x2 v_mfma_f32_32x32x16_bf16 accumulators. FWD / BWD-D: operand tiles go global -> LDS with
+// global_load_lds_dwordx4 (no VGPR staging) through a 4-deep ring, waited for with a counted vmcnt and a raw
+// s_barrier (igemm_fwd_glds); the K-contiguous tiles use an XOR chunk swizzle so every ds_read_b128 lane group hits
+// 16 distinct bank slots. WRW: the m-contiguous tiles are register-staged into a double-buffered LDS ring (global
+// loads for step k+1 are issued before the MFMAs of step k) and read with ds_read_b64_tr_b16 (hardware transpose)
+// from rows padded to 320 B, which makes the 4 rows of each half-wave read land on disjoint banks. Block ids are
+// remapped so that consecutive tiles (sharing the weight panel) run on the same XCD (T1). Round 2's register-staged
+// forward kernel and its LDS-DMA weight gradient (measured slower, profiles/r2_wrw_ab_remap_variant.log) are gone.
+#include "mfma_tile.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
+typedef MfmaT<1>::v8 bf16x8_t;
+
+// This file's own zero page, not mfma_tile.h's gemm_zero_page: that one has internal linkage, its address is formed
+// differently, and igemm_fwd_glds then gets another register allocation (same register counts and LDS, 8-32
+// instructions apart). Kept so that the forward kernels' code stays exactly as it was measured.
+__device__ __attribute__((aligned(64))) char g_zero_page[64];
 
 struct ConvGeom {
   int N, H, W, C;       // input image (NHWC)
@@ -36,32 +40,6 @@ struct ConvGeom {
 #define TILE_K 32
 #define NTHREADS 256
 
-// bijective XCD-aware remap of a linear block id (guide §5, "XCD swizzle must be bijective")
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg / 8, r = nwg % 8;
-  const int xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
-
-// Division by a runtime-uniform divisor via multiply-high (CUTLASS-style FastDivmod); valid for n < 2^31.
-struct FastDiv {
-  unsigned d, mul, shr;
-};
-static inline FastDiv make_fastdiv(unsigned d) {
-  FastDiv f;
-  f.d = d;
-  if (d == 1) { f.mul = 0; f.shr = 0; return f; }
-  unsigned l = 0;
-  while ((1u << l) < d) ++l;                       // ceil(log2 d)
-  const unsigned p = 31 + l;
-  f.mul = (unsigned)(((1ull << p) + d - 1) / d);
-  f.shr = p - 32;
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
-  return f.d == 1 ? n : (__umulhi(n, f.mul) >> f.shr);
-}
-
 // byte offset of (row, 16-byte chunk) in a swizzled [rows][4 chunks] K-contiguous tile
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
@@ -71,165 +49,7 @@ __device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chu
 //   scatter > 0: 1x1 bwd-data with stride `scatter`: output pixel m=(n,oh,ow) goes to row (n, oh*s, ow*s) of
 //   an image with dims (g.OH*s', g.OW*s') given by out_H/out_W.
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NTHREADS) void igemm_fwd_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wt,
-                                                              const float* __restrict__ bias, bf16* __restrict__ Y,
-                                                              ConvGeom g, int Kred, int scatter, int out_H, int out_W,
-                                                              int accum, float* __restrict__ tstats) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_N * TILE_K * 2];   // 2 buffers x (A + B) = 32 KB
-  const int M = g.N * g.OH * g.OW;
-  const int Nout = g.K;
-  const int tiles_m = (M + TILE_M - 1) / TILE_M;
-  const int tiles_n = (Nout + TILE_N - 1) / TILE_N;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  // n-major inside an XCD chunk: consecutive blocks share the pixel panel? -> pixel panels are bigger, so
-  // iterate n fastest to reuse the im2col tile from L2 across the Nout tiles.
-  const int tn = bid % tiles_n, tm = bid / tiles_n;
-  if (tm >= tiles_m) return;
-  const int n0 = tn * TILE_N, m0 = tm * TILE_M;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wn = wid >> 1, wm = wid & 1;
-
-  // ---- per-thread load assignment: 2 rows (r0, r0+64) x chunk c of each 128x32 tile
-  const int lrow = tid >> 2, lchunk = tid & 3;
-  // weight rows
-  const bf16* wrow[2];
-  bool wok[2];
-  for (int i = 0; i < 2; ++i) {
-    const int n = n0 + lrow + 64 * i;
-    wok[i] = n < Nout;
-    wrow[i] = Wt + (long long)(wok[i] ? n : 0) * Kred;
-  }
-  // pixel rows: (image n, ih0, iw0)
-  int pn[2], pih[2], piw[2];
-  bool pok[2];
-  for (int i = 0; i < 2; ++i) {
-    const int m = m0 + lrow + 64 * i;
-    pok[i] = m < M;
-    const int mm = pok[i] ? m : 0;
-    const int ow = mm % g.OW, t = mm / g.OW;
-    const int oh = t % g.OH;
-    pn[i] = t / g.OH;
-    pih[i] = oh * g.sh - g.ph;
-    piw[i] = ow * g.sw - g.pw;
-  }
-  // k -> (r, s, c) decomposition of this thread's chunk, advanced by TILE_K every step
-  int kc = lchunk * 8;
-  int cc = kc % g.C, rs = kc / g.C;
-  int rr = rs / g.S, ss = rs % g.S;
-
-  f32x16_t acc[2][2];
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b)
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-
-  uint4 wreg[2], xreg[2];
-  const int nk = (Kred + TILE_K - 1) / TILE_K;
-
-  auto gload = [&](int kt) {
-    const int k = kt * TILE_K + kc;
-    const bool kin = k < Kred;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (wok[i] && kin) wreg[i] = *reinterpret_cast<const uint4*>(wrow[i] + k);
-      else wreg[i] = make_uint4(0, 0, 0, 0);
-      const int ih = pih[i] + rr * g.dh, iw = piw[i] + ss * g.dw;
-      if (pok[i] && kin && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W)
-        xreg[i] = *reinterpret_cast<const uint4*>(X + (((long long)pn[i] * g.H + ih) * g.W + iw) * g.C + cc);
-      else xreg[i] = make_uint4(0, 0, 0, 0);
-    }
-    // advance (r, s, c) by TILE_K for the next step
-    cc += TILE_K;
-    while (cc >= g.C) { cc -= g.C; if (++ss == g.S) { ss = 0; ++rr; } }
-  };
-  auto sstore = [&](int buf) {
-    char* A = smem + buf * (2 * TILE_N * TILE_K * 2);
-    char* B = A + TILE_N * TILE_K * 2;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = lrow + 64 * i;
-      *reinterpret_cast<uint4*>(A + swz(row, lchunk)) = wreg[i];
-      *reinterpret_cast<uint4*>(B + swz(row, lchunk)) = xreg[i];
-    }
-  };
-
-  gload(0);
-  sstore(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) gload(kt + 1);
-    const char* A = smem + buf * (2 * TILE_N * TILE_K * 2);
-    const char* B = A + TILE_N * TILE_K * 2;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int chunk = ks * 2 + (lane >> 5);
-      bf16x8_t af[2], bfr[2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const int row = wn * 64 + a * 32 + (lane & 31);
-        af[a] = *reinterpret_cast<const bf16x8_t*>(A + swz(row, chunk));
-      }
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int row = wm * 64 + b * 32 + (lane & 31);
-        bfr[b] = *reinterpret_cast<const bf16x8_t*>(B + swz(row, chunk));
-      }
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
-    }
-    if (kt + 1 < nk) sstore(buf ^ 1);
-    __syncthreads();
-  }
-
-  // ---- epilogue: D[n][m] -> Y[row(m)][n], 4 consecutive channels per 8-byte store
-  const int hh = lane >> 5;
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int m = m0 + wm * 64 + b * 32 + (lane & 31);
-    if (m >= M) continue;
-    long long orow;
-    if (scatter > 0) {
-      const int ow = m % g.OW, t = m / g.OW;
-      const int oh = t % g.OH, n = t / g.OH;
-      orow = ((long long)n * out_H + oh * scatter) * out_W + ow * scatter;
-    } else {
-      orow = m;
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n = n0 + wn * 64 + a * 32 + 8 * q + 4 * hh;
-        if (n >= Nout) continue;
-        u16 o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v = acc[a][b][4 * q + j];
-          if (bias) v += bias[n + j];
-          o[j] = f2bf(v);
-        }
-        if (accum) {                                    // dX += result (fan-out gradient summed in place)
-          const uint2 old = *reinterpret_cast<const uint2*>(Y + orow * Nout + n);
-          o[0] = f2bf(bf2f(o[0]) + bf2f((u16)(old.x & 0xffff)));
-          o[1] = f2bf(bf2f(o[1]) + bf2f((u16)(old.x >> 16)));
-          o[2] = f2bf(bf2f(o[2]) + bf2f((u16)(old.y & 0xffff)));
-          o[3] = f2bf(bf2f(o[3]) + bf2f((u16)(old.y >> 16)));
-        }
-        uint2 pk;
-        pk.x = (unsigned)o[0] | ((unsigned)o[1] << 16);
-        pk.y = (unsigned)o[2] | ((unsigned)o[3] << 16);
-        *reinterpret_cast<uint2*>(Y + orow * Nout + n) = pk;
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// FWD / BWD-DATA, LDS-DMA pipeline (v2). Same math and output as igemm_fwd_kernel, but operand tiles go
-// global -> LDS with global_load_lds_dwordx4 (no VGPR staging) through a G_STAGES-deep ring, so up to
+// LDS-DMA pipeline: operand tiles go global -> LDS with global_load_lds_dwordx4 (no VGPR staging) through a G_STAGES-deep ring, so up to
 // G_STAGES-1 K-steps of loads are in flight per block. The ResNet convs here have only 2-72 K-steps and
 // 100-800 tiles: per-block load latency, not MFMA issue, sets their time, so the pipeline depth is the lever.
 // LDS image is lane-linear per wave-instruction (16 rows x 64 B); the XOR chunk swizzle is applied on the
@@ -241,25 +61,11 @@ __global__ __launch_bounds__(NTHREADS) void igemm_fwd_kernel(const bf16* __restr
 #define G_STAGES 4
 #define G_STAGE_BYTES (2 * TILE_N * TILE_K * 2)
 
-__device__ __attribute__((aligned(64))) char g_zero_page[64];
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-
 __device__ __forceinline__ void wait_stage(int ahead) {
   // ahead = number of later stages whose 4 DMAs/thread may stay in flight
-  if (ahead >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  if (ahead >= 2) wait_vm<8>();
+  else if (ahead == 1) wait_vm<4>();
+  else wait_vm<0>();
 }
 
 // FAST (C % TILE_K == 0): every K-step stays inside one filter tap (r, s), so the step's source offset is a
@@ -275,7 +81,7 @@ __global__ __launch_bounds__(NTHREADS) void igemm_fwd_glds(const bf16* __restric
   const int Nout = g.K;
   const int tiles_m = (M + TILE_M - 1) / TILE_M;
   const int tiles_n = (Nout + TILE_N - 1) / TILE_N;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = xcd_remap_g(blockIdx.x, gridDim.x);
   const int tn = bid % tiles_n, tm = bid / tiles_n;
   if (tm >= tiles_m) return;
   const int n0 = tn * TILE_N, m0 = tm * TILE_M;
@@ -396,7 +202,7 @@ __global__ __launch_bounds__(NTHREADS) void igemm_fwd_glds(const bf16* __restric
   // stores (each output pixel row of the tile is 256 contiguous bytes in NHWC).
   const int hh = lane >> 5;
   if ((Nout & 7) == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     raw_barrier();                                   // all waves are done reading the operand ring
     char* T = smem;
 #pragma unroll
@@ -536,15 +342,10 @@ __global__ __launch_bounds__(NTHREADS) void igemm_fwd_glds(const bf16* __restric
   }
 }
 
-static int g_fwd_variant = 1;   // 1 = LDS-DMA pipeline (default), 0 = register-staged kernel
-DL4J_API void dl4j_conv_set_variant(int v) { g_fwd_variant = v; }
-
-#define LAUNCH_FWD(fast, grid, ...)                                                                        \
-  do {                                                                                                      \
-    if (g_fwd_variant == 1 && (fast))                                                                       \
-      hipLaunchKernelGGL(igemm_fwd_glds<true>, grid, dim3(NTHREADS), 0, s, __VA_ARGS__);                    \
-    else if (g_fwd_variant == 1) hipLaunchKernelGGL(igemm_fwd_glds<false>, grid, dim3(NTHREADS), 0, s, __VA_ARGS__); \
-    else hipLaunchKernelGGL(igemm_fwd_kernel, grid, dim3(NTHREADS), 0, s, __VA_ARGS__);                    \
+#define LAUNCH_FWD(fast, grid, ...)                                                               \
+  do {                                                                                             \
+    if (fast) hipLaunchKernelGGL(igemm_fwd_glds<true>, grid, dim3(NTHREADS), 0, s, __VA_ARGS__);   \
+    else hipLaunchKernelGGL(igemm_fwd_glds<false>, grid, dim3(NTHREADS), 0, s, __VA_ARGS__);       \
   } while (0)
 
 // ------------------------------------------------------------------------------------------------------
@@ -556,8 +357,7 @@ DL4J_API void dl4j_conv_set_variant(int v) { g_fwd_variant = v; }
 __global__ __launch_bounds__(NTHREADS) void igemm_wrw_kernel(const bf16* __restrict__ X, const bf16* __restrict__ dY,
                                                               float* __restrict__ dW, float* __restrict__ db,
                                                               ConvGeom g, int m_per_split, FastDiv fOW, FastDiv fOH,
-                                                              int remap, float* __restrict__ part,
-                                                              float* __restrict__ partb) {
+                                                              float* __restrict__ part, float* __restrict__ partb) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_K * WRW_ROW];   // 2 buffers x (A + B) = 40 KB
   const int M = g.N * g.OH * g.OW;
   const int Kout = g.K;
@@ -566,7 +366,7 @@ __global__ __launch_bounds__(NTHREADS) void igemm_wrw_kernel(const bf16* __restr
   // XCD-aware order: logical ids are contiguous per XCD and tile-fastest, so every (k, j) tile of one pixel split
   // runs on the same XCD and the split's dY/X rows are fetched into one L2 instead of one per tile.
   const int hbid = blockIdx.x + blockIdx.y * gridDim.x;
-  const int lbid = remap ? xcd_remap(hbid, gridDim.x * gridDim.y) : hbid;
+  const int lbid = xcd_remap_g(hbid, gridDim.x * gridDim.y);
   const int tile = lbid % gridDim.x, split = lbid / gridDim.x;
   const int tk = tile % tiles_k, tj = tile / tiles_k;
   const int k0 = tk * TILE_N, j0 = tj * TILE_M;
@@ -716,152 +516,6 @@ __global__ __launch_bounds__(NTHREADS) void igemm_wrw_kernel(const bf16* __restr
     }
   }
 }
-
-// ------------------------------------------------------------------------------------------------------
-// WRW, LDS-DMA pipeline (v2): same math/output as igemm_wrw_kernel. Per stage: A = dY[32 m][128 k] and
-// B = im2col(X)[32 m][128 j], 256-byte rows, filled by global_load_lds (4 rows per wave-instruction, lane slot s
-// of row r holds 16-byte chunk s ^ 2(r&3): the 4 rows a transposed 16-lane read touches then cover 8 distinct
-// chunks = 32 distinct banks). Fragments are read with ds_read_b64_tr_b16 exactly as in the v1 kernel.
-// Every lane owns one fixed column chunk (fixed filter tap), so the per-step work is one multiply-high pixel
-// decode + bounds check per row.
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wrw_addr(int row, int col) {
-  return row * 256 + ((((col >> 3) ^ ((row & 3) << 1))) << 4) + (col & 7) * 2;
-}
-
-__global__ __launch_bounds__(NTHREADS) void igemm_wrw_glds(const bf16* __restrict__ X, const bf16* __restrict__ dY,
-                                                            float* __restrict__ dW, float* __restrict__ db,
-                                                            ConvGeom g, int m_per_split, FastDiv fOW, FastDiv fOH,
-                                                            int remap) {
-  __shared__ __attribute__((aligned(16))) char smem[G_STAGES * G_STAGE_BYTES];   // 4 x (8 KB + 8 KB)
-  const int M = g.N * g.OH * g.OW;
-  const int Kout = g.K;
-  const int RSC = g.R * g.S * g.C;
-  const int tiles_k = (Kout + TILE_N - 1) / TILE_N;
-  // XCD-aware order: logical ids are contiguous per XCD and tile-fastest, so every (k, j) tile of one pixel split
-  // runs on the same XCD and the split's dY/X rows are fetched into one L2 instead of one per tile.
-  const int hbid = blockIdx.x + blockIdx.y * gridDim.x;
-  const int lbid = remap ? xcd_remap(hbid, gridDim.x * gridDim.y) : hbid;
-  const int tile = lbid % gridDim.x, split = lbid / gridDim.x;
-  const int tk = tile % tiles_k, tj = tile / tiles_k;
-  const int k0 = tk * TILE_N, j0 = tj * TILE_M;
-  const int mbeg = split * m_per_split;
-  int mend = mbeg + m_per_split;
-  if (mend > M) mend = M;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wk = wid >> 1, wj = wid & 1;
-
-  int row[2], kcol[2], cc[2], rdh[2], sdw[2];
-  bool kok[2], jok[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    row[i] = (i * 4 + wid) * 4 + (lane >> 4);
-    const int chunk = (lane & 15) ^ ((row[i] & 3) << 1);
-    kcol[i] = k0 + chunk * 8;
-    kok[i] = kcol[i] < Kout;
-    const int jcol = j0 + chunk * 8;
-    jok[i] = jcol < RSC;
-    const int jc = jok[i] ? jcol : 0;
-    cc[i] = jc % g.C;
-    const int rs = jc / g.C;
-    rdh[i] = (rs / g.S) * g.dh - g.ph;
-    sdw[i] = (rs % g.S) * g.dw - g.pw;
-  }
-  const int nsteps = (mend - mbeg + TILE_K - 1) / TILE_K;
-  const bool do_bias = (db != nullptr) && (tj == 0);
-  float bsum = 0.f;
-
-  auto issue = [&](int st, int buf) {
-    char* A = smem + buf * G_STAGE_BYTES;
-    char* B = A + TILE_K * 256;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int m = mbeg + st * TILE_K + row[i];
-      const bool mok = m < mend;
-      const void* sa = (mok && kok[i]) ? (const void*)(dY + (long long)m * Kout + kcol[i]) : (const void*)g_zero_page;
-      const unsigned mm = mok ? (unsigned)m : 0u;
-      const unsigned t = fdiv(mm, fOW);
-      const int ow = (int)(mm - t * fOW.d);
-      const unsigned pn = fdiv(t, fOH);
-      const int oh = (int)(t - pn * fOH.d);
-      const int ih = oh * g.sh + rdh[i], iw = ow * g.sw + sdw[i];
-      const bool bok = mok && jok[i] && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
-      const void* sb = bok ? (const void*)(X + (((long long)pn * g.H + ih) * g.W + iw) * g.C + cc[i])
-                           : (const void*)g_zero_page;
-      glds16(sa, A + (i * 4 + wid) * 1024);
-      glds16(sb, B + (i * 4 + wid) * 1024);
-    }
-  };
-  const int grp = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-  auto frag = [&](const char* T, int colbase, int ks) -> bf16x8_t {
-    const int col = colbase + (grp & 1) * 16 + 4 * p;
-    const int r0 = ks * 16 + (grp >> 1) * 8 + q;
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(T + wrw_addr(r0, col)));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(T + wrw_addr(r0 + 4, col)));
-    bf16x8_t f;
-    const __bf16* l4 = reinterpret_cast<const __bf16*>(&lo);
-    const __bf16* h4 = reinterpret_cast<const __bf16*>(&hi);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { f[e] = l4[e]; f[e + 4] = h4[e]; }
-    return f;
-  };
-
-  f32x16_t acc[2][2];
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b)
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-
-#pragma unroll
-  for (int st = 0; st < G_STAGES - 1; ++st)
-    if (st < nsteps) issue(st, st);
-
-  for (int st = 0; st < nsteps; ++st) {
-    const int ahead = min(G_STAGES - 2, nsteps - 1 - st);
-    wait_stage(ahead);
-    raw_barrier();
-    if (st + G_STAGES - 1 < nsteps) issue(st + G_STAGES - 1, (st + G_STAGES - 1) % G_STAGES);
-    const char* A = smem + (st % G_STAGES) * G_STAGE_BYTES;
-    const char* B = A + TILE_K * 256;
-    if (do_bias && tid < TILE_N) {                  // conv-bias gradient: column sums of the dY tile
-#pragma unroll 8
-      for (int r = 0; r < TILE_K; ++r) bsum += bf2f(*reinterpret_cast<const u16*>(A + wrw_addr(r, tid)));
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t af[2], bfr[2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a) af[a] = frag(A, wk * 64 + a * 32, ks);
-#pragma unroll
-      for (int b = 0; b < 2; ++b) bfr[b] = frag(B, wj * 64 + b * 32, ks);
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
-    }
-  }
-
-  const int hh = lane >> 5;
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int j = j0 + wj * 64 + b * 32 + (lane & 31);
-    if (j >= RSC) continue;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int k = k0 + wk * 64 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        if (k < Kout) atomicAdd(dW + (long long)k * RSC + j, acc[a][b][e]);
-      }
-    }
-  }
-  if (do_bias && tid < TILE_N && k0 + tid < Kout) atomicAdd(db + k0 + tid, bsum);
-}
-
-static int g_wrw_variant = 0;   // v1 register-staged measured faster here (occupancy); v2 kept for A/B
-DL4J_API void dl4j_conv_set_wrw_variant(int v) { g_wrw_variant = v; }
-static int g_wrw_remap = 1;     // 1 = XCD-aware block order (all tiles of a pixel split on one XCD), 0 = launch order
-DL4J_API void dl4j_conv_set_wrw_remap(int v) { g_wrw_remap = v; }
 
 // ------------------------------------------------------------------------------------------------------
 // Weight relayout (bf16): W[K][C][R][S] -> Wkrsc[K][R][S][C]  and  Wflip[C][R][S][K] = W[k][c][R-1-r][S-1-s]
@@ -1034,7 +688,7 @@ DL4J_API int dl4j_conv_w_relayout(const void* W, void* krsc, void* flip, int K, 
 
 // Forward: X NHWC [N,H,W,C] bf16, Wkrsc [K][R*S*C], bias fp32 [K] or null, Y NHWC [N,OH,OW,K].
 // tstats (optional, fp32 [3][2*ceil(M/128)][K]): per-tile BatchNorm partial statistics of Y. Returns 1 when they
-// were written, 0 when not (unsupported variant), a HIP error code otherwise.
+// were written, 0 when not (unsupported shape), a HIP error code otherwise.
 DL4J_API int dl4j_conv_fwd(const void* X, const void* Wkrsc, const float* bias, void* Y, int N, int H, int W, int C,
                            int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
                            float* tstats, hipStream_t s) {
@@ -1042,7 +696,7 @@ DL4J_API int dl4j_conv_fwd(const void* X, const void* Wkrsc, const float* bias, 
   ConvGeom g = mk(N, H, W, C, OH, OW, K, R, S, sh, sw, ph, pw, dh, dw);
   const long long M = (long long)N * OH * OW;
   const int tiles = (int)(((M + TILE_M - 1) / TILE_M) * ((K + TILE_N - 1) / TILE_N));
-  const int stats_ok = tstats != nullptr && g_fwd_variant == 1 && C % TILE_K == 0 && R * S <= 64 && K % 8 == 0;
+  const int stats_ok = tstats != nullptr && C % TILE_K == 0 && R * S <= 64 && K % 8 == 0;
   LAUNCH_FWD(C % TILE_K == 0 && R * S <= 64, dim3(tiles), (const bf16*)X, (const bf16*)Wkrsc, bias, (bf16*)Y, g, R * S * C, 0, 0, 0,
              0, stats_ok ? tstats : nullptr);
   const int e = (int)hipGetLastError();
@@ -1096,16 +750,9 @@ DL4J_API int dl4j_conv_wrw_permute(float* ws, float* dW, int K, int C, int R, in
   return (int)hipGetLastError();
 }
 
-// Weight gradient: dW fp32 workspace [K][R][S][C] (pre-zeroed, accumulated atomically; equal to the DL4J layout
-// when R == S == 1), db fp32 [K] (pre-zeroed) or null.
-DL4J_API int dl4j_conv_wrw(const void* X, const void* dY, float* dW, float* db, int N, int H, int W, int C, int K,
-                           int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW, int splits,
-                           hipStream_t s) {
-  if (C % 8 != 0 || K % 8 != 0) return -1;
-  ConvGeom g = mk(N, H, W, C, OH, OW, K, R, S, sh, sw, ph, pw, dh, dw);
-  const int M = N * OH * OW;
-  const int RSC = R * S * C;
-  const int tiles = ((K + TILE_N - 1) / TILE_N) * ((RSC + TILE_M - 1) / TILE_M);
+// Pixel split of the weight gradient over `tiles` (k, j) tiles: sets the split count (requested, or chosen when
+// splits <= 0) and returns the pixels per split, a multiple of TILE_K with no empty split.
+static int wrw_split(int M, int tiles, int& splits) {
   if (splits <= 0) {
     // ~1.5 workgroups per CU in total (measured sweet spot between fill and atomic traffic, tools/conv_bench.py
     // --sweep-wrw); every split keeps >= 8 k-steps so the atomic epilogue stays amortised
@@ -1117,13 +764,23 @@ DL4J_API int dl4j_conv_wrw(const void* X, const void* dY, float* dW, float* db, 
   int mps = (M + splits - 1) / splits;
   mps = (mps + TILE_K - 1) / TILE_K * TILE_K;
   splits = (M + mps - 1) / mps;
-  if (g_wrw_variant == 1)
-    hipLaunchKernelGGL(igemm_wrw_glds, dim3(tiles, splits), dim3(NTHREADS), 0, s, (const bf16*)X, (const bf16*)dY, dW,
-                       db, g, mps, make_fastdiv((unsigned)OW), make_fastdiv((unsigned)OH), g_wrw_remap);
-  else
-    hipLaunchKernelGGL(igemm_wrw_kernel, dim3(tiles, splits), dim3(NTHREADS), 0, s, (const bf16*)X, (const bf16*)dY, dW,
-                       db, g, mps, make_fastdiv((unsigned)OW), make_fastdiv((unsigned)OH), g_wrw_remap,
-                       (float*)nullptr, (float*)nullptr);
+  return mps;
+}
+
+// Weight gradient: dW fp32 workspace [K][R][S][C] (pre-zeroed, accumulated atomically; equal to the DL4J layout
+// when R == S == 1), db fp32 [K] (pre-zeroed) or null.
+DL4J_API int dl4j_conv_wrw(const void* X, const void* dY, float* dW, float* db, int N, int H, int W, int C, int K,
+                           int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW, int splits,
+                           hipStream_t s) {
+  if (C % 8 != 0 || K % 8 != 0) return -1;
+  ConvGeom g = mk(N, H, W, C, OH, OW, K, R, S, sh, sw, ph, pw, dh, dw);
+  const int M = N * OH * OW;
+  const int RSC = R * S * C;
+  const int tiles = ((K + TILE_N - 1) / TILE_N) * ((RSC + TILE_M - 1) / TILE_M);
+  const int mps = wrw_split(M, tiles, splits);
+  hipLaunchKernelGGL(igemm_wrw_kernel, dim3(tiles, splits), dim3(NTHREADS), 0, s, (const bf16*)X, (const bf16*)dY, dW,
+                     db, g, mps, make_fastdiv((unsigned)OW), make_fastdiv((unsigned)OH), (float*)nullptr,
+                     (float*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -1164,15 +821,7 @@ DL4J_API long long dl4j_conv_wrw_det_floats(int N, int C, int K, int R, int S, i
   const int M = N * OH * OW;
   const int RSC = R * S * C;
   const int tiles = ((K + TILE_N - 1) / TILE_N) * ((RSC + TILE_M - 1) / TILE_M);
-  if (splits <= 0) {
-    splits = (384 + tiles - 1) / tiles;
-    const int maxs = (M + 8 * TILE_K - 1) / (8 * TILE_K);
-    if (splits > maxs) splits = maxs;
-    if (splits < 1) splits = 1;
-  }
-  int mps = (M + splits - 1) / splits;
-  mps = (mps + TILE_K - 1) / TILE_K * TILE_K;
-  splits = (M + mps - 1) / mps;
+  wrw_split(M, tiles, splits);
   return (long long)splits * K * (RSC + 1);
 }
 
@@ -1185,20 +834,12 @@ DL4J_API int dl4j_conv_wrw_det(const void* X, const void* dY, float* dW, float* 
   const int M = N * OH * OW;
   const int RSC = R * S * C;
   const int tiles = ((K + TILE_N - 1) / TILE_N) * ((RSC + TILE_M - 1) / TILE_M);
-  if (splits <= 0) {
-    splits = (384 + tiles - 1) / tiles;
-    const int maxs = (M + 8 * TILE_K - 1) / (8 * TILE_K);
-    if (splits > maxs) splits = maxs;
-    if (splits < 1) splits = 1;
-  }
-  int mps = (M + splits - 1) / splits;
-  mps = (mps + TILE_K - 1) / TILE_K * TILE_K;
-  splits = (M + mps - 1) / mps;
+  const int mps = wrw_split(M, tiles, splits);
   float* partb = part + (long long)splits * K * RSC;
   hipLaunchKernelGGL(igemm_wrw_kernel, dim3(tiles, splits), dim3(NTHREADS), 0, s, (const bf16*)X, (const bf16*)dY,
                      (float*)nullptr, (float*)nullptr, g, mps, make_fastdiv((unsigned)OW), make_fastdiv((unsigned)OH),
-                     g_wrw_remap, part, db ? partb : (float*)nullptr);
-  // a split whose pixel range is empty never stores: only possible when splits > ceil(M / mps), excluded above
+                     part, db ? partb : (float*)nullptr);
+  // a split whose pixel range is empty never stores: only possible when splits > ceil(M / mps), excluded by wrw_split
   const long long total = (long long)K * RSC;
   long long gsz = (total + 255) / 256;
   if (gsz > 4096) gsz = 4096;

@@ -28,14 +28,6 @@ constexpr int stream_smem() {
   return BN * KC * 128 + S * 128 * 128 + 128 * BN * 2;
 }
 
-template <int N> __device__ __forceinline__ void wait_vm_s() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else if constexpr (N == 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-  else if constexpr (N == 48) asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
 template <int DT, int BN, int KC, int S, int WGM, int WGN>
 __global__ __launch_bounds__((WGM * WGN + 1) * 64) void gemm_stream(GemmArgs g) {
   constexpr int BM = 128;
@@ -98,12 +90,12 @@ __global__ __launch_bounds__((WGM * WGN + 1) * 64) void gemm_stream(GemmArgs g) 
     for (int c = 0; c < D; ++c) issue(c);
 #pragma unroll 1
     for (int c = 0; c < nchunks; ++c) {
-      wait_vm_s<(D - 1) * NIA>();                  // chunk c (and everything before it) has landed
+      wait_vm<(D - 1) * NIA>();                  // chunk c (and everything before it) has landed
       raw_barrier();                               // B1(c)
       issue(c + D);                                // into the slot chunk c-1 occupied (read before B1(c))
       if (c % KC == KC - 1) raw_barrier();         // B2: the consumers' epilogue image
     }
-    wait_vm_s<0>();
+    wait_vm<0>();
     return;
   }
 
@@ -336,12 +328,12 @@ __global__ __launch_bounds__((WGM * WGN + 1) * 64) void conv_stream(GemmArgs g, 
     for (int c = 0; c < D; ++c) issue(c);
 #pragma unroll 1
     for (int c = 0; c < nchunks; ++c) {
-      wait_vm_s<(D - 1) * NI>();
+      wait_vm<(D - 1) * NI>();
       raw_barrier();                               // B1(c)
       issue(c + D);
       if (c % nk == nk - 1) raw_barrier();         // B2
     }
-    wait_vm_s<0>();
+    wait_vm<0>();
     return;
   }
 

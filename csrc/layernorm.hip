@@ -320,89 +320,6 @@ __global__ void __launch_bounds__(256) ln_bwd_reduce(const float* __restrict__ p
   }
 }
 
-// Partial-row fold for the block kernel's [P][NP*N] partials: grid (ceil(NP*N/64), S = ceil(P/32)); each block sums
-// 32 rows of 64 columns (4 row groups x 8 independent loads) and hands its row to the last block of its column chunk
-// (agent-scope ticket; write-through atomic stores drained before the relaxed ticket add, atomic loads in the reducer:
-// no fence), which sums the S rows in fixed order and writes dgamma / dbeta / dsum. ~36 x 16 blocks for BERT-base
-// (P = 512, N = 768) instead of ln_bwd_reduce's 72 latency-bound blocks.
-typedef __attribute__((address_space(1))) unsigned lq32;
-__device__ unsigned g_ln_ticket[64 * 128];
-
-__global__ void __launch_bounds__(256) ln_bwd_fold(const float* __restrict__ part, int P, int NPN, int N,
-                                                   float* __restrict__ q, unsigned* __restrict__ ticket,
-                                                   float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                   float* __restrict__ dsum) {
-  __shared__ float red[4][64];
-  const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + cl;
-  const int r0 = blockIdx.y * 32 + grp * 8;
-  float v[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) v[u] = (j < NPN && r0 + u < P) ? part[(long long)(r0 + u) * NPN + j] : 0.f;
-  float sacc = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) sacc += v[u];
-  red[grp][cl] = sacc;
-  __syncthreads();
-  const float t = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
-  auto out = [&](float x) {
-    const int which = j / N, col = j - which * N;
-    (which == 0 ? dgamma : (which == 1 ? dbeta : dsum))[col] = x;
-  };
-  if (gridDim.y == 1) {
-    if (grp == 0 && j < NPN) out(t);
-    return;
-  }
-  if (grp == 0 && j < NPN)
-    __hip_atomic_store((lq32*)(q + (long long)blockIdx.y * NPN + j), __float_as_uint(t), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add((lq32*)&ticket[blockIdx.x], 1u, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = old == gridDim.y - 1;
-    if (last) {
-      __hip_atomic_store((lq32*)&ticket[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");        // one acquire, then plain loads all in flight
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    red[0][0] = last ? 1.f : 0.f;
-  }
-  __syncthreads();
-  if (red[0][0] == 0.f) return;
-  __syncthreads();                                               // everyone has read the flag before red is reused
-  const int S = gridDim.y;
-  float x = 0.f;
-  if (j < NPN) {
-    constexpr int UL = 8;
-    for (int i0 = grp; i0 < S; i0 += 4 * UL) {
-      float v2[UL];
-#pragma unroll
-      for (int u = 0; u < UL; ++u) v2[u] = i0 + 4 * u < S ? q[(long long)(i0 + 4 * u) * NPN + j] : 0.f;
-#pragma unroll
-      for (int u = 0; u < UL; ++u) x += v2[u];
-    }
-  }
-  red[grp][cl] = x;
-  __syncthreads();
-  if (grp == 0 && j < NPN) out(red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl]);
-}
-
-static unsigned* ln_ticket_slot(int cols) {
-  static unsigned* base[64] = {nullptr};
-  static unsigned next = 0;
-  int dev = 0;
-  if (cols > 128 || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  if (!base[dev]) {
-    void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_ln_ticket)) != hipSuccess) return nullptr;
-    base[dev] = (unsigned*)p;
-  }
-  const unsigned k = __atomic_fetch_add(&next, 1u, __ATOMIC_RELAXED) % 64u;
-  return base[dev] + 128 * k;
-}
-
 template <typename T, int CH, bool DROP = false>
 static int fwd_l(const void* x, const void* r, const float* g, const float* b, void* y, float* mean, float* rstd,
                  long long M, int N, float eps, hipStream_t s, LnDrop dr = LnDrop{0, nullptr, 1.f, nullptr}) {
@@ -424,10 +341,9 @@ static int fwd_drop_l(const void* x, const void* r, const float* g, const float*
 static constexpr int kRPW = 16;
 
 // Block-partial kernel geometry: up to g_ln_cap (512) blocks of W waves, at least one row per wave.
-static int g_ln_cap = 128, g_ln_fold = 0;   // measured: tools/ln_bench.py (profiles/r3_ln_bwd_bench.log)
-DL4J_API void dl4j_ln_set_config(int block_cap, int fold) {
+static int g_ln_cap = 128;   // measured: tools/ln_bench.py (profiles/r3_ln_bwd_bench.log)
+DL4J_API void dl4j_ln_set_config(int block_cap) {
   g_ln_cap = block_cap < 1 ? 1 : (block_cap > 512 ? 512 : block_cap);
-  g_ln_fold = fold;
 }
 static inline int ln_waves(int N) { return N <= 1024 ? 8 : (N <= 2048 ? 4 : 2); }
 static inline long long ln_blocks(long long M, int N) {
@@ -438,8 +354,7 @@ static inline long long ln_blocks(long long M, int N) {
 
 static long long ln_bwd_partials(long long M) {
   const long long old = ((M + 4 * kRPW - 1) / (4 * kRPW)) * 4;
-  long long blk = M < 512 ? M : 512;                         // the block kernel never needs more rows than this,
-  blk += (blk + 31) / 32;                                    // plus the fold's ceil(rows / 32) rows of q
+  const long long blk = M < 512 ? M : 512;                   // the block kernel never needs more rows than this
   return old > blk ? old : blk;
 }
 
@@ -486,17 +401,8 @@ static int bwd_l(const void* dy, const void* x, const void* r, const float* g, c
     }
 #undef LNB
     const int NP = ds ? 3 : 2;
-    const int cols = (NP * N + 63) / 64, S = (int)((blocks + 31) / 32);
-    unsigned* tk = S > 1 && g_ln_fold ? ln_ticket_slot(cols) : nullptr;
-    if (g_ln_fold && (S == 1 || tk)) {
-      // q (the folded rows) lives right after the partial rows in the caller's workspace (see ln_bwd_partials)
-      float* q = part + blocks * NP * N;
-      hipLaunchKernelGGL(ln_bwd_fold, dim3(cols, S), dim3(256), 0, s, part, (int)blocks, NP * N, N, q, tk, dgamma,
-                         dbeta, dsum);
-    } else {
-      hipLaunchKernelGGL(ln_bwd_reduce, dim3((NP * N + 31) / 32), dim3(256), 0, s, part, (int)blocks, N, dgamma,
-                         dbeta, dsum, NP);
-    }
+    hipLaunchKernelGGL(ln_bwd_reduce, dim3((NP * N + 31) / 32), dim3(256), 0, s, part, (int)blocks, N, dgamma, dbeta,
+                       dsum, NP);
     return (int)hipGetLastError();
   }
   const long long blocks = (M + 4 * kRPW - 1) / (4 * kRPW);

@@ -1,7 +1,7 @@
-// Shared building blocks of the LDS-DMA MFMA tile kernels (csrc/gemm.hip GEMM, csrc/conv_gemm.hip implicit-GEMM
-// convolution): operand fragment reads from the swizzled K-contiguous / M-contiguous LDS images, the counted-vmcnt
-// helpers, and the LDS epilogue (alpha / bias / beta*C / pre-activation / activation, 16-byte row stores, BatchNorm
-// tile statistics). Everything lives in an anonymous namespace: each including translation unit gets its own copy.
+// Shared building blocks of the LDS-DMA MFMA tile kernels (csrc/gemm.hip GEMM, csrc/conv_*.hip convolutions):
+// operand fragment reads from the swizzled K-contiguous / M-contiguous LDS images, the counted-wait helpers, the
+// multiply-high division, and the LDS epilogue (alpha / bias / beta*C / pre-activation / activation, 16-byte row
+// stores, BatchNorm tile statistics). Everything lives in an anonymous namespace: each including translation unit gets its own copy.
 #pragma once
 #include "common.h"
 #include <hip/hip_fp16.h>
@@ -65,7 +65,6 @@ struct GemmArgs {
   const unsigned char* bnmask;   // bnb 3: the forward's ReLU bitmask (1 byte per 8 channels, residual BN layers)
   int bnb;
   int store_nt;                  // lean read-out: 1 = non-temporal (streaming) output stores (DL4J_AMD_GEMM_STORE_NT)
-  unsigned* sk_ticket;           // split-K fixup in the kernel (gemm_glds): per-tile arrival counters, else null
 };
 
 // Non-temporal (streaming) output stores in the lean read-out for outputs of >= 32 MB, which no L2 keeps for the
@@ -108,15 +107,44 @@ __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// Counted waits. The asm form is also a compiler memory barrier (nothing moves across it).
 template <int N> __device__ __forceinline__ void wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_lgkm() {
+  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
+// The same waits through the builtin, which is no compiler memory barrier: the halo kernels (csrc/conv_halo.hip,
+// csrc/conv_wrw.hip) are scheduled around it, and the asm form changes their code.
+// gfx9 s_waitcnt: vmcnt[3:0] | expcnt[6:4] (7 = no wait) | lgkmcnt[11:8] (15 = no wait) | vmcnt[5:4] at [15:14]
+template <int N> __device__ __forceinline__ void wait_vm_nb() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
+}
+template <int N> __device__ __forceinline__ void wait_lgkm_nb() {
+  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
+  __builtin_amdgcn_s_waitcnt(15 | (7 << 4) | (N << 8) | (3 << 14));
+}
+
+// Division by a runtime-uniform divisor via multiply-high (CUTLASS-style FastDivmod); valid for n < 2^31.
+struct FastDiv {
+  unsigned d, mul, shr;
+};
+inline FastDiv make_fastdiv(unsigned d) {
+  FastDiv f;
+  f.d = d < 1 ? 1 : d;
+  if (f.d == 1) { f.mul = 0; f.shr = 0; return f; }
+  unsigned l = 0;
+  while ((1u << l) < f.d) ++l;                     // ceil(log2 d)
+  const unsigned p = 31 + l;
+  f.mul = (unsigned)(((1ull << p) + f.d - 1) / f.d);
+  f.shr = p - 32;
+  return f;
+}
+__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
+  return f.d == 1 ? n : (__umulhi(n, f.mul) >> f.shr);
 }
 
 // ----------------------------------------------------------------------------------------------- epilogue
@@ -441,19 +469,7 @@ struct EpiOut {
   int dt;             // destination dtype (0 f32, 1 bf16, 2 f16)
   bool raw;           // split-K slab: no epilogue math
   bool vec;           // 16-byte aligned rows (ld and base) for vector stores
-  bool coh;           // slab stores coherent at agent scope (sc1 write-through): read by another block's fixup
 };
-
-// 16-byte / 4-byte stores visible to every XCD once the storing wave's vmcnt drains (sc1: written through the
-// XCD-local L2), for split-K slabs that the tile's last-arriving block sums (gemm_glds fixup)
-__device__ __forceinline__ void st_coh16(void* p, float a, float b, float c, float d) {
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
-  const f32x4v v = {a, b, c, d};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void st_coh4(float* p, float a) {
-  __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __device__ __forceinline__ void epi_chunk8(const GemmArgs& g, const EpiOut& o, void* Zp, int m, int n, float* v) {
   if (!o.raw) {
@@ -505,11 +521,6 @@ __device__ __forceinline__ void epi_chunk8(const GemmArgs& g, const EpiOut& o, v
     }
   }
   char* p = o.dst + ((long long)m * o.ld + n) * (o.dt == 0 ? 4 : 2);
-  if (o.coh) {
-    for (int j = 0; j < 8; ++j)
-      if (n + j < g.N) st_coh4(reinterpret_cast<float*>(p) + j, v[j]);
-    return;
-  }
   if (o.vec && n + 8 <= g.N) {
     if (o.dt == 0) {
       reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
@@ -575,16 +586,10 @@ __device__ __forceinline__ void epi_sweep(const GemmArgs& g, const EpiOut& o, vo
       }
     }
   };
-  const bool coh = o.coh;
   auto store8 = [&](char* p, const float* w) {
     if constexpr (F32) {
-      if (coh) {
-        st_coh16(p, w[0], w[1], w[2], w[3]);
-        st_coh16(p + 16, w[4], w[5], w[6], w[7]);
-      } else {
-        reinterpret_cast<float4*>(p)[0] = make_float4(w[0], w[1], w[2], w[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(w[4], w[5], w[6], w[7]);
-      }
+      reinterpret_cast<float4*>(p)[0] = make_float4(w[0], w[1], w[2], w[3]);
+      reinterpret_cast<float4*>(p)[1] = make_float4(w[4], w[5], w[6], w[7]);
     } else {
       uint4 pk;
       pk.x = (unsigned)to16(w[0], dt) | ((unsigned)to16(w[1], dt) << 16);

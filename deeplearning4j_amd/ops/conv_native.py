@@ -61,21 +61,6 @@ def _zeroed_wrw_ws(K, R, S, C, device):
     return ws
 
 
-def set_kernel_variant(v):
-    """1 = LDS-DMA pipelined forward/backward-data kernel (default), 0 = register-staged kernel (A/B testing)."""
-    native.load().dl4j_conv_set_variant(int(v))
-
-
-def set_wrw_variant(v):
-    """0 = register-staged weight-gradient kernel (default), 1 = LDS-DMA pipelined variant."""
-    native.load().dl4j_conv_set_wrw_variant(int(v))
-
-
-def set_wrw_remap(v):
-    """1 = XCD-aware weight-gradient block order (default), 0 = plain launch order (A/B only)."""
-    native.load().dl4j_conv_set_wrw_remap(int(v))
-
-
 def bump_version():
     WEIGHT_VERSION[0] += 1
 

@@ -49,12 +49,10 @@ def main():
     ap.add_argument("--variant", default="dl4j")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--kernel-variant", type=int, default=1)
     ap.add_argument("--sweep-wrw", action="store_true", help="time the weight-gradient kernel for several splits")
     a = ap.parse_args()
     from deeplearning4j_amd.ops import conv_native as CN
     dev = torch.device("cuda")
-    CN.set_kernel_variant(a.kernel_variant)
     shapes = capture_shapes(a.variant)
     count = collections.Counter(shapes)
     rows = []

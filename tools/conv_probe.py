@@ -20,11 +20,8 @@ def main():
             x = torch.randn(N, C, H, H, device=dev, dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
             w = (torch.randn(K, C, R, R, device=dev) * 0.05).to(torch.bfloat16)
             fl = 2.0 * N * H * H * K * C * R * R
-            for v in (0, 1):
-                CN.set_kernel_variant(v)
-                CN.bump_version()
-                ms = timeit(lambda: CN.conv2d_fwd(x, w, None, (1, 1), pad, (1, 1)), reps)
-                print(f"conv C={C} H={H} K={K} R={R} N={N} v{v}: {ms*1e3:8.1f} us  {fl/ms/1e9:6.0f} TF/s")
+            ms = timeit(lambda: CN.conv2d_fwd(x, w, None, (1, 1), pad, (1, 1)), reps)
+            print(f"conv C={C} H={H} K={K} R={R} N={N}: {ms*1e3:8.1f} us  {fl/ms/1e9:6.0f} TF/s")
             a = torch.randn(N * H * H, C * R * R, device=dev, dtype=torch.bfloat16)
             b = torch.randn(C * R * R, K, device=dev, dtype=torch.bfloat16)
             ms = timeit(lambda: a @ b, reps)

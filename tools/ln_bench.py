@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""LayerNorm backward timing (BERT-base shape M=4096, N=768, residual, dx column sums) over block caps and the two
-partial-reduction kernels (fold vs reduce), GPU-side time.  Usage: python tools/ln_bench.py"""
+"""LayerNorm backward timing (BERT-base shape M=4096, N=768, residual, dx column sums) over block caps, GPU-side
+time.  Usage: python tools/ln_bench.py"""
 import sys
 
 import torch
@@ -23,15 +23,14 @@ def main():
     L = native.load()
     ref = None
     for cap in (512, 256, 128, 64):
-        for fold in (1, 0):
-            L.dl4j_ln_set_config(cap, fold)
-            dx, dg, db = TN.ln_bwd(dy, x, g, mean, rstd, r, None, None, ds)
-            if ref is None:
-                ref = (dg.clone(), ds.clone())
-            err = max((dg - ref[0]).abs().max().item(), (ds - ref[1]).abs().max().item())
-            t = gpu_time(lambda: TN.ln_bwd(dy, x, g, mean, rstd, r, None, None, ds), reps=20) * 1e3
-            print(f"cap {cap:4d} fold {fold}: {t:7.1f} us  (max diff vs first {err:.2e})")
-    L.dl4j_ln_set_config(128, 0)
+        L.dl4j_ln_set_config(cap)
+        dx, dg, db = TN.ln_bwd(dy, x, g, mean, rstd, r, None, None, ds)
+        if ref is None:
+            ref = (dg.clone(), ds.clone())
+        err = max((dg - ref[0]).abs().max().item(), (ds - ref[1]).abs().max().item())
+        t = gpu_time(lambda: TN.ln_bwd(dy, x, g, mean, rstd, r, None, None, ds), reps=20) * 1e3
+        print(f"cap {cap:4d}: {t:7.1f} us  (max diff vs first {err:.2e})")
+    L.dl4j_ln_set_config(128)
 
 
 if __name__ == "__main__":
