@@ -784,36 +784,65 @@ static inline void bn_reduce_stage(float*& p1, float*& p2, int& nblk, int C, flo
     else hipLaunchKernelGGL((KERNEL<T, false, false>), __VA_ARGS__);                   \
   } while (0)
 
-// dtype: 0 fp32, 1 bf16, 2 fp16. ws: >= dl4j_bn_workspace_floats floats. ctx_out: 4*C floats (mean, invstd,
+// Element-type dispatch of the entry points: f(Ty<T>{}) with T = bf16 (dtype 1), f16 (dtype 2) or, where the entry
+// point has fp32 kernels (F32), float (any other dtype). The 16-bit-only entry points reject other dtypes first.
+template <typename T> struct Ty { typedef T type; };
+template <bool F32, typename F>
+static int bn_typed(int dtype, F&& f) {
+  if (dtype == 1) return f(Ty<bf16>{});
+  if (dtype == 2) return f(Ty<f16>{});
+  if constexpr (F32) return f(Ty<float>{});
+  else return -1;
+}
+
+// bn_fold's forward finalisation (FIN 0). x: row 0 is the statistics shift; rpp: rows per tile partial (SRC 1 only).
+static inline BnFin bn_fin_fwd(long long M, const void* x, const float* gamma, const float* beta, float gconst,
+                               float bconst, float* run_mean, float* run_var, float decay, float eps, float* ctx_out,
+                               int rpp) {
+  return BnFin{M, x, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out,
+               nullptr, nullptr, nullptr, nullptr, nullptr, rpp};
+}
+
+// bn_fold's backward finalisation (FIN 1): dbeta / dgamma (optional) and the means cdb / cdg the apply pass reads.
+static inline BnFin bn_fin_bwd(long long M, float* dbeta, float* dgamma, float* cdb, float* cdg) {
+  return BnFin{M, nullptr, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, 0.f, 0.f, nullptr, dbeta, dgamma, cdb, cdg,
+               nullptr, 0};
+}
+
+// The forward's apply pass from the finalized context. y null: statistics only (a shortcut BN folded into its
+// consumer); rctx: that shortcut BN's context, y = relu(bn(x) + bn_r(res)).
+template <typename T>
+static int bn_apply_launch(const T* x, const T* res, T* y, long long M, int C, const float* ctx, unsigned char* mask,
+                           const float* rctx, int relu, hipStream_t s) {
+  if (!y) return (int)hipGetLastError();
+  if (rctx && res)
+    hipLaunchKernelGGL((bn_apply<T, true, true, true>), dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, y, M, C, ctx,
+                       mask, rctx);
+  else
+    BN_DISPATCH3(bn_apply, T, relu, res, dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, y, M, C, ctx, mask,
+                 (const float*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// dtype: 0 fp32, 1 bf16, 2 fp16. ws: >= dl4j_bn_workspace_floats floats. f.ctx: 4*C floats (mean, invstd,
 // scale, shift). res: optional residual (same layout as x) -> y = relu(bn(x) + res) (relu forced on).
 template <typename T>
-static int bn_fwd_impl(const T* x, const T* res, T* y, long long M, int C, const float* gamma, const float* beta,
-                       float gconst, float bconst, float* run_mean, float* run_var, float decay, float eps,
-                       int training, int relu, float* ws, float* ctx_out, unsigned char* mask, hipStream_t s,
-                       const float* rctx = nullptr) {
+static int bn_fwd_impl(const T* x, const T* res, T* y, int C, const BnFin& f, int training, int relu, float* ws,
+                       unsigned char* mask, const float* rctx, hipStream_t s) {
   int nblk; long long rpb;
-  bn_grid(M, C, &nblk, &rpb);
+  bn_grid(f.M, C, &nblk, &rpb);
   float* p1 = ws;
   float* p2 = ws + (long long)nblk * C;
   float* q = p2 + (long long)nblk * C;
   if (training) {
-    hipLaunchKernelGGL(bn_stats_partial<T>, dim3(nblk), dim3(256), 0, s, x, M, C, rpb, p1, p2);
-    BnFin f{M, x, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out,
-            nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    hipLaunchKernelGGL(bn_stats_partial<T>, dim3(nblk), dim3(256), 0, s, x, f.M, C, rpb, p1, p2);
     const int rc = bn_fold_launch<T, 0, 0>(p1, p2, nblk, C, q, f, s);
     if (rc) return rc;
   } else {
-    hipLaunchKernelGGL(bn_finalize<T>, dim3((C + 63) / 64), dim3(256), 0, s, p1, p2, nblk, C, M, x, gamma, beta,
-                       gconst, bconst, run_mean, run_var, decay, eps, training, ctx_out);
+    hipLaunchKernelGGL(bn_finalize<T>, dim3((C + 63) / 64), dim3(256), 0, s, p1, p2, nblk, C, f.M, x, f.gamma, f.beta,
+                       f.gconst, f.bconst, f.run_mean, f.run_var, f.decay, f.eps, training, f.ctx);
   }
-  if (!y) return (int)hipGetLastError();              // statistics only (a shortcut BN folded into its consumer)
-  if (rctx && res)
-    hipLaunchKernelGGL((bn_apply<T, true, true, true>), dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, y, M, C,
-                       ctx_out, mask, rctx);
-  else
-    BN_DISPATCH3(bn_apply, T, relu, res, dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, y, M, C, ctx_out, mask,
-                 (const float*)nullptr);
-  return (int)hipGetLastError();
+  return bn_apply_launch<T>(x, res, y, f.M, C, f.ctx, mask, rctx, relu, s);
 }
 
 // mask: optional (res != nullptr only) M*C/8-byte ReLU bitmask for dl4j_bn_bwd (bn_apply).
@@ -824,12 +853,11 @@ DL4J_API int dl4j_bn_fwd(int dtype, const void* x, const void* res, void* y, lon
   if (C % 8 != 0 || C / 8 > 256) return -1;
   if (res) relu = 1;
   else mask = nullptr;
-#define BNF(T) return bn_fwd_impl<T>((const T*)x, (const T*)res, (T*)y, M, C, gamma, beta, gconst, bconst, run_mean, \
-                                     run_var, decay, eps, training, relu, ws, ctx_out, mask, s)
-  if (dtype == 1) BNF(bf16);
-  if (dtype == 2) BNF(f16);
-  BNF(float);
-#undef BNF
+  const BnFin f = bn_fin_fwd(M, x, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out, 0);
+  return bn_typed<true>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    return bn_fwd_impl<T>((const T*)x, (const T*)res, (T*)y, C, f, training, relu, ws, mask, nullptr, s);
+  });
 }
 
 // Training forward with the statistics already reduced per tile by the producing conv kernel (tstats, P partials):
@@ -840,23 +868,12 @@ DL4J_API long long dl4j_bn_tiles_workspace_floats(long long P, int C) {
 }
 
 template <typename T>
-static int bn_fwd_tiles_impl(const T* xb, const T* res, T* y, long long M, int C, const float* tstats, long long P,
-                             int rpp, const float* gamma, const float* beta, float gconst, float bconst,
-                             float* run_mean, float* run_var, float decay, float eps, int relu, float* ws,
-                             float* ctx_out, unsigned char* mask, hipStream_t s, const float* rctx = nullptr) {
-  BnFin f{M, xb, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out,
-          nullptr, nullptr, nullptr, nullptr, nullptr, rpp};
+static int bn_fwd_tiles_impl(const T* xb, const T* res, T* y, int C, const float* tstats, long long P, const BnFin& f,
+                             int relu, float* ws, unsigned char* mask, const float* rctx, hipStream_t s) {
   // one launch: tile re-centring + fold + finalize
   const int rc = bn_fold_launch<T, 1, 0>(tstats, nullptr, P, C, ws, f, s);
   if (rc) return rc;
-  if (!y) return (int)hipGetLastError();              // statistics only (a shortcut BN folded into its consumer)
-  if (rctx && res)
-    hipLaunchKernelGGL((bn_apply<T, true, true, true>), dim3(apply_grid(M, C)), dim3(256), 0, s, xb, res, y, M, C,
-                       ctx_out, mask, rctx);
-  else
-    BN_DISPATCH3(bn_apply, T, relu, res, dim3(apply_grid(M, C)), dim3(256), 0, s, xb, res, y, M, C, ctx_out,
-                 mask, (const float*)nullptr);
-  return (int)hipGetLastError();
+  return bn_apply_launch<T>(xb, res, y, f.M, C, f.ctx, mask, rctx, relu, s);
 }
 
 // rpp: rows per partial (64 for the implicit-GEMM / GEMM epilogues, the chunk's pixel count for dl4j_conv_halo);
@@ -869,11 +886,11 @@ DL4J_API int dl4j_bn_fwd_tiles(int dtype, const void* x, const void* res, void* 
     return -1;
   if (res) relu = 1;
   else mask = nullptr;
-  if (dtype == 2)
-    return bn_fwd_tiles_impl<f16>((const f16*)x, (const f16*)res, (f16*)y, M, C, tstats, P, rpp, gamma, beta, gconst,
-                                  bconst, run_mean, run_var, decay, eps, relu, ws, ctx_out, mask, s);
-  return bn_fwd_tiles_impl<bf16>((const bf16*)x, (const bf16*)res, (bf16*)y, M, C, tstats, P, rpp, gamma, beta,
-                                 gconst, bconst, run_mean, run_var, decay, eps, relu, ws, ctx_out, mask, s);
+  const BnFin f = bn_fin_fwd(M, x, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out, rpp);
+  return bn_typed<false>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    return bn_fwd_tiles_impl<T>((const T*)x, (const T*)res, (T*)y, C, tstats, P, f, relu, ws, mask, nullptr, s);
+  });
 }
 
 // dres: gradient w.r.t. the fused residual input (required when res != nullptr).
@@ -889,9 +906,7 @@ static int bn_bwd_impl(const T* x, const T* res, const T* dy, T* dx, T* dres, lo
   float* cdg = cdb + C;
   BN_DISPATCH3(bn_bwd_partial, T, relu, res, dim3(nblk), dim3(256), 0, s, x, res, dy, M, C, rpb, ctx, p1, p2, mask,
                (const float*)nullptr, (float*)nullptr);
-  BnFin f{M, nullptr, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, 0.f, 0.f, nullptr, dbeta, dgamma, cdb, cdg,
-          nullptr, 0};
-  const int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, f, s);
+  const int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, bn_fin_bwd(M, dbeta, dgamma, cdb, cdg), s);
   if (rc) return rc;
   BN_DISPATCH3(bn_bwd_apply, T, relu, res, dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, dy, dx, dres, M, C, ctx,
                cdb, cdg, mask, (const float*)nullptr, (const float*)nullptr);
@@ -924,13 +939,9 @@ static int bn_bwd_rbn_impl(const T* x, const T* res, const T* dy, T* dx, T* dres
   float* cdg2 = cdb2 + C;
   hipLaunchKernelGGL((bn_bwd_partial<T, true, true, true>), dim3(nblk), dim3(256), 0, s, x, res, dy, M, C, rpb, ctx, p1,
                      p2, mask, rctx, p3);
-  BnFin f{M, nullptr, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, 0.f, 0.f, nullptr, dbeta, dgamma, cdb, cdg,
-          nullptr, 0};
-  int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, f, s);
+  int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, bn_fin_bwd(M, dbeta, dgamma, cdb, cdg), s);
   if (rc) return rc;
-  BnFin f2{M, nullptr, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, 0.f, 0.f, nullptr, dbeta2, dgamma2, cdb2, cdg2,
-           nullptr, 0};
-  rc = bn_fold_launch<T, 0, 1>(p1, p3, nblk, C, q2, f2, s);
+  rc = bn_fold_launch<T, 0, 1>(p1, p3, nblk, C, q2, bn_fin_bwd(M, dbeta2, dgamma2, cdb2, cdg2), s);
   if (rc) return rc;
   hipLaunchKernelGGL((bn_bwd_apply<T, true, true, true>), dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, dy, dx, dres,
                      M, C, ctx, cdb, cdg, mask, rctx, cdg2);
@@ -941,11 +952,11 @@ DL4J_API int dl4j_bn_bwd_rbn(int dtype, const void* x, const void* res, const vo
                              long long M, int C, const float* ctx, float* dgamma, float* dbeta, const float* rctx,
                              float* dgamma2, float* dbeta2, float* ws, const unsigned char* mask, hipStream_t s) {
   if (C % 8 != 0 || C / 8 > 256 || !res || !dres || !rctx || (dtype != 1 && dtype != 2)) return -1;
-  if (dtype == 2)
-    return bn_bwd_rbn_impl<f16>((const f16*)x, (const f16*)res, (const f16*)dy, (f16*)dx, (f16*)dres, M, C, ctx, dgamma,
-                                dbeta, rctx, dgamma2, dbeta2, ws, mask, s);
-  return bn_bwd_rbn_impl<bf16>((const bf16*)x, (const bf16*)res, (const bf16*)dy, (bf16*)dx, (bf16*)dres, M, C, ctx,
-                               dgamma, dbeta, rctx, dgamma2, dbeta2, ws, mask, s);
+  return bn_typed<false>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    return bn_bwd_rbn_impl<T>((const T*)x, (const T*)res, (const T*)dy, (T*)dx, (T*)dres, M, C, ctx, dgamma, dbeta,
+                              rctx, dgamma2, dbeta2, ws, mask, s);
+  });
 }
 
 // Residual forward with the shortcut BN folded in: y = relu(bn(x) + bn_r(res)), rctx the shortcut BN's finalized
@@ -955,19 +966,15 @@ DL4J_API int dl4j_bn_fwd_rbn(int dtype, const void* x, const void* res, const fl
                              float* run_var, float decay, float eps, float* ws, float* ctx_out, unsigned char* mask,
                              const float* tstats, long long P, int rpp, hipStream_t s) {
   if (C % 8 != 0 || C / 8 > 256 || !res || !rctx || !y || (dtype != 1 && dtype != 2)) return -1;
-  if (tstats) {
-    if (rpp < 1) return -1;
-    if (dtype == 2)
-      return bn_fwd_tiles_impl<f16>((const f16*)x, (const f16*)res, (f16*)y, M, C, tstats, P, rpp, gamma, beta,
-                                    gconst, bconst, run_mean, run_var, decay, eps, 1, ws, ctx_out, mask, s, rctx);
-    return bn_fwd_tiles_impl<bf16>((const bf16*)x, (const bf16*)res, (bf16*)y, M, C, tstats, P, rpp, gamma, beta,
-                                   gconst, bconst, run_mean, run_var, decay, eps, 1, ws, ctx_out, mask, s, rctx);
-  }
-  if (dtype == 2)
-    return bn_fwd_impl<f16>((const f16*)x, (const f16*)res, (f16*)y, M, C, gamma, beta, gconst, bconst, run_mean,
-                            run_var, decay, eps, 1, 1, ws, ctx_out, mask, s, rctx);
-  return bn_fwd_impl<bf16>((const bf16*)x, (const bf16*)res, (bf16*)y, M, C, gamma, beta, gconst, bconst, run_mean,
-                           run_var, decay, eps, 1, 1, ws, ctx_out, mask, s, rctx);
+  if (tstats && rpp < 1) return -1;
+  const BnFin f = bn_fin_fwd(M, x, gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, ctx_out,
+                             tstats ? rpp : 0);
+  return bn_typed<false>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    if (tstats)
+      return bn_fwd_tiles_impl<T>((const T*)x, (const T*)res, (T*)y, C, tstats, P, f, 1, ws, mask, rctx, s);
+    return bn_fwd_impl<T>((const T*)x, (const T*)res, (T*)y, C, f, 1, 1, ws, mask, rctx, s);
+  });
 }
 
 DL4J_API int dl4j_bn_bwd(int dtype, const void* x, const void* res, const void* dy, void* dx, void* dres, long long M,
@@ -976,57 +983,11 @@ DL4J_API int dl4j_bn_bwd(int dtype, const void* x, const void* res, const void* 
   if (C % 8 != 0 || C / 8 > 256) return -1;
   if (res) relu = 1;
   else mask = nullptr;
-#define BNB(T) return bn_bwd_impl<T>((const T*)x, (const T*)res, (const T*)dy, (T*)dx, (T*)dres, M, C, ctx, dgamma, \
-                                     dbeta, relu, ws, mask, s)
-  if (dtype == 1) BNB(bf16);
-  if (dtype == 2) BNB(f16);
-  BNB(float);
-#undef BNB
-}
-
-// Backward with the partial sums already produced by the epilogue of the kernel that wrote dy (csrc/mfma_tile.h
-// epi_bnbwd_wave, armed by dl4j_bnb_arm): planes [2][P][C] of sum(d), sum(d*xhat) per 64-row partial. One fold +
-// finalize launch and the apply pass; bn_bwd_partial's full read of x and dy is gone. With a fused residual (res
-// flag) the ReLU comes from the forward's bitmask and dres (the masked dy) is written as in dl4j_bn_bwd.
-DL4J_API long long dl4j_bn_bwd_planes_workspace_floats(long long P, int C) {
-  return 2 * ((P + 31) / 32) * (long long)C + 4LL * C;
-}
-
-template <typename T>
-static int bn_bwd_planes_impl(const T* x, const T* dy, T* dx, T* dres, const unsigned char* mask, long long M, int C,
-                              const float* ctx, float* dgamma, float* dbeta, int relu, const float* planes,
-                              long long P, float* ws, hipStream_t s) {
-  float* q = ws;
-  float* cdb = q + 2 * ((P + 31) / 32) * (long long)C;
-  float* cdg = cdb + C;
-  BnFin f{M, nullptr, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, 0.f, 0.f, nullptr, dbeta, dgamma, cdb, cdg,
-          nullptr, 0};
-  const int rc = bn_fold_launch<T, 0, 1>(planes, planes + P * C, P, C, q, f, s);
-  if (rc) return rc;
-  if (dres)
-    hipLaunchKernelGGL((bn_bwd_apply<T, true, true>), dim3(apply_grid(M, C)), dim3(256), 0, s, x, nullptr, dy, dx,
-                       dres, M, C, ctx, cdb, cdg, mask, nullptr, nullptr);
-  else if (relu)
-    hipLaunchKernelGGL((bn_bwd_apply<T, true, false>), dim3(apply_grid(M, C)), dim3(256), 0, s, x, nullptr, dy, dx,
-                       nullptr, M, C, ctx, cdb, cdg, nullptr, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply<T, false, false>), dim3(apply_grid(M, C)), dim3(256), 0, s, x, nullptr, dy, dx,
-                       nullptr, M, C, ctx, cdb, cdg, nullptr, nullptr, nullptr);
-  return (int)hipGetLastError();
-}
-
-// dres / mask: both or neither (residual BN layers: dres = the masked dy, ReLU from the forward's bitmask).
-DL4J_API int dl4j_bn_bwd_planes(int dtype, const void* x, const void* dy, void* dx, void* dres,
-                                const unsigned char* mask, long long M, int C, const float* ctx, float* dgamma,
-                                float* dbeta, int relu, const float* planes, long long P, float* ws, hipStream_t s) {
-  if (C % 8 != 0 || C / 8 > 256 || P < 1 || P != (M + 63) / 64 || ((dres == nullptr) != (mask == nullptr))) return -1;
-  if (dtype == 1)
-    return bn_bwd_planes_impl<bf16>((const bf16*)x, (const bf16*)dy, (bf16*)dx, (bf16*)dres, mask, M, C, ctx, dgamma,
-                                    dbeta, relu, planes, P, ws, s);
-  if (dtype == 2)
-    return bn_bwd_planes_impl<f16>((const f16*)x, (const f16*)dy, (f16*)dx, (f16*)dres, mask, M, C, ctx, dgamma,
-                                   dbeta, relu, planes, P, ws, s);
-  return -1;
+  return bn_typed<true>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    return bn_bwd_impl<T>((const T*)x, (const T*)res, (const T*)dy, (T*)dx, (T*)dres, M, C, ctx, dgamma, dbeta, relu,
+                          ws, mask, s);
+  });
 }
 
 // -------------------------------------------------------------------------------------------- BN + ReLU + max pool
@@ -1462,13 +1423,12 @@ DL4J_API int dl4j_bn_pool_fwd(int dtype, const void* x, void* y, unsigned char* 
                               float* run_var, float decay, float eps, int training, const float* tstats,
                               long long P, int rpp, float* ws, float* ctx_out, hipStream_t s) {
   if (C % 8 != 0 || C / 8 > 256 || kh * kw > 127 || kh < 1 || kw < 1) return -1;
-#define BPF(T) return bn_pool_fwd_impl<T>((const T*)x, (T*)y, am, (T*)xh, N, H, W, C, OH, OW, kh, kw, sh, sw, pt, pl, \
-                                          gamma, beta, gconst, bconst, run_mean, run_var, decay, eps, training,    \
-                                          tstats, P, rpp, ws, ctx_out, s)
-  if (dtype == 1) BPF(bf16);
-  if (dtype == 2) BPF(f16);
-  BPF(float);
-#undef BPF
+  return bn_typed<true>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    return bn_pool_fwd_impl<T>((const T*)x, (T*)y, am, (T*)xh, N, H, W, C, OH, OW, kh, kw, sh, sw, pt, pl, gamma, beta,
+                               gconst, bconst, run_mean, run_var, decay, eps, training, tstats, P, rpp, ws, ctx_out,
+                               s);
+  });
 }
 
 // dy: gradient w.r.t. the pooled output; dx: w.r.t. x (the BN input). ws: >= dl4j_bn_workspace_floats(N*OH*OW, C).
@@ -1513,10 +1473,9 @@ DL4J_API int dl4j_bn_pool_bwd(int dtype, const void* x, const void* dy, const un
                               void* dx, int N, int H, int W, int C, int OH, int OW, int kh, int kw, int sh, int sw,
                               int pt, int pl, const float* ctx, float* dgamma, float* dbeta, float* ws, hipStream_t s) {
   if (C % 8 != 0 || C / 8 > 256 || kh * kw > 127) return -1;
-#define BPB(T) return bn_pool_bwd_impl<T>((const T*)x, (const T*)dy, am, (const T*)xh, (T*)dx, N, H, W, C, OH, OW, kh, \
-                                          kw, sh, sw, pt, pl, ctx, dgamma, dbeta, ws, s)
-  if (dtype == 1) BPB(bf16);
-  if (dtype == 2) BPB(f16);
-  BPB(float);
-#undef BPB
+  return bn_typed<true>(dtype, [&](auto ty) {
+    typedef typename decltype(ty)::type T;
+    return bn_pool_bwd_impl<T>((const T*)x, (const T*)dy, am, (const T*)xh, (T*)dx, N, H, W, C, OH, OW, kh, kw, sh, sw,
+                               pt, pl, ctx, dgamma, dbeta, ws, s);
+  });
 }

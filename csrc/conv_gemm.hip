@@ -29,7 +29,7 @@ struct ConvA {
   int R, S, sh, sw, ph, pw, dh, dw;
 };
 
-template <int DT, int BM, int BN, int WGM, int WGN, int STAGES, bool BNB = false, bool LEAN = false>
+template <int DT, int BM, int BN, int WGM, int WGN, int STAGES, bool LEAN = false>
 __global__ __launch_bounds__(WGM* WGN * 64, 2) void conv_glds(GemmArgs g, ConvA ca) {
   constexpr int NW = WGM * WGN;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
@@ -217,8 +217,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, 2) void conv_glds(GemmArgs g, ConvA 
     });
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     raw_barrier();
-    if constexpr (BNB) epi_bnbwd<RPP, BN, NW * 64>(g, smem, m0 + P * RPP, n0, tid);
-    else if (g.tstats) epi_stats<RPP, BN, NW * 64>(g, smem, m0 + P * RPP, n0, tid);
+    if (g.tstats) epi_stats<RPP, BN, NW * 64>(g, smem, m0 + P * RPP, n0, tid);
     epi_readout<RPP, BN, NW * 64>(g, o, nullptr, smem, m0 + P * RPP, n0, tid);
     if (P + 1 < BM / RPP) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -237,35 +236,34 @@ struct TileCfg {
 constexpr int kNumVariants = 5;
 const TileCfg kTiles[kNumVariants] = {{256, 128}, {128, 128}, {256, 64}, {128, 64}, {128, 256}};
 
-template <int DT, bool BNB, bool LEAN>
+template <int DT, bool LEAN>
 int launch_conv_t(int v, const GemmArgs& g, const ConvA& ca, hipStream_t s) {
   dim3 grid(g.tiles_m * g.tiles_n);
   switch (v) {
-    case 0: hipLaunchKernelGGL((conv_glds<DT, 256, 128, 4, 2, 3, BNB, LEAN>), grid, dim3(512), 0, s, g, ca); break;
-    case 1: hipLaunchKernelGGL((conv_glds<DT, 128, 128, 2, 2, 2, BNB, LEAN>), grid, dim3(256), 0, s, g, ca); break;
-    case 2: hipLaunchKernelGGL((conv_glds<DT, 256, 64, 4, 1, 3, BNB, LEAN>), grid, dim3(256), 0, s, g, ca); break;
-    case 3: hipLaunchKernelGGL((conv_glds<DT, 128, 64, 2, 2, 3, BNB, LEAN>), grid, dim3(256), 0, s, g, ca); break;
-    default: hipLaunchKernelGGL((conv_glds<DT, 128, 256, 2, 4, 3, BNB, LEAN>), grid, dim3(512), 0, s, g, ca); break;
+    case 0: hipLaunchKernelGGL((conv_glds<DT, 256, 128, 4, 2, 3, LEAN>), grid, dim3(512), 0, s, g, ca); break;
+    case 1: hipLaunchKernelGGL((conv_glds<DT, 128, 128, 2, 2, 2, LEAN>), grid, dim3(256), 0, s, g, ca); break;
+    case 2: hipLaunchKernelGGL((conv_glds<DT, 256, 64, 4, 1, 3, LEAN>), grid, dim3(256), 0, s, g, ca); break;
+    case 3: hipLaunchKernelGGL((conv_glds<DT, 128, 64, 2, 2, 3, LEAN>), grid, dim3(256), 0, s, g, ca); break;
+    default: hipLaunchKernelGGL((conv_glds<DT, 128, 256, 2, 4, 3, LEAN>), grid, dim3(512), 0, s, g, ca); break;
   }
   return (int)hipGetLastError();
 }
 
 // lean epilogue (mfma_tile.h): plain or biased 16-bit output, optional BN tile statistics; the fan-out beta
-// accumulation and the BN-backward sums keep the generic LDS epilogue
+// accumulation keeps the generic LDS epilogue
 bool conv_lean_ok(const GemmArgs& g) {
   static const int off = [] {
     const char* e = getenv("DL4J_AMD_GEMM_LEAN");
     return (e && e[0] == '0') ? 1 : 0;
   }();
-  if (off || g.bnb || g.beta != 0.f || g.act != 0) return false;
+  if (off || g.beta != 0.f || g.act != 0) return false;
   if (g.bias_mode == 1 && (reinterpret_cast<uintptr_t>(g.bias) & 15)) return false;
   return (g.N & 7) == 0 && (g.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0;
 }
 
 template <int DT>
 int launch_conv(int v, const GemmArgs& g, const ConvA& ca, hipStream_t s) {
-  if (g.bnb) return launch_conv_t<DT, true, false>(v, g, ca, s);
-  return conv_lean_ok(g) ? launch_conv_t<DT, false, true>(v, g, ca, s) : launch_conv_t<DT, false, false>(v, g, ca, s);
+  return conv_lean_ok(g) ? launch_conv_t<DT, true>(v, g, ca, s) : launch_conv_t<DT, false>(v, g, ca, s);
 }
 
 // Default tile when the host has no timing for the shape: the largest tile whose width fits the channel count and
@@ -329,13 +327,6 @@ DL4J_API int dl4j_conv_fwd_v3(int dt, const void* X, const void* Wkrsc, const fl
   g.store_nt = store_nt_for(M * K * 2);
   g.tstats = tstats;
   g.stats_P = tstats ? (int)((M + 63) / 64) : 0;
-  if (tstats && bnb_armed().mode) {                 // BN-backward sums of dX (stride-1 bwd-data as a transposed conv)
-    if (bias || K % 4 != 0) return -1;             // beta != 0: sums of the stored dX + beta*Y (fan-out)
-    g.bnx = bnb_armed().x;
-    g.bnctx = bnb_armed().ctx;
-    g.bnmask = bnb_armed().mask;
-    g.bnb = bnb_armed().mode;
-  }
   ConvA ca;
   ca.X = X;
   ca.N = N; ca.H = H; ca.W = W; ca.C = C; ca.OH = OH; ca.OW = OW;

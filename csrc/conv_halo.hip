@@ -340,7 +340,6 @@ DL4J_API int dl4j_conv_halo(int dt, const void* X, const void* Wkrsc, const floa
                             float beta, float* tstats, hipStream_t s) {
   if ((dt != 1 && dt != 2) || beta != 0.f) return -1;
   if (dl4j_conv_halo_plan(N, H, W, C, K, R, S, sh, sw, ph, pw, dh, dw, OH, OW, nullptr) <= 0) return -1;
-  if (tstats && bnb_armed().mode) return -1;         // BN-backward sums of dX: the round-3 kernels' epilogue only
   if ((long long)N * H * W * 64 >= 0x7fffffffLL) return -1;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(Wkrsc) & 15) ||
       (reinterpret_cast<uintptr_t>(Y) & 15) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15)))

@@ -62,7 +62,7 @@ constexpr int glds_smem(int BM, int BN, int STAGES) {
   return cmax(STAGES * (BM + BN) * 128, cmax(BM * BN * 2, 64 * (BN * 4 + 16)));
 }
 
-template <int DT, int BM, int BN, int WGM, int WGN, bool AKC, bool BKC, int STAGES, bool BNB = false, bool LEAN = false>
+template <int DT, int BM, int BN, int WGM, int WGN, bool AKC, bool BKC, int STAGES, bool LEAN = false>
 __global__ __launch_bounds__(WGM* WGN * 64, (STAGES == 1 && WGM * WGN == 4 ? 4 : 2)) void gemm_glds(GemmArgs g) {
   constexpr int NW = WGM * WGN;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
@@ -271,8 +271,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (STAGES == 1 && WGM * WGN == 4 ? 4 :
     });
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     raw_barrier();
-    if constexpr (BNB) epi_bnbwd<RPP, BN, WGM * WGN * 64>(g, smem, m0 + P * RPP, n0, tid);
-    else if (g.tstats) epi_stats<RPP, BN, WGM * WGN * 64>(g, smem, m0 + P * RPP, n0, tid);
+    if (g.tstats) epi_stats<RPP, BN, WGM * WGN * 64>(g, smem, m0 + P * RPP, n0, tid);
     epi_readout<RPP, BN, WGM * WGN * 64>(g, o, Zp, smem, m0 + P * RPP, n0, tid);
     if (P + 1 < BM / RPP) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -405,7 +404,7 @@ template <> struct Mfma16<2> {
   }
 };
 
-template <int DT, bool AKC, bool BKC, bool BNB = false, bool LEAN = false>
+template <int DT, bool AKC, bool BKC, bool LEAN = false>
 __global__ __launch_bounds__(512) void gemm_8ph(GemmArgs g) {
   typedef typename MfmaT<DT>::v8 v8;
   __shared__ __attribute__((aligned(1024))) char smem[2 * 4 * 16384 + 8192];   // + pad rows of the epilogue tile
@@ -671,8 +670,7 @@ __global__ __launch_bounds__(512) void gemm_8ph(GemmArgs g) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       raw_barrier();
       GSTAMP(4 + 2 * P);
-      if constexpr (BNB) epi_bnbwd<128, 256, 512>(g, smem, m0 + P * 128, n0, tid);
-      else if (g.tstats) epi_stats<128, 256, 512>(g, smem, m0 + P * 128, n0, tid);
+      if (g.tstats) epi_stats<128, 256, 512>(g, smem, m0 + P * 128, n0, tid);
       epi_readout<128, 256, 512>(g, o, Zp, smem, m0 + P * 128, n0, tid);
       GSTAMP(5 + 2 * P);
       if (P == 0) {
@@ -953,32 +951,16 @@ int launch_fast(int cfg, const GemmArgs& g, int batch, hipStream_t s) {
   const int tiles = g.tiles_m * g.tiles_n;
   dim3 grid(tiles, g.splits, batch);
   switch (cfg) {
-    case 0: hipLaunchKernelGGL((gemm_glds<DT, 256, 256, 2, 4, AKC, BKC, 2, false, LEAN>), grid, dim3(512), 0, s, g); break;
-    case 1: hipLaunchKernelGGL((gemm_glds<DT, 256, 128, 4, 2, AKC, BKC, 3, false, LEAN>), grid, dim3(512), 0, s, g); break;
-    case 2: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 2, false, LEAN>), grid, dim3(256), 0, s, g); break;
-    case 3: hipLaunchKernelGGL((gemm_glds<DT, 128, 64, 2, 2, AKC, BKC, 3, false, LEAN>), grid, dim3(256), 0, s, g); break;
-    case 5: hipLaunchKernelGGL((gemm_glds<DT, 128, 64, 2, 2, AKC, BKC, 1, false, LEAN>), grid, dim3(256), 0, s, g); break;
-    case 6: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 3, false, LEAN>), grid, dim3(256), 0, s, g); break;
-    case 7: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 4, false, LEAN>), grid, dim3(256), 0, s, g); break;
-    case 8: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 1, false, LEAN>), grid, dim3(256), 0, s, g); break;
-    case 9: hipLaunchKernelGGL((gemm_glds<DT, 128, 256, 2, 4, AKC, BKC, 1, false, LEAN>), grid, dim3(512), 0, s, g); break;
-    default: hipLaunchKernelGGL((gemm_8ph<DT, AKC, BKC, false, LEAN>), grid, dim3(512), 0, s, g); break;
-  }
-  return (int)hipGetLastError();
-}
-
-// BN-backward epilogue instantiations: only the 1x1 bwd-data layout (dY rows K-contiguous, W [K][C] N-contiguous)
-template <int DT>
-int launch_fast_bnb(int cfg, const GemmArgs& g, hipStream_t s) {
-  if (cfg >= 6) return -1;                      // the deep-ring 128x128 tiles have no BN-backward instantiation
-  dim3 grid(g.tiles_m * g.tiles_n, 1, 1);
-  switch (cfg) {
-    case 0: hipLaunchKernelGGL((gemm_glds<DT, 256, 256, 2, 4, true, false, 2, true>), grid, dim3(512), 0, s, g); break;
-    case 1: hipLaunchKernelGGL((gemm_glds<DT, 256, 128, 4, 2, true, false, 3, true>), grid, dim3(512), 0, s, g); break;
-    case 2: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, true, false, 2, true>), grid, dim3(256), 0, s, g); break;
-    case 3: hipLaunchKernelGGL((gemm_glds<DT, 128, 64, 2, 2, true, false, 3, true>), grid, dim3(256), 0, s, g); break;
-    case 5: hipLaunchKernelGGL((gemm_glds<DT, 128, 64, 2, 2, true, false, 1, true>), grid, dim3(256), 0, s, g); break;
-    default: hipLaunchKernelGGL((gemm_8ph<DT, true, false, true>), grid, dim3(512), 0, s, g); break;
+    case 0: hipLaunchKernelGGL((gemm_glds<DT, 256, 256, 2, 4, AKC, BKC, 2, LEAN>), grid, dim3(512), 0, s, g); break;
+    case 1: hipLaunchKernelGGL((gemm_glds<DT, 256, 128, 4, 2, AKC, BKC, 3, LEAN>), grid, dim3(512), 0, s, g); break;
+    case 2: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 2, LEAN>), grid, dim3(256), 0, s, g); break;
+    case 3: hipLaunchKernelGGL((gemm_glds<DT, 128, 64, 2, 2, AKC, BKC, 3, LEAN>), grid, dim3(256), 0, s, g); break;
+    case 5: hipLaunchKernelGGL((gemm_glds<DT, 128, 64, 2, 2, AKC, BKC, 1, LEAN>), grid, dim3(256), 0, s, g); break;
+    case 6: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 3, LEAN>), grid, dim3(256), 0, s, g); break;
+    case 7: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 4, LEAN>), grid, dim3(256), 0, s, g); break;
+    case 8: hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, AKC, BKC, 1, LEAN>), grid, dim3(256), 0, s, g); break;
+    case 9: hipLaunchKernelGGL((gemm_glds<DT, 128, 256, 2, 4, AKC, BKC, 1, LEAN>), grid, dim3(512), 0, s, g); break;
+    default: hipLaunchKernelGGL((gemm_8ph<DT, AKC, BKC, LEAN>), grid, dim3(512), 0, s, g); break;
   }
   return (int)hipGetLastError();
 }
@@ -993,7 +975,6 @@ int launch_fast_lay(int cfg, int akc, int bkc, const GemmArgs& g, int batch, hip
 
 template <int DT>
 int launch_fast_l(int cfg, int akc, int bkc, const GemmArgs& g, int batch, bool lean, hipStream_t s) {
-  if (g.bnb) return (akc && !bkc && batch == 1) ? launch_fast_bnb<DT>(cfg, g, s) : -3;
   return lean ? launch_fast_lay<DT, true>(cfg, akc, bkc, g, batch, s) : launch_fast_lay<DT, false>(cfg, akc, bkc, g, batch, s);
 }
 
@@ -1001,7 +982,7 @@ int launch_fast_l(int cfg, int akc, int bkc, const GemmArgs& g, int batch, bool 
 // (pre-activation kept in Z or not) / gelu-backward from Z, no beta, no split-K slabs, 16-byte addressable rows; BN
 // tile statistics from the 16-bit image.
 bool lean_ok(const GemmArgs& g, int batch) {
-  if (g.splits > 1 || g.bnb || g.out_dt == 0 || g.beta != 0.f) return false;
+  if (g.splits > 1 || g.out_dt == 0 || g.beta != 0.f) return false;
   if (g.tstats && g.act != 0) return false;        // statistics are of the stored pre-activation output
   if (g.act != 0 && g.act != 1 && g.act != 4 && g.act != kActDGelu) return false;
   if (g.act == kActDGelu && !g.Z) return false;
@@ -1058,25 +1039,6 @@ DL4J_API long long dl4j_gemm_plan(int M, int N, int K, int batch, int* cfg, int*
   return *splits > 1 ? (long long)(*splits) * M * N * 4 : 0;
 }
 
-BnbArm& bnb_armed() {
-  static thread_local BnbArm a{nullptr, nullptr, nullptr, 0};
-  return a;
-}
-
-// Arms (mode 1: plain, 2: ReLU recomputed from x, 3: ReLU from the forward's bitmask) or disarms (mode 0)
-// BatchNorm-backward statistics for the next dl4j_gemm / dl4j_conv_fwd_v3 launches of this thread that pass a
-// statistics buffer: planes [2][P][N] of sum(d), sum(d*xhat) of the stored output instead of the forward [3][P][N]
-// tile statistics. x: the BN layer's input, laid out like the output; ctx: its forward [mean | invstd | scale | shift]
-// (csrc/batchnorm.hip); mask: bn_apply's ReLU bitmask (mode 3).
-DL4J_API void dl4j_bnb_arm(const void* x, const float* ctx, const unsigned char* mask, int mode) {
-  BnbArm& a = bnb_armed();
-  const bool ok = mode && x && ctx && (mode != 3 || mask);
-  a.x = ok ? x : nullptr;
-  a.ctx = ok ? ctx : nullptr;
-  a.mask = ok ? mask : nullptr;
-  a.mode = ok ? mode : 0;
-}
-
 // Fast path. in_dt: 1 bf16, 2 f16. out_dt: 0 f32, 1 bf16, 2 f16. akc/bkc: operand layout flags (see top).
 // Requirements (else -1): lda/ldb multiples of 8 elements and 16-byte aligned bases; K % 8 == 0 for K-contiguous
 // operands, M % 8 == 0 (N % 8 == 0) for an M- (N-) contiguous A (B); batch > 1 only without split-K.
@@ -1120,19 +1082,11 @@ DL4J_API int dl4j_gemm(int in_dt, int out_dt, int M, int N, int K, int batch, co
   g.alpha = alpha; g.beta = beta; g.bias_mode = bias ? bias_mode : 0; g.act = act; g.out_dt = out_dt;
   g.tstats = nullptr;
   g.stats_P = 0;
-  g.bnx = nullptr; g.bnctx = nullptr; g.bnmask = nullptr; g.bnb = 0;
   g.store_nt = store_nt_for((long long)M * N * batch * (out_dt == 0 ? 4 : 2));
   if (tstats) {                                   // statistics only from the 8-phase epilogue without split-K
     if (splits > 1 || batch > 1) return -3;
     g.tstats = tstats;
     g.stats_P = stats_P;
-    const BnbArm& ba = bnb_armed();
-    if (ba.mode) {                                // BN-backward sums of the stored output (mfma_tile.h epi_bnbwd_wave)
-      if (bias || act || (N & 3) || (ldc & 3) || (out_dt != 1 && out_dt != 2) || (ba.mode == 3 && ldc != N) ||
-          (reinterpret_cast<uintptr_t>(C) & 7))
-        return -3;
-      g.bnx = ba.x; g.bnctx = ba.ctx; g.bnmask = ba.mask; g.bnb = ba.mode;
-    }
   }
   {
     const int esz = out_dt == 0 ? 4 : 2;
@@ -1143,7 +1097,7 @@ DL4J_API int dl4j_gemm(int in_dt, int out_dt, int M, int N, int K, int batch, co
   g.tiles_n = (N + kCfg[cfg].bn - 1) / kCfg[cfg].bn;
   const bool lean = lean_ok(g, batch);
   if (cfg == 10) {                                // streaming kernel: its contract, else refused (-4)
-    if (!akc || !bkc || batch != 1 || splits != 1 || !lean || g.bnb || g.Z || (M % 128)) return -4;
+    if (!akc || !bkc || batch != 1 || splits != 1 || !lean || g.Z || (M % 128)) return -4;
     return dl4j_gemm_stream(in_dt, A, lda, B, ldb, C, ldc, M, N, K, alpha, g.bias, g.bias_mode, act, out_dt, tstats,
                             stats_P, g.store_nt, s);
   }

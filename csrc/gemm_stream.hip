@@ -447,7 +447,6 @@ DL4J_API int dl4j_conv_stream(int dt, const void* X, const void* Wkrsc, const fl
                               int C, int K, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
                               float beta, float* tstats, hipStream_t s) {
   if ((dt != 1 && dt != 2) || C % 64 != 0 || K % 64 != 0 || R * S > 64 || R < 1 || S < 1 || beta != 0.f) return -1;
-  if (tstats && bnb_armed().mode) return -1;        // BN-backward sums of dX: the round-3 kernels' epilogue only
   const long long M = (long long)N * OH * OW;
   if (M <= 0 || M % 128 || (long long)N * H * W * C >= 0x7fffffffLL || M * K >= 0x7fffffffLL) return -1;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(Wkrsc) & 15) ||

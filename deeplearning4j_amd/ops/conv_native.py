@@ -10,7 +10,6 @@ Weights are re-laid-out once per parameter version (KRSC for forward, flipped CR
 """
 import ctypes
 import weakref
-import contextlib
 import functools
 import os
 
@@ -384,7 +383,13 @@ def _fwd_launch(variant, x, wk, bias, y, geom, beta, ts):
                              OW, _ptr(ts), _stream())
 
 
-def _v3_pick(key, launch, out, make_ts, allow_r2=True):
+def _bwd_key(acc, geo, dtype):
+    """Choice key of a stride-1 backward-data shape. The constant False was the flag of a removed kernel mode: the
+    shipped kernel-choice database (tunedb) stores its keys by repr with it, so dropping it would miss every entry."""
+    return ("bwd_acc" if acc else "bwd", geo, dtype, False)
+
+
+def _v3_pick(key, launch, out, make_ts):
     """Per-shape kernel choice: the first eager call times every tile variant of the round-3 engine and the round-2
     kernel on scratch outputs (inline on this stream) and keeps the fastest; calls under HIP-graph capture, or with
     DL4J_AMD_CONV_TUNE=0, use the remembered choice or the engine's default tile."""
@@ -393,9 +398,7 @@ def _v3_pick(key, launch, out, make_ts, allow_r2=True):
         return v                                       # steady state: nothing below is built per launch
     lib = native.load()
     geom = key[1]
-    # allow_r2=False: the round-2 kernel lacks an epilogue the caller needs (BN-backward sums), so its lower kernel
-    # time would not be the lower step time
-    r2 = [-1] if out.dtype == torch.bfloat16 and allow_r2 else []
+    r2 = [-1] if out.dtype == torch.bfloat16 else []
     scratch = functools.cache(lambda: out.clone() if key[0] == "bwd_acc" else torch.empty_like(out))
     ts = functools.lru_cache(maxsize=1)(make_ts)       # one statistics buffer per candidate, not per launch
     return autotune.pick(
@@ -425,18 +428,12 @@ def _conv2d_bwd(x, w, dy, stride, pad4, dilation, need_dx, need_dw, need_db, gW=
     if C != Cw or C % 8 != 0 or K % 8 != 0:
         return None
     OH, OW = dy.shape[2], dy.shape[3]
-    bnb = getattr(x, "_bn_bwd_req", None) if need_dx else None   # x is a training BN layer's output (ops/native.py)
     x = _cl(x)
     dy = _cl(dy)
     adt = x.dtype
     lib = native.load()
     dx = None
     pw = _is_pointwise(R, S, stride, pad4, dilation)
-    if dx_accum is not None and hasattr(dx_accum, "_bn_bwd_stats"):
-        del dx_accum._bn_bwd_stats                     # about to be summed into: its BN-backward sums go stale
-    if bnb is not None and (adt not in (torch.bfloat16, torch.float16) or tuple(bnb[0].shape) != (N * H * W, C) or
-                            bnb[0].dtype != adt or (dx_accum is not None and native.BNB_MODE < 2)):
-        bnb = None
     if need_dx and pw and gemm_dx:
         from .gemm import mmul
         M = N * H * W
@@ -444,16 +441,8 @@ def _conv2d_bwd(x, w, dy, stride, pad4, dilation, need_dx, need_dw, need_db, gW=
             and dx_accum.is_contiguous(memory_format=torch.channels_last)
         dx = dx_accum if acc else arena.empty((N, C, H, W), adt, x.device, channels_last=True)
         # dX[M, C] = dY[M, K] . W[K, C]  (+= the other consumer's gradient through beta)
-        if bnb is not None and (acc or dx_accum is None):
-            # ... with the consuming BN layer's backward partial sums (of the stored sum) from the epilogue
-            planes = torch.empty((2, (M + 63) // 64, C), dtype=torch.float32, device=x.device)
-            with native.bnb_armed(bnb):
-                mmul(dy.permute(0, 2, 3, 1).reshape(M, K), w.reshape(K, C), out=dx.permute(0, 2, 3, 1).reshape(M, C),
-                     beta=1.0 if acc else 0.0, stats=planes, stats_tag="bnb_acc" if acc else "bnb")
-            native.bnb_tag(dx, planes, bnb)
-        else:
-            mmul(dy.permute(0, 2, 3, 1).reshape(M, K), w.reshape(K, C), out=dx.permute(0, 2, 3, 1).reshape(M, C),
-                 beta=1.0 if acc else 0.0)
+        mmul(dy.permute(0, 2, 3, 1).reshape(M, K), w.reshape(K, C), out=dx.permute(0, 2, 3, 1).reshape(M, C),
+             beta=1.0 if acc else 0.0)
     elif need_dx:
         s1 = tuple(stride) == (1, 1) and tuple(dilation) == (1, 1)
         pure_1x1 = R == 1 and S == 1 and not any(pad4) and tuple(dilation) == (1, 1)
@@ -471,19 +460,9 @@ def _conv2d_bwd(x, w, dy, stride, pad4, dilation, need_dx, need_dw, need_db, gW=
                 return lib.dl4j_conv_bwd_data_s1(_ptr(dy), _ptr(flip), _ptr(out), N, H, W, C, K, R, S, pad4[0],
                                                  pad4[2], OH, OW, int(acc), _stream())
             v = -1
-            P = (N * H * W + 63) // 64
-            mk = (lambda var: torch.empty((2, P, C), dtype=torch.float32, device=x.device) if var >= 0 else None) \
-                if bnb is not None else (lambda var: None)
-            with (native.bnb_armed(bnb) if bnb is not None else contextlib.nullcontext()):
-                if _v3_ok(K, C, R, S):
-                    v = _v3_pick(("bwd_acc" if acc else "bwd", geo_b, adt, bnb is not None), bwd_launch, dx, mk,
-                                 allow_r2=bnb is None)
-                planes = mk(v)
-                rc = bwd_launch(v, dx, planes)
-            if rc == 1:
-                native.bnb_tag(dx, planes, bnb)
-                rc = 0
-            native._check(rc, "conv_bwd_data_s1")
+            if _v3_ok(K, C, R, S):
+                v = _v3_pick(_bwd_key(acc, geo_b, adt), bwd_launch, dx, lambda var: None)
+            native._check(bwd_launch(v, dx, None), "conv_bwd_data_s1")
         elif pure_1x1 and stride[0] == stride[1] and not fp16:
             _, flip = _relayout(w, False, True)
             if acc:

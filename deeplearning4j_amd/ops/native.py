@@ -355,18 +355,14 @@ def bn_fwd(x, gamma, beta, run_mean, run_var, training, decay, eps, relu, residu
                                    _ptr(run_mean), _ptr(run_var), float(decay), float(eps), 1 if relu else 0,
                                    _ptr(wst), _ptr(ctx), _ptr(mask), _stream())
         _check(rc, "bn_fwd_tiles")
-        if stats_only:
-            return x, ("NATIVE_STATS", x, ctx, False, M, C, None, None)
-        _bnb_request(y, xr, ctx, relu, res, mask, training, dt)
-        return y, ("NATIVE", x, ctx, relu, M, C, res, mask)
-    rc = lib.dl4j_bn_fwd(dt, _ptr(xr), _ptr(res), _ptr(y), M, C, _ptr(g), _ptr(b),
-                         float(gamma) if g is None else 1.0, float(beta) if b is None else 0.0, _ptr(run_mean),
-                         _ptr(run_var), float(decay), float(eps), 1 if training else 0, 1 if relu else 0, _ptr(ws),
-                         _ptr(ctx), _ptr(mask), _stream())
-    _check(rc, "bn_fwd")
+    else:
+        rc = lib.dl4j_bn_fwd(dt, _ptr(xr), _ptr(res), _ptr(y), M, C, _ptr(g), _ptr(b),
+                             float(gamma) if g is None else 1.0, float(beta) if b is None else 0.0, _ptr(run_mean),
+                             _ptr(run_var), float(decay), float(eps), 1 if training else 0, 1 if relu else 0,
+                             _ptr(ws), _ptr(ctx), _ptr(mask), _stream())
+        _check(rc, "bn_fwd")
     if stats_only:
         return x, ("NATIVE_STATS", x, ctx, False, M, C, None, None)
-    _bnb_request(y, xr, ctx, relu, res, mask, training, dt)
     return y, ("NATIVE", x, ctx, relu, M, C, res, mask)
 
 
@@ -405,67 +401,11 @@ def _bn_fwd_rbn(lib, x, xr, dt, M, C, gamma, beta, run_mean, run_var, decay, eps
     return y, ("NATIVE", x, ctx, True, M, C, res, mask, rctx)
 
 
-# ------------------------------------------------------------------ BN backward sums from the producer's epilogue
-# A training BN layer tags its output with ``_bn_bwd_req = (x rows, ctx, relu, mask)`` (mask: the forward's ReLU
-# bitmask of a layer with a fused residual). The conv / GEMM that consumes that output computes, in the epilogue of its
-# backward-data launch, the BN backward partial sums of the dX it stores (csrc/mfma_tile.h epi_bnbwd_wave; when it sums
-# into another consumer's gradient, of the stored sum) and tags dX with ``_bn_bwd_stats``; bn_bwd then folds those
-# planes (dl4j_bn_bwd_planes) instead of re-reading dy and x in bn_bwd_partial. A later contribution to that gradient
-# (a kernel summing into it drops the tag; a torch sum makes a new, untagged tensor), an in-place edit (version
-# counter), or a layout the kernels do not take leaves no valid tag, and the full backward runs.
-# DL4J_AMD_BN_BWD_EPILOGUE: 0 off (default), 1 plain BN layers only (no fused residual, no fan-out sum), 2 also residual
-# layers and summed gradients (their epilogue reads the old sum and the mask besides x: no less traffic than
-# bn_bwd_partial). Off by default: on the ResNet-50 bench (bf16, batch 512) mode 0 / 1 / 2 measured 31.1k / 30.5k /
-# 29.1k images/s (profiles/r3_bench_bnbmode*.log) — bn_bwd_partial already streams at ~5 TB/s, and the epilogue's
-# exposed load latency costs more than the dy re-read it saves.
-BNB_MODE = int(os.environ.get("DL4J_AMD_BN_BWD_EPILOGUE", "0") or 0)
-BNB = BNB_MODE > 0
-
-
-def _bnb_request(y, xr, ctx, relu, res, mask, training, dt):
-    if BNB and training and (res is None or (mask is not None and BNB_MODE >= 2)) and dt in (1, 2) and \
-            xr.dim() == 2:
-        y._bn_bwd_req = (xr, ctx, bool(relu), mask)
-
-
-class bnb_armed:
-    """Context manager: arms the BN-backward epilogue (dl4j_bnb_arm) for the GEMM / conv launches in its body that
-    pass a statistics buffer; always disarmed on exit."""
-
-    def __init__(self, req):
-        self.req = req
-
-    def __enter__(self):
-        xr, ctx, relu, mask = self.req
-        load().dl4j_bnb_arm(_ptr(xr), _ptr(ctx), _ptr(mask), 3 if mask is not None else (2 if relu else 1))
-        return self
-
-    def __exit__(self, *exc):
-        load().dl4j_bnb_arm(None, None, None, 0)
-        return False
-
-
-def bnb_tag(dx, planes, req):
-    """Marks dx as carrying BN-backward planes for the BN layer whose forward context is req[1]."""
-    dx._bn_bwd_stats = (planes, req[1], planes.shape[1], dx._version)
-
-
-def _bnb_planes(dy, c, res, M, C, mask=None):
-    st = getattr(dy, "_bn_bwd_stats", None)
-    if st is None or (res is not None and mask is None):
-        return None
-    planes, ctx_t, P, ver = st
-    if ctx_t is not c or ver != dy._version or P != (M + 63) // 64 or tuple(planes.shape) != (2, P, C):
-        return None
-    return planes
-
-
 def bn_bwd(dy, ctx, dgamma_out=None, dbeta_out=None, rgrads=None):
     """``rgrads``: (dgamma, dbeta) outputs of the folded-in shortcut BN (ctx from _bn_fwd_rbn); dres is then the
     gradient w.r.t. that BN's input. Returns (dx, dgamma, dbeta, dres) and, with rgrads, fills them."""
     _, x, c, relu, M, C, res, mask = ctx[:8]
     rctx = ctx[8] if len(ctx) > 8 else None
-    planes = _bnb_planes(dy, c, res, M, C, mask) if rctx is None else None
     dy = _rows_like(dy, x)
     lib = load()
     dx = _like_rows(x)
@@ -486,15 +426,6 @@ def bn_bwd(dy, ctx, dgamma_out=None, dbeta_out=None, rgrads=None):
             for dst, src in zip(rgrads, (dg2, db2)):
                 if dst is not None and dst is not src:
                     dst.copy_(src.reshape(dst.shape))
-        return dx, dgamma, dbeta, dres
-    if planes is not None:
-        P = planes.shape[1]
-        ws = _ae((lib.dl4j_bn_bwd_planes_workspace_floats(P, C),), torch.float32, x.device)
-        rc = lib.dl4j_bn_bwd_planes(_dt16(x), _ptr(x), _ptr(dy), _ptr(dx), _ptr(dres), _ptr(mask if dres is not None
-                                                                                               else None), M, C,
-                                    _ptr(c), _ptr(dgamma), _ptr(dbeta), 1 if relu else 0, _ptr(planes), P, _ptr(ws),
-                                    _stream())
-        _check(rc, "bn_bwd_planes")
         return dx, dgamma, dbeta, dres
     ws = _ae((lib.dl4j_bn_workspace_floats(M, C),), torch.float32, x.device)
     rc = lib.dl4j_bn_bwd(_dt16(x), _ptr(x), _ptr(res), _ptr(dy), _ptr(dx), _ptr(dres), M, C, _ptr(c), _ptr(dgamma),
@@ -526,6 +457,8 @@ def bn_pool_fwd(x, gamma, beta, run_mean, run_var, training, decay, eps, kernel,
     xh = _ae((N, C, OH, OW), x.dtype, x.device, channels_last=True) if training else None
     ts = getattr(x, "_bn_tile_stats", None)
     M = N * H * W
+    # not _tile_rpp: chunked partials are taken here only when they tile M exactly (P * rpp == M), there also with a
+    # short last chunk (P == ceil(M / rpp))
     rpp = ts[2] if ts is not None and len(ts) > 2 else 64
     if not (training and ts is not None and dt in (1, 2) and ts[0].shape[2] == C and
             (ts[1] * rpp == M if rpp != 64 else ts[1] == 2 * ((M + 127) // 128))):

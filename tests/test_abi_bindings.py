@@ -18,7 +18,7 @@ I64, U64 = ctypes.c_int64, ctypes.c_uint64
 # hand-written from the C definitions; together they meet every C type the header uses
 EXPECTED = {
     "dl4j_bn_tiles_workspace_floats": ([LL, I], LL),
-    "dl4j_bnb_arm": ([P, P, P, I], None),
+    "rt_threshold_decode": ([P, P, F], None),                     # the void return
     "dl4j_lstm_step_guard": ([], P),
     "dl4j_attn_fwd_drop_dt": ([I, P, P, P, P, I, I, I, I, F, I, F, ULL, P, P], I),
     "dl4j_lstm_fwd_coop": ([P] * 14 + [I, I, I, U, I, P], I),

@@ -85,3 +85,19 @@ def test_cu_count_mismatch_ignores_file_and_forget(tmp_path, fresh):
     fresh.setattr(tunedb, "_db", None)
     fresh.setattr(tunedb, "_cus", lambda: None)       # no device (CPU): the file is used as is
     assert tunedb.lookup("gemm", (1, 2, 3)) == (3, 2)
+
+
+def test_shipped_backward_data_and_statistics_keys_still_hit():
+    """The shipped database stores keys by repr. The stride-1 backward-data keys end in the (constant False) flag of a
+    removed kernel mode and the GEMM statistics keys in ('stats', None); the key builders must reproduce them byte for
+    byte or every such shape re-tunes in its first step. No shipped key may name that mode as switched on."""
+    from deeplearning4j_amd.ops import conv_native
+    with open(tunedb.default_path("gfx950")) as f:
+        tables = json.load(f)["tables"]
+    geo = (1024, 14, 14, 128, 512, 1, 1, 1, 1, 0, 0, 1, 1, 14, 14)
+    assert repr(conv_native._bwd_key(True, geo, torch.bfloat16)) in tables["conv_v3"]
+    assert repr(conv_native._bwd_key(False, geo, torch.bfloat16))[:6] == "('bwd'"
+    bwd = [k for k in tables["conv_v3"] if k.startswith(("('bwd',", "('bwd_acc',"))]
+    assert bwd and all(k.endswith(", False)") for k in bwd)
+    stats = [k for k in tables["gemm"] if "'stats'" in k]
+    assert stats and all(k.endswith(", 'stats', None)") for k in stats)
