@@ -20,14 +20,20 @@
 //    m in the exp2 domain, sum l, unnormalised accumulator) to a workspace and attn_decode_combine_kernel merges
 //    them in the fixed order s = 0 .. S-1 — no atomics, bitwise reproducible for a given split count. A split that
 //    is causally empty for a query leaves (-inf, 0, 0) and is skipped by the merge.
+//  * Ragged batches (prompts of different lengths, right-padded): the host keeps one upper bound pos and a device
+//    array shortfall[b] = what row b lacks against it, written once per sequence. The *_ragged_kernel variants run
+//    the same bodies at pos - shortfall[b]; for a row with at least S key blocks the result is the bits the uniform
+//    kernel gives that row alone at its own position with the same S.
 #include "attention_body.h"
 
 // partial workspace for S splits: acc[((bh*Tn + q)*S + s)*D + d] (16-byte aligned rows), then ml[(bh*Tn + q)*S + s][2]
 // holding (m, l)
+// The body takes the position of its own batch row: the uniform kernel passes the host's pos, the ragged one
+// pos - shortfall[b] (everything below — key-block count, split ranges, causal cut, zero staging — follows from it).
 template <int D, typename hb>
-__global__ void __launch_bounds__(256) attn_decode_kernel(const hb* __restrict__ qkv, const hb* __restrict__ kv,
-                                                          hb* __restrict__ out, float* __restrict__ ws, int Tn, int H,
-                                                          int pos, int Tcap, int S, float scale2) {
+__device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, const hb* __restrict__ kv,
+                                                 hb* __restrict__ out, float* __restrict__ ws, int Tn, int H, int pos,
+                                                 int Tcap, int S, float scale2) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = BLK + 8;
   constexpr int CPR = D / 8, PER = BLK * CPR / 256;              // 16-byte chunks per row / per thread per block
@@ -141,6 +147,25 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const hb* __restrict__
   for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f4_t*>(arow + dt * 16 + hgrp * 4) = acc[dt];
 }
 
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_decode_kernel(const hb* __restrict__ qkv, const hb* __restrict__ kv,
+                                                          hb* __restrict__ out, float* __restrict__ ws, int Tn, int H,
+                                                          int pos, int Tcap, int S, float scale2) {
+  attn_decode_body<D, hb>(qkv, kv, out, ws, Tn, H, pos, Tcap, S, scale2);
+}
+
+// Per-row positions: pos is the host's upper bound (it sizes the grid and the split count S), shortfall[b] what row
+// b lacks against it, clamped into [0, pos]. A row with fewer key blocks than S leaves its upper splits empty:
+// they write the (-inf, 0, 0) partial the merge skips.
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_decode_ragged_kernel(const hb* __restrict__ qkv, const hb* __restrict__ kv,
+                                                                 hb* __restrict__ out, float* __restrict__ ws, int Tn,
+                                                                 int H, int pos, int Tcap, int S, float scale2,
+                                                                 const int* __restrict__ shortfall) {
+  const int b = blockIdx.y / H;
+  attn_decode_body<D, hb>(qkv, kv, out, ws, Tn, H, pos - min(max(shortfall[b], 0), pos), Tcap, S, scale2);
+}
+
 // out[b, q, h*D + d] = sum_s acc_s[d] 2^(m_s - M) / sum_s l_s 2^(m_s - M), M = max_s m_s, in the order s = 0 .. S-1;
 // one thread per (bh, q, 4 consecutive d)
 template <int D, typename hb>
@@ -206,6 +231,22 @@ __global__ void __launch_bounds__(256) attn_kv_append_kernel(const uint4* __rest
   kv[(b * Tcap + pos + t) * (2LL * EC) + c] = qkv[bt * (3LL * EC) + EC + c];
 }
 
+// The same copy to rows [pos - shortfall[b], pos - shortfall[b] + Tn) of batch row b; the shortfall is clamped into
+// [0, pos], so whatever the array holds no write leaves rows [0, pos + Tn) of its own batch row.
+__global__ void __launch_bounds__(256) attn_kv_append_ragged_kernel(const uint4* __restrict__ qkv,
+                                                                    uint4* __restrict__ kv, long long total, int Tn,
+                                                                    int EC, int pos, int Tcap,
+                                                                    const int* __restrict__ shortfall) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % (2 * EC));
+  const long long bt = i / (2 * EC);                             // b*Tn + t
+  const int t = (int)(bt % Tn);
+  const long long b = bt / Tn;
+  const int pb = pos - min(max(shortfall[b], 0), pos);
+  kv[(b * Tcap + pb + t) * (2LL * EC) + c] = qkv[bt * (3LL * EC) + EC + c];
+}
+
 // ------------------------------------------------------------------------------------------------ launch
 // Default split count, from the measurements of tools/bench_decode.py --kernel --sweep (profiles/decode_attention.txt):
 // a block's pass over its key blocks is a chain of dependent memory round trips, so short chains on many blocks win
@@ -249,22 +290,38 @@ DL4J_API long long dl4j_attn_decode_ws_bytes(int B, int Tn, int H, int D, int sp
 // dt: 1 = bf16, 2 = fp16. qkv [B,Tn,3*H*D]; kv [B,Tcap,2*H*D]; pos = tokens already in the cache (host integer, the
 // same for every batch row). Copies the K and V columns of qkv to cache rows [pos, pos+Tn).
 // -1 = unsupported shape / dtype, pos + Tn > Tcap, or operands not 16-byte aligned.
-DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, int Tn, int H, int D, int pos, int Tcap,
-                                    hipStream_t s) {
+// shortfall: null, or int32 [B] on the device: row b is pos - shortfall[b] long instead of pos (clamped into
+// [0, pos]) and its new rows go to [pos - shortfall[b], pos - shortfall[b] + Tn).
+DL4J_API int dl4j_attn_kv_append_ragged_dt(int dt, const void* qkv, void* kv, const int* shortfall, int B, int Tn,
+                                           int H, int D, int pos, int Tcap, hipStream_t s) {
   if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv) return -1;
   if (!attn_aligned16({qkv, kv})) return -1;
   const int EC = H * D / 8;                                      // 16-byte chunks of E columns
   const long long total = (long long)B * Tn * 2 * EC;
-  hipLaunchKernelGGL(attn_kv_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const uint4*)qkv,
-                     (uint4*)kv, total, Tn, EC, pos, Tcap);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (shortfall)
+    hipLaunchKernelGGL(attn_kv_append_ragged_kernel, grid, dim3(256), 0, s, (const uint4*)qkv, (uint4*)kv, total, Tn,
+                       EC, pos, Tcap, shortfall);
+  else
+    hipLaunchKernelGGL(attn_kv_append_kernel, grid, dim3(256), 0, s, (const uint4*)qkv, (uint4*)kv, total, Tn, EC, pos,
+                       Tcap);
   return (int)hipGetLastError();
+}
+
+// Every batch row at pos.
+DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, int Tn, int H, int D, int pos, int Tcap,
+                                    hipStream_t s) {
+  return dl4j_attn_kv_append_ragged_dt(dt, qkv, kv, nullptr, B, Tn, H, D, pos, Tcap, s);
 }
 
 // out [B,Tn,H*D]; rows [0, pos+Tn) of kv are the keys / values (the new rows already appended), query i sees keys
 // <= pos + i. splits >= 1 is clamped to the number of 64-key blocks; ws: fp32 workspace of
 // dl4j_attn_decode_ws_bytes(..., splits) bytes (may be null for one split). -1 = unsupported shape / dtype.
-DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
-                                 int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
+// shortfall: null, or int32 [B] on the device: the keys of row b are rows [0, pos - shortfall[b] + Tn) and its query i
+// sees keys <= pos - shortfall[b] + i. The grid and the split count still follow the upper bound pos.
+DL4J_API int dl4j_attn_decode_ragged_dt(int dt, const void* qkv, const void* kv, void* out, float* ws,
+                                        const int* shortfall, int B, int Tn, int H, int D, int pos, int Tcap,
+                                        int splits, float scale, hipStream_t s) {
   if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv || !out || splits < 1) return -1;
   if (!attn_aligned16({qkv, kv, out, ws})) return -1;
   const int S = decode_clamp_splits(splits, pos + Tn);
@@ -273,8 +330,12 @@ DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* 
     constexpr int DD = decltype(d)::value;
     using hb = typename decltype(e)::type;
     const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
-    hipLaunchKernelGGL((attn_decode_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv, (hb*)out,
-                       ws, Tn, H, pos, Tcap, S, scale * kLog2e);
+    if (shortfall)
+      hipLaunchKernelGGL((attn_decode_ragged_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv,
+                         (hb*)out, ws, Tn, H, pos, Tcap, S, scale * kLog2e, shortfall);
+    else
+      hipLaunchKernelGGL((attn_decode_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv, (hb*)out,
+                         ws, Tn, H, pos, Tcap, S, scale * kLog2e);
     if (S > 1) {
       const long long n = (long long)B * H * Tn * (DD / 4);
       hipLaunchKernelGGL((attn_decode_combine_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
@@ -282,4 +343,10 @@ DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* 
     }
     return (int)hipGetLastError();
   });
+}
+
+// Every batch row at pos.
+DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
+                                 int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
+  return dl4j_attn_decode_ragged_dt(dt, qkv, kv, out, ws, nullptr, B, Tn, H, D, pos, Tcap, splits, scale, s);
 }

@@ -176,18 +176,18 @@ __global__ __launch_bounds__(256) void emb_scatter_kernel(const T* __restrict__ 
 // BERT input embedding: e[r, :] = Wword[idx[r], :] + Wpos[pos0 + r % T, :] + Wtype[0, :] for r = b*T + t, summed in
 // fp32 and rounded once (three gathers and two adds of the imported graph in one pass). Rows are 16-byte vectors.
 // pos0: position of the chunk's first token (0 for a whole sequence, the tokens already seen in rnnTimeStep).
-template <typename T>
-__global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const T* __restrict__ Ww, const T* __restrict__ Wp,
-                                                             const T* __restrict__ Wt,
-                                                             const long long* __restrict__ idx, T* __restrict__ out,
-                                                             int rows, int Tn, int E, long long sw, long long sp,
-                                                             int V, int pos0) {
+// posrow(r): the position-table row of output row r.
+template <typename T, typename PosRow>
+__device__ __forceinline__ void bert_embed_fwd_rows(const T* __restrict__ Ww, const T* __restrict__ Wp,
+                                                    const T* __restrict__ Wt, const long long* __restrict__ idx,
+                                                    T* __restrict__ out, int rows, int E, long long sw, long long sp,
+                                                    int V, PosRow posrow) {
   const int lane = threadIdx.x & 63;
   for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {
     const long long k = idx[r];
     const bool ok = k >= 0 && k < V;
     const T* a = Ww + (ok ? k : 0) * sw;
-    const T* p = Wp + (long long)(pos0 + r % Tn) * sp;
+    const T* p = Wp + (long long)posrow(r) * sp;
     T* dst = out + (long long)r * E;
     for (int c = lane * 8; c < E; c += 512) {
       float va[8], vp[8], vt[8];
@@ -199,6 +199,31 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const T* __restrict
       Vec8<T>::store(dst + c, va);
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const T* __restrict__ Ww, const T* __restrict__ Wp,
+                                                             const T* __restrict__ Wt,
+                                                             const long long* __restrict__ idx, T* __restrict__ out,
+                                                             int rows, int Tn, int E, long long sw, long long sp,
+                                                             int V, int pos0) {
+  bert_embed_fwd_rows<T>(Ww, Wp, Wt, idx, out, rows, E, sw, sp, V, [=](int r) { return pos0 + r % Tn; });
+}
+
+// Ragged batch: row b = r / Tn lacks shortfall[b] tokens against pos0, its positions are pos0 - shortfall[b] + t,
+// clamped into the table's P rows whatever the array holds.
+template <typename T>
+__global__ __launch_bounds__(256) void bert_embed_fwd_ragged_kernel(const T* __restrict__ Ww, const T* __restrict__ Wp,
+                                                                    const T* __restrict__ Wt,
+                                                                    const long long* __restrict__ idx,
+                                                                    T* __restrict__ out, int rows, int Tn, int E,
+                                                                    long long sw, long long sp, int V, int pos0, int P,
+                                                                    const int* __restrict__ shortfall) {
+  bert_embed_fwd_rows<T>(Ww, Wp, Wt, idx, out, rows, E, sw, sp, V, [=](int r) {
+    const int b = r / Tn;
+    const long long p = (long long)pos0 - shortfall[b] + (r - b * Tn);
+    return (int)min(max(p, 0LL), (long long)P - 1);
+  });
 }
 
 // Position / token-type gradients of that sum, deterministic (no atomics):
@@ -400,7 +425,23 @@ DL4J_API int dl4j_bert_embed_fwd_pos(int dt, const void* Ww, const void* Wp, con
   return (int)HIP_LAUNCH_CHECK();
 }
 
-DL4J_API int dl4j_bert_embed_fwd(int dt, const void* Ww, const void* Wp, const void* Wt, const long long* idx,
+// shortfall: null (= dl4j_bert_embed_fwd_pos), or int32 [rows / Tn] on the device: batch row b takes positions
+// pos0 - shortfall[b] + t, clamped into the P rows of Wpos.
+DL4J_API int dl4j_bert_embed_fwd_ragged(int dt, const void* Ww, const void* Wp, const void* Wt, const long long* idx,
+                                        void* out, const int* shortfall, int rows, int Tn, int E, long long sw,
+                                        long long sp, int V, int pos0, int P, hipStream_t s) {
+  if (!shortfall) return dl4j_bert_embed_fwd_pos(dt, Ww, Wp, Wt, idx, out, rows, Tn, E, sw, sp, V, pos0, s);
+  if (rows <= 0) return 0;
+  if (Tn <= 0 || pos0 < 0 || P < 1 || E % 8 || sw % 8 || sp % 8) return -1;
+  for (const void* q : {Ww, Wp, Wt, (const void*)out})
+    if (reinterpret_cast<uintptr_t>(q) & 15) return -1;
+  DISPATCH_T(dt, hipLaunchKernelGGL(bert_embed_fwd_ragged_kernel<T>, dim3(grid_for(rows, 4)), dim3(256), 0, s,
+                                    (const T*)Ww, (const T*)Wp, (const T*)Wt, idx, (T*)out, rows, Tn, E, sw, sp, V,
+                                    pos0, P, shortfall));
+  return (int)HIP_LAUNCH_CHECK();
+}
+
+DL4J_API int dl4j_bert_embed_fwd(int dt,const void* Ww, const void* Wp, const void* Wt, const long long* idx,
                                  void* out, int rows, int Tn, int E, long long sw, long long sp, int V,
                                  hipStream_t s) {
   return dl4j_bert_embed_fwd_pos(dt, Ww, Wp, Wt, idx, out, rows, Tn, E, sw, sp, V, 0, s);

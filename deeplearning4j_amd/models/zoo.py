@@ -961,11 +961,12 @@ class TextGenerationTransformer(ZooModel):
     DEFAULT_SHAPE = [128]
 
     @staticmethod
-    def generate(net, prompt, **cfg):
-        """``net.generate`` for this model: ``prompt`` [mb, Tp] token ids of one common length; ``cfg``:
-        GenerationConfig fields (maxNewTokens, doSample, temperature, topK, topP, numBeams, eosToken, seed, ...).
+    def generate(net, prompt, promptLengths=None, **cfg):
+        """``net.generate`` for this model: ``prompt`` [mb, Tp] token ids of one common length, or right-padded to Tp
+        with ``promptLengths`` [mb] the length of every row; ``cfg``: GenerationConfig fields (maxNewTokens,
+        doSample, temperature, topK, topP, numBeams, eosToken, seed, ...).
         -> GenerationResult(tokens, lengths, scores)."""
-        return net.generate(prompt, **cfg)
+        return net.generate(prompt, promptLengths=promptLengths, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
                  maxPositions=512, learningRate=1e-3, **kw):
@@ -1019,12 +1020,14 @@ class TransformerSeq2Seq(ZooModel):
     DEFAULT_SHAPE = [128, 128]
 
     @staticmethod
-    def generate(net, source, start, sourceMask=None, **cfg):
+    def generate(net, source, start, sourceMask=None, startLengths=None, **cfg):
         """``net.generate`` for this model: ``source`` [mb, Ts] ids, ``start`` [mb, Tp] the first target tokens (e.g.
-        one begin-of-sequence id per row), ``sourceMask`` [mb, Ts] the source padding; ``cfg``: GenerationConfig
-        fields. -> GenerationResult(tokens, lengths, scores)."""
+        one begin-of-sequence id per row), ``sourceMask`` [mb, Ts] the source padding, ``startLengths`` [mb] the
+        length of every row of a right-padded ``start`` (forced prefixes of different lengths); ``cfg``:
+        GenerationConfig fields. -> GenerationResult(tokens, lengths, scores)."""
         masks = None if sourceMask is None else [sourceMask, None]
-        return net.generate(start, others={"source": source}, masks=masks, tokenInput="target", **cfg)
+        return net.generate(start, others={"source": source}, masks=masks, tokenInput="target",
+                            promptLengths=startLengths, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, sourceVocabSize=None, hidden=256, layers=4, heads=4,
                  ffn=None, maxPositions=512, learningRate=1e-3, hiddenDropout=0.0, attentionDropout=0.0, **kw):

@@ -6,7 +6,12 @@ Per generated token the loop runs one device op that turns the next-token distri
 ``rnnReorderState`` (the key/value-cache gather) and one ``rnnTimeStep``. The distribution is read in the network's
 compute dtype, the int64 token tensor the kernel wrote is the next input as it is, and the host reads the device's
 count of unfinished rows only every ``eosCheckEvery`` steps (never without an ``eosToken``): steps run past the point
-where every row finished only produce ``padToken``, so the result does not depend on that interval."""
+where every row finished only produce ``padToken``, so the result does not depend on that interval.
+
+Prompts of different lengths go in right-padded with ``promptLengths``: the prompt runs once on the padded rectangle,
+``rnnTrimState(lengths)`` lets every cached layer continue row b at its own position (a device array of per-row
+shortfalls, written once per sequence), row b's first distribution is read at time step ``lengths[b] - 1`` and the
+loops run unchanged."""
 import collections
 import dataclasses
 from typing import Optional
@@ -81,6 +86,33 @@ def _prompt_tensor(prompt, device):
     return p.to(device=device, dtype=torch.int64)
 
 
+def _lengths_tensor(lengths, mb, what):
+    """``lengths`` as int64 [mb] on the host (the one host read of a ragged batch)."""
+    try:
+        n = torch.as_tensor(lengths).detach().cpu().reshape(-1)
+    except (ValueError, TypeError, RuntimeError) as e:
+        raise DL4JInvalidInputException(f"{what}: lengths must be integers [{mb}]: {e}") from None
+    if n.is_floating_point() or n.dtype == torch.bool or (mb is not None and n.numel() != mb):
+        raise DL4JInvalidInputException(f"{what}: lengths must be integers [{mb}], got {n.dtype} {tuple(n.shape)}")
+    return n.to(torch.int64)
+
+
+def trim_layers(named, lengths):
+    """rnnTrimState of a network over its (label, layer) pairs: the lengths are read once, every layer first only
+    validates (a layer that keeps rnnTimeStep state but cannot trim it refuses), then every layer is trimmed."""
+    n = _lengths_tensor(lengths, None, "rnnTrimState")
+    todo = [(label, l) for label, l in named if hasattr(l, "rnnClearPreviousState")]
+    for dry in (True, False):
+        for label, l in todo:
+            try:
+                if not hasattr(l, "rnnTrimState"):
+                    from .layers.recurrent import cannot_trim
+                    cannot_trim(l)
+                l.rnnTrimState(n, dryRun=dry)
+            except DL4JInvalidInputException as e:
+                raise DL4JInvalidInputException(f"{label}: {e}") from None
+
+
 class _Stepper:
     """Feeds the network: the first call with the prompt (and the other inputs), then one token tensor per call.
     Every call returns the last time step's distribution [rows, V], contiguous, in the compute dtype."""
@@ -119,7 +151,7 @@ class _Stepper:
             self._hot.zero_()
         return self._hot.scatter_(1, ids.reshape(rows, 1, T), 1.0)
 
-    def _run(self, x, first):
+    def _run(self, x, first, last=None):
         if self.graph:
             ins = [None] * len(self.names)
             if first:
@@ -130,12 +162,23 @@ class _Stepper:
             out = self.net._rnn_time_step_raw(*ins, masks=self.masks if first else None)[0]
         else:
             out = self.net._rnn_time_step_raw(x)
+        if last is not None:                                     # ragged prompts: row b's own last time step
+            return out.gather(2, last.reshape(-1, 1, 1).expand(out.shape[0], out.shape[1], 1))[:, :, 0].contiguous()
         return out[:, :, -1].contiguous() if out.dim() == 3 else out.contiguous()
 
-    def first(self, prompt):
+    def first(self, prompt, lengths=None):
+        """``lengths``: None, or int64 [mb] on the host: the prompt is right-padded and row b is that long. The
+        state is trimmed to them after the prefill and row b's distribution comes from time step lengths[b] - 1."""
         if self.cfg.inputEncoding == "onehot":
             self.vocab = _vocab(self.net)
-        return self._run(self._encode(prompt), True)
+        if lengths is None:
+            return self._run(self._encode(prompt), True)
+        p = self._run(self._encode(prompt), True, last=(lengths - 1).to(prompt.device))
+        if self.graph:
+            self.net.rnnTrimState(lengths, self.names[self.tidx])
+        else:
+            self.net.rnnTrimState(lengths)
+        return p
 
     def step(self, tok):
         return self._run(self._encode(tok.reshape(-1, 1)), False)
@@ -156,8 +199,12 @@ def _stream(cfg, device):
     return s
 
 
-def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=False, **configFields):
-    """Generate ``maxNewTokens`` tokens per row of ``prompt`` [mb, Tp] (ids of one common length).
+def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=False, promptLengths=None,
+             **configFields):
+    """Generate ``maxNewTokens`` tokens per row of ``prompt`` [mb, Tp] (ids of one common length, or with
+    ``promptLengths`` [mb] right-padded to Tp with row b that long, 1 <= promptLengths[b] <= Tp; the entries past a
+    row's length must be valid ids and otherwise do not matter: the prompt runs as one padded rectangle, then
+    ``rnnTrimState`` lets every row continue at its own position).
     ``config``: a GenerationConfig, and / or its fields as keywords. ``others``: for a graph, the remaining network
     inputs for the first call (e.g. the source of an encoder-decoder model) by name; ``masks``: as in
     ComputationGraph.rnnTimeStep, for the first call. ``useBeamPath`` runs numBeams == 1 through the beam search.
@@ -172,10 +219,18 @@ def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=Fals
         cfg = dataclasses.replace(cfg, **configFields)
     cfg.validate()
     prompt = _prompt_tensor(prompt, net.device)
+    lengths = None
+    if promptLengths is not None:
+        mb, Tp = prompt.shape
+        lengths = _lengths_tensor(promptLengths, mb, "generate: promptLengths")
+        if int(lengths.min()) < 1 or int(lengths.max()) > Tp:
+            raise DL4JInvalidInputException(
+                f"generate: every prompt length must be in 1..{Tp} (the padded prompt's width), got "
+                f"{lengths.tolist()}")
     stepper = _Stepper(net, cfg, others, masks)
     net.rnnClearPreviousState()
     with torch.no_grad():
-        p = stepper.first(prompt)
+        p = stepper.first(prompt, lengths)
         if int(cfg.numBeams) > 1 or useBeamPath:
             return _beam(net, stepper, p, cfg)
         return _sample(stepper, p, cfg)
@@ -201,7 +256,9 @@ def _sample(stepper, p, cfg):
             break
         p = stepper.step(tokens[t])
     toks = tokens.t().contiguous()
-    return GenerationResult(toks, _lengths(toks, eos), logps.sum(0))
+    # summed in fp64 and rounded once: a row's score does not depend on how many rows the batch has (torch's fp32
+    # column sum picks its order by the shape), so a ragged batch scores every row as the row alone
+    return GenerationResult(toks, _lengths(toks, eos), logps.sum(0, dtype=torch.float64).float())
 
 
 def _lengths(toks, eos):

@@ -778,12 +778,33 @@ class ComputationGraph(BaseNetwork):
             if hasattr(l, "rnnReorderState"):
                 l.rnnReorderState(parents, groupSize)
 
-    def generate(self, prompt, config=None, others=None, masks=None, **configFields):
+    def rnnTrimState(self, lengths, input=None):
+        """The chunk(s) fed to network input ``input`` (a name; default: the last input) since
+        rnnClearPreviousState() were right-padded: row b holds ``lengths[b]`` real tokens (integers [mb],
+        1 <= lengths[b] <= tokens fed). Every layer downstream of that input continues row b at its own position
+        (key/value caches and position embeddings take per-row positions on the device); layers fed only by other
+        inputs (the encoder of an encoder-decoder model) are left alone. Once per sequence. A downstream layer whose
+        stored state cannot be trimmed (LSTM family, SimpleRnn) makes the call raise DL4JInvalidInputException before
+        any layer is changed."""
+        from ..generation import trim_layers
+        names = list(self.conf.networkInputs)
+        src = names[-1] if input is None else input
+        if src not in names:
+            raise DL4JInvalidInputException(f"rnnTrimState: {src!r} is not one of the network inputs {names}")
+        reach = {src}
+        for name in self.topo:
+            if any(i in reach for i in self.vertex_inputs[name]):
+                reach.add(name)
+        trim_layers([(f"vertex {n!r}", self.layers_by_name[n]) for n in self.topo
+                     if n in reach and n in self.layers_by_name], lengths)
+
+    def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, **configFields):
         """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py); ``others``
         maps the remaining network inputs to their arrays for the first call, ``masks`` as in rnnTimeStep.
+        ``promptLengths`` [mb]: the prompts are right-padded to Tp and row b is that long.
         -> GenerationResult(tokens [mb, maxNewTokens], lengths [mb], scores [mb])."""
         from ..generation import generate
-        return generate(self, prompt, config, others, masks, **configFields)
+        return generate(self, prompt, config, others, masks, promptLengths=promptLengths, **configFields)
 
     def rnnGetPreviousState(self, layerName):
         """Stored rnnTimeStep state of one recurrent layer (reference ComputationGraph.rnnGetPreviousState,

@@ -229,6 +229,9 @@ class CrossAttentionLayerImpl(MemoryKVState, LayerImpl):
     def rnnReorderState(self, parents, groupSize=None):
         self.memoryReorder(parents, groupSize)
 
+    def rnnTrimState(self, lengths, dryRun=False):
+        """The stored memory projection does not depend on how long the rows of the own stream are: nothing to do."""
+
     def rnnGetPreviousState(self):
         return self.memoryGet()
 

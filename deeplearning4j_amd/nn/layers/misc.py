@@ -95,5 +95,9 @@ class MaskZeroLayerImpl(LayerImpl):
         if hasattr(self.inner, "rnnReorderState"):
             self.inner.rnnReorderState(parents, groupSize)
 
+    def rnnTrimState(self, lengths, dryRun=False):
+        from .recurrent import forward_trim
+        forward_trim(self.inner, lengths, dryRun)
+
 
 _ = torch

@@ -249,6 +249,23 @@ def _lstm_bwd(eps, cache, W, RW, H, peephole, act, gate_act, mask, tbptt_back, g
     return dx, dh_next, dc_next
 
 
+def cannot_trim(layer):
+    """rnnTrimState on a layer whose step state the padded steps have already changed (a recurrence cannot take them
+    back): always refused, naming the layer."""
+    from ...exceptions import DL4JInvalidInputException
+    raise DL4JInvalidInputException(
+        f"rnnTrimState on layer {layer.index} ({type(layer.conf).__name__}): this layer's rnnTimeStep state cannot be "
+        "trimmed to per-row lengths, the padded time steps have already gone into it; feed rows of one common length")
+
+
+def forward_trim(inner, lengths, dryRun):
+    """rnnTrimState of a wrapper layer: the wrapped layer's, refused where that one keeps state it cannot trim."""
+    if hasattr(inner, "rnnTrimState"):
+        inner.rnnTrimState(lengths, dryRun)
+    elif hasattr(inner, "rnnClearPreviousState"):
+        cannot_trim(inner)
+
+
 class BaseRecurrentImpl(LayerImpl):
     def __init__(self, conf, index=0, net=None):
         super().__init__(conf, index, net)
@@ -261,6 +278,9 @@ class BaseRecurrentImpl(LayerImpl):
     def rnnClearPreviousState(self):
         self.stateMap = {}
         self.tBpttStateMap = {}
+
+    def rnnTrimState(self, lengths, dryRun=False):
+        cannot_trim(self)
 
     def _check_state_mb(self, x):
         """rnnTimeStep continues the stored state, so the minibatch size cannot change between calls without
@@ -643,3 +663,6 @@ class LastTimeStepImpl(LayerImpl):
     def rnnReorderState(self, parents, groupSize=None):
         if hasattr(self.inner, "rnnReorderState"):
             self.inner.rnnReorderState(parents, groupSize)
+
+    def rnnTrimState(self, lengths, dryRun=False):
+        forward_trim(self.inner, lengths, dryRun)

@@ -241,14 +241,29 @@ class KVCacheState:
     """rnnTimeStep state of a causal attention layer: one key/value cache ``kv [mb, Tcap, 2E]`` in the compute dtype
     (K of head h at column h*D, V at E + h*D; the layout of csrc/attention_decode.hip) and the number of valid rows.
     Tcap is a multiple of 64 and grows geometrically, so a steady-state step neither allocates nor copies. The stored
-    state handed out / taken in is ``{"kv": [mb, L, 2E]}`` trimmed to the valid length."""
+    state handed out / taken in is ``{"kv": [mb, L, 2E]}`` trimmed to the valid length.
+
+    Ragged batches: after a right-padded chunk ``rnnTrimState(lengths)`` stores ``short[b] = seen - lengths[b]``
+    (int32 on the cache's device). ``_kv_len`` stays the upper bound the host counts; row b continues at
+    ``_kv_len - short[b]``, overwriting what its padding left in the cache. The state then carries ``"short"``."""
     _kv = None
     _kv_len = 0
     _kv_alt = None      # rnnReorderState's second buffer (same shape as _kv, or None): the two are swapped per call
+    _kv_short = None    # int32 [mb] shortfall of every row against _kv_len (None: every row is _kv_len long)
 
     def rnnClearPreviousState(self):
-        self._kv = self._kv_alt = None
+        self._kv = self._kv_alt = self._kv_short = None
         self._kv_len = 0
+
+    def rnnTrimState(self, lengths, dryRun=False):
+        """The rows of the stored chunk(s) were right-padded: row b holds ``lengths[b]`` real tokens (1 <= lengths[b]
+        <= tokens seen). ``lengths``: integers [mb] (read on the host once, here). Once per sequence; ``dryRun``
+        only validates. A layer without a cache (a bidirectional block) has nothing to trim."""
+        if self._kv is None:
+            return
+        short = _trim_shortfall(self, lengths, self._kv_len, self._kv.shape[0], self._kv_short is not None)
+        if not dryRun:
+            self._kv_short = short.to(self._kv.device)
 
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of the cache becomes the old row ``parents[i]`` (int32 device tensor [mbNew]; mbNew may differ from
@@ -265,11 +280,15 @@ class KVCacheState:
         GN.cache_gather(kv, alt, parents, self._kv_len)
         self._kv_alt = kv if tuple(kv.shape) == shape else None
         self._kv = alt
+        self._kv_short = _reorder_short(self._kv_short, parents, groupSize)
 
     def rnnGetPreviousState(self):
         if self._kv is None:
             return {}
-        return {"kv": self._kv[:, :self._kv_len].clone()}
+        st = {"kv": self._kv[:, :self._kv_len].clone()}
+        if self._kv_short is not None:
+            st["short"] = self._kv_short.clone()
+        return st
 
     def rnnSetPreviousState(self, state):
         kv = state.get("kv") if state else None
@@ -280,6 +299,9 @@ class KVCacheState:
         self._kv_reserve(mb, E2, L, kv.dtype, kv.device)
         self._kv[:, :L] = kv
         self._kv_len = L
+        if state.get("short") is not None:
+            self._kv_short = _trim_shortfall(self, L - torch.as_tensor(state["short"]).cpu().to(torch.int64), L, mb,
+                                             False).to(kv.device)
 
     def _check_state_mb(self, x):
         """rnnTimeStep continues the stored cache, so the minibatch size cannot change between calls without
@@ -312,24 +334,58 @@ class KVCacheState:
         from ...ops import transformer_native as TN
         mb, Tn, E3 = qkv.shape
         E = E3 // 3
-        pos = self._kv_len
+        pos, short = self._kv_len, self._kv_short
         self._kv_reserve(mb, 2 * E, pos + Tn, qkv.dtype, qkv.device)
         kv = self._kv
         out = None
         if _native(qkv, "attention") and qkv.is_contiguous() and TN.attn_decode_supported(qkv, kv, H):
-            if TN.attn_kv_append(qkv, kv, H, pos) is not None:
+            if TN.attn_kv_append(qkv, kv, H, pos, short) is not None:
                 if pos == 0 and Tn >= 64:
                     out = TN.attn_fwd(qkv, H, None, True)[0]
                 else:
-                    out = TN.attn_decode(qkv, kv, H, pos)
+                    out = TN.attn_decode(qkv, kv, H, pos, short=short)
         if out is None:
             if qkv.is_cuda:
                 from ...ops import fallback
                 fallback.record("attention", f"{what} head size {E // H} / dtype {qkv.dtype}: torch reference path")
-            kv[:, pos:pos + Tn] = qkv[:, :, E:]
-            out = TN.attention_decode_reference(qkv[:, :, :E], kv[:, :pos + Tn, :E], kv[:, :pos + Tn, E:], H, pos)
+            if short is None:
+                kv[:, pos:pos + Tn] = qkv[:, :, E:]
+            else:
+                rows = (pos - short.to(torch.int64)).reshape(mb, 1) + torch.arange(Tn, device=kv.device).reshape(1, Tn)
+                kv[torch.arange(mb, device=kv.device).reshape(mb, 1), rows] = qkv[:, :, E:]
+            out = TN.attention_decode_reference(qkv[:, :, :E], kv[:, :pos + Tn, :E], kv[:, :pos + Tn, E:], H, pos,
+                                                short=short)
         self._kv_len = pos + Tn
         return out
+
+
+def _trim_shortfall(layer, lengths, seen, mb, trimmed):
+    """``seen - lengths`` as int32 [mb] on the host for a layer's rnnTrimState, after checking ``lengths`` (integers
+    [mb], 1 <= lengths[b] <= seen) and that the state has not been trimmed already."""
+    from ...exceptions import DL4JInvalidInputException
+    who = f"rnnTrimState on layer {layer.index} ({type(layer.conf).__name__})"
+    if trimmed:
+        raise DL4JInvalidInputException(
+            f"{who}: the state has been trimmed already; call rnnClearPreviousState() to start a new sequence")
+    n = torch.as_tensor(lengths).detach().cpu().reshape(-1)
+    if n.is_floating_point() or n.dtype == torch.bool or n.numel() != mb:
+        raise DL4JInvalidInputException(
+            f"{who}: lengths must be integers [{mb}] (one per row of the stored state), got {n.dtype} "
+            f"{tuple(torch.as_tensor(lengths).shape)}")
+    n = n.to(torch.int64)
+    if n.numel() and (int(n.min()) < 1 or int(n.max()) > seen):
+        raise DL4JInvalidInputException(
+            f"{who}: every length must be in 1..{seen} (the tokens seen since rnnClearPreviousState()), got "
+            f"{n.tolist()}")
+    return (seen - n).to(torch.int32)
+
+
+def _reorder_short(short, parents, groupSize):
+    """rnnReorderState of a shortfall array: row i becomes the old row parents[i]. With ``groupSize`` and an unchanged
+    number of rows nothing moves (the rows of a group share a prompt, so they share its length)."""
+    if short is None or (groupSize is not None and short.shape[0] == parents.numel()):
+        return short
+    return short.index_select(0, parents.to(device=short.device, dtype=torch.int64)).contiguous()
 
 
 def _token_major(x):
@@ -736,33 +792,61 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         copy_grad_(g["Wtype"], gt)
         return self.make_gradient(), None
 
-    def _embed(self, idx, pos):
-        """[B*T, E] = Wword[idx] + Wpos[pos .. pos+T-1] + Wtype[0] in the compute dtype (in-tree kernel on a GPU)."""
+    def _embed(self, idx, pos, short=None):
+        """[B*T, E] = Wword[idx] + Wpos[pos .. pos+T-1] + Wtype[0] in the compute dtype (in-tree kernel on a GPU);
+        with ``short`` (int32 [B]) row b takes the positions from pos - short[b]."""
         from ...ops import nn_misc
         B, T = idx.shape
-        e = nn_misc.bert_embed_forward(self.W("Wword"), self.W("Wpos"), self.W("Wtype"), idx, pos) if idx.is_cuda \
-            else None
+        e = nn_misc.bert_embed_forward(self.W("Wword"), self.W("Wpos"), self.W("Wtype"), idx, pos, short) \
+            if idx.is_cuda else None
         if e is None:
-            e = self.W("Wword")[idx.reshape(-1)] + self.W("Wpos")[pos:pos + T].repeat(B, 1) + \
+            if short is None:
+                wp = self.W("Wpos")[pos:pos + T].repeat(B, 1)
+            else:
+                rows = (pos - short.to(torch.int64)).reshape(B, 1) + torch.arange(T, device=short.device).reshape(1, T)
+                wp = self.W("Wpos")[rows.clamp(0, self.W("Wpos").shape[0] - 1).reshape(-1)]
+            e = self.W("Wword")[idx.reshape(-1)] + wp + \
                 self.W("Wtype")[0].reshape(1, -1)
             e = e.to(self.W("Wword").dtype).contiguous()
         return e
 
-    # rnnTimeStep state: the number of tokens seen so far (and the minibatch size they were seen with)
+    # rnnTimeStep state: the number of tokens seen so far (and the minibatch size they were seen with); after
+    # rnnTrimState the shortfall of every row against that count (int32 [mb] on the device), as in KVCacheState
     _seen = None
+    _short = None
 
     def rnnClearPreviousState(self):
-        self._seen = None
+        self._seen = self._short = None
+
+    def rnnTrimState(self, lengths, dryRun=False):
+        """Row b of what has been fed so far holds ``lengths[b]`` real tokens, right-padded: its next token takes
+        position ``lengths[b]``. Validated on the host, once per sequence; ``dryRun`` only validates."""
+        pos, mb = self._seen if self._seen is not None else (0, torch.as_tensor(lengths).numel())
+        short = _trim_shortfall(self, lengths, pos, mb, self._short is not None)
+        if not dryRun:
+            self._short = short.to(self.params["Wword"].device)
 
     def rnnReorderState(self, parents, groupSize=None):
         if self._seen is not None:
             self._seen = (self._seen[0], int(parents.numel()))
+            self._short = _reorder_short(self._short, parents, groupSize)
 
     def rnnGetPreviousState(self):
-        return {} if self._seen is None else {"pos": self._seen[0], "mb": self._seen[1]}
+        if self._seen is None:
+            return {}
+        st = {"pos": self._seen[0], "mb": self._seen[1]}
+        if self._short is not None:
+            st["short"] = self._short.clone()
+        return st
 
     def rnnSetPreviousState(self, state):
-        self._seen = (int(state["pos"]), int(state["mb"])) if state and "pos" in state else None
+        self.rnnClearPreviousState()
+        if state and "pos" in state:
+            self._seen = (int(state["pos"]), int(state["mb"]))
+            if state.get("short") is not None:
+                n = self._seen[0] - torch.as_tensor(state["short"]).cpu().to(torch.int64)
+                self._short = _trim_shortfall(self, n, self._seen[0], self._seen[1], False) \
+                    .to(self.params["Wword"].device)
 
     def rnnTimeStep(self, x, mask=None):
         """Token ids [mb, Tn] (or [mb, 1, Tn]) embedded at positions pos .. pos+Tn-1, pos = the tokens seen since
@@ -783,7 +867,7 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
                 f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): {pos} tokens seen + {T} new exceed "
                 f"maxPositions {maxp}; call rnnClearPreviousState() to start a new sequence")
         self.training = False
-        e = self._embed(idx, pos)
+        e = self._embed(idx, pos, self._short)
         y, _ = _ln_fwd(e, None, self.params["lng"], self.params["lnb"], self.conf.layerNormEps)
         self._seen = (pos + T, B)
         return y.reshape(B, T, -1).permute(0, 2, 1)

@@ -464,11 +464,21 @@ class MultiLayerNetwork(BaseNetwork):
             if hasattr(l, "rnnReorderState"):
                 l.rnnReorderState(parents, groupSize)
 
-    def generate(self, prompt, config=None, others=None, masks=None, **configFields):
+    def rnnTrimState(self, lengths):
+        """The chunk(s) fed through rnnTimeStep since rnnClearPreviousState() were right-padded: row b holds
+        ``lengths[b]`` real tokens (integers [mb], 1 <= lengths[b] <= tokens fed). From here on every row continues
+        at its own position: key/value caches and position embeddings take per-row positions on the device. Once
+        per sequence. A layer whose stored state cannot be trimmed (LSTM family, SimpleRnn: the padded steps have
+        already gone into it) makes the call raise DL4JInvalidInputException before any layer is changed."""
+        from .generation import trim_layers
+        trim_layers([(f"layer {i}", l) for i, l in enumerate(self.layers)], lengths)
+
+    def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, **configFields):
         """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py).
+        ``promptLengths`` [mb]: the prompts are right-padded to Tp and row b is that long.
         -> GenerationResult(tokens [mb, maxNewTokens], lengths [mb], scores [mb])."""
         from .generation import generate
-        return generate(self, prompt, config, others, masks, **configFields)
+        return generate(self, prompt, config, others, masks, promptLengths=promptLengths, **configFields)
 
     def rnnGetPreviousState(self, layer):
         return self.layers[layer].rnnGetPreviousState()

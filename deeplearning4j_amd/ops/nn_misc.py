@@ -175,20 +175,29 @@ def embedding_backward_(dW, idx, g):
     return dW
 
 
-def bert_embed_forward(Ww, Wp, Wt, idx, pos=0):
+def bert_embed_forward(Ww, Wp, Wt, idx, pos=0, short=None):
     """[B*T, E] = Wword[idx] + Wpos[pos + t] + Wtype[0] for token ids ``idx`` [B, T] in one HIP pass (fp32 sum, one
-    rounding); ``pos``: position of the first token (rnnTimeStep continues a sequence). None when the kernel does not
-    take these operands (the caller sums with torch)."""
+    rounding); ``pos``: position of the first token (rnnTimeStep continues a sequence). ``short``: None, or int32 [B]
+    on the device (ragged batches): row b takes positions pos - short[b] + t, clamped into the table. None when the
+    kernel does not take these operands (the caller sums with torch)."""
     B, T = idx.shape
     E = Ww.shape[1]
     if not (use_native(Ww, "embedding") and _dt(Ww) is not None and Ww.dtype == Wp.dtype == Wt.dtype and
             Ww.dim() == Wp.dim() == Wt.dim() == 2 and Ww.stride(1) == Wp.stride(1) == Wt.stride(1) == 1 and
             pos >= 0 and Wp.shape[0] >= pos + T and Wp.shape[1] == Wt.shape[1] == E):
         return None
+    if short is not None and not (torch.is_tensor(short) and short.dtype == torch.int32 and short.dim() == 1 and
+                                  short.shape[0] == B and short.is_contiguous() and short.device == Ww.device):
+        return None
     fi = idx.reshape(-1).to(torch.int64).contiguous()
     out = torch.empty((B * T, E), dtype=Ww.dtype, device=Ww.device)
-    rc = _lib().dl4j_bert_embed_fwd_pos(_dt(Ww), _p(Ww), _p(Wp), _p(Wt), _p(fi), _p(out), B * T, T, E, Ww.stride(0),
-                                        Wp.stride(0), Ww.shape[0], int(pos), _s())
+    if short is None:
+        rc = _lib().dl4j_bert_embed_fwd_pos(_dt(Ww), _p(Ww), _p(Wp), _p(Wt), _p(fi), _p(out), B * T, T, E,
+                                            Ww.stride(0), Wp.stride(0), Ww.shape[0], int(pos), _s())
+    else:
+        rc = _lib().dl4j_bert_embed_fwd_ragged(_dt(Ww), _p(Ww), _p(Wp), _p(Wt), _p(fi), _p(out), _p(short), B * T, T,
+                                               E, Ww.stride(0), Wp.stride(0), Ww.shape[0], int(pos), Wp.shape[0],
+                                               _s())
     return out if rc == 0 else None
 
 

@@ -10,8 +10,15 @@
              128, batch 1 / 32: greedy, sampling and numBeams=4, against the loop written on the public API before
              generate() existed (rnnTimeStep, torch.multinomial on the device, one .item() eos test per step; that
              loop touches nothing this tool's tree changed). Host clock around work that ends in a device synchronise.
+  --ragged   ragged prompts (per-row cache lengths). (a) the decode-attention kernel with an all-zero shortfall array
+             against the uniform kernel on the same operands, at the shapes of profiles/decode_attention.txt, the
+             variants alternating within every pass; with --parent-lib also against the uniform kernel of a kernel
+             library built from the parent commit. (b) generate(promptLengths=...) on 32 prompts with lengths spread
+             evenly over [Tp/4, Tp] against the same prompts generated one length bucket at a time (rows grouped by
+             their exact length, one generate() per group), same model as --model; the tokens of both are compared.
 
-Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]"""
+Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
+       python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]"""
 import argparse
 import sys
 import time
@@ -149,12 +156,132 @@ def model_mode(batches, n, passes):
     say()
 
 
+def _decode_call(lib, qkv, kv, out, ws, short, B, H, D, pos, splits):
+    """One decode-attention launch straight on a kernel library's C ABI (the uniform entry point when ``short`` is
+    None); argument types set by hand so that a library without the ragged entry point can be driven too."""
+    import ctypes
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    ptr = lambda t: None if t is None else vp(t.data_ptr())      # noqa: E731
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    scale = ctypes.c_float(D ** -0.5)
+    if short is None:
+        f = lib.dl4j_attn_decode_dt
+        f.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
+        return f(1, ptr(qkv), ptr(kv), ptr(out), ptr(ws), B, 1, H, D, pos, kv.shape[1], splits, scale, stream)
+    f = lib.dl4j_attn_decode_ragged_dt
+    f.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
+    return f(1, ptr(qkv), ptr(kv), ptr(out), ptr(ws), ptr(short), B, 1, H, D, pos, kv.shape[1], splits, scale, stream)
+
+
+def ragged_kernel_mode(passes, reps, parent_lib):
+    import ctypes
+    from deeplearning4j_amd.ops import native
+    from deeplearning4j_amd.ops import transformer_native as TN
+    libs = [("uniform", ctypes.CDLL(native.KERNEL_LIB), False), ("zero shortfall", ctypes.CDLL(native.KERNEL_LIB), True)]
+    if parent_lib:
+        libs.insert(0, ("parent uniform", ctypes.CDLL(parent_lib), False))
+    say(f"== attn_decode, Tn = 1, bf16, default splits, GPU time per call in us (mean of {reps} back-to-back launches; "
+        f"median of {passes} passes, min .. max; the variants alternate within a pass)")
+    say("   uniform = this tree's kernel without an array; zero shortfall = the ragged kernel with an all-zero array"
+        + ("; parent uniform = the parent commit's kernel library" if parent_lib else ""))
+    H, D = 12, 64
+    E = H * D
+    for B in (1, 32):
+        for L in (128, 1024, 4096):
+            torch.manual_seed(B + L)
+            pos = L - 1
+            qkv = (torch.randn(B, 1, 3 * E, device=DEV) * 0.8).to(torch.bfloat16)
+            kv = (torch.randn(B, L + 64, 2 * E, device=DEV) * 0.8).to(torch.bfloat16)
+            short = torch.zeros(B, dtype=torch.int32, device=DEV)
+            splits = TN.attn_decode_splits(B, 1, H, D, L)
+            ws = torch.empty(max(1, B * H * splits * (D + 2)), dtype=torch.float32, device=DEV)
+            outs, times = [], [[] for _ in libs]
+            for _, lib, rag in libs:
+                o = torch.empty(B, 1, E, dtype=torch.bfloat16, device=DEV)
+                assert _decode_call(lib, qkv, kv, o, ws, short if rag else None, B, H, D, pos, splits) == 0
+                outs.append(o)
+            torch.cuda.synchronize()
+            same = all(torch.equal(outs[0], o) for o in outs[1:])
+            for _ in range(passes):
+                for i, (_, lib, rag) in enumerate(libs):
+                    o = outs[i]
+                    times[i].append(gpu_time(lambda: _decode_call(lib, qkv, kv, o, ws, short if rag else None, B, H,
+                                                                  D, pos, splits), reps=reps, warmup=3) * 1e3)
+            line = f"B={B:2d} H={H} D={D} L={L:4d} splits={splits:2d}:"
+            med = []
+            for (name, _, _), t in zip(libs, times):
+                t = sorted(t)
+                med.append(t[len(t) // 2])
+                line += f"  {name} {t[len(t) // 2]:7.2f} ({t[0]:.2f} .. {t[-1]:.2f})"
+            line += f"  zero shortfall / uniform {med[-1] / med[-2]:5.3f}x"
+            if parent_lib:
+                line += f"  uniform / parent {med[1] / med[0]:5.3f}x"
+            say(line + f"  outputs bitwise equal: {same}")
+    say()
+
+
+def ragged_model_mode(n, passes):
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, Tp, mb = 77, 128, 32
+    net = TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=768, layers=12, heads=12, maxPositions=512,
+                                    dataType=DataType.BFLOAT16).init(device=DEV)
+    g = torch.Generator().manual_seed(mb)
+    lens = [Tp // 4 + (b * (Tp - Tp // 4)) // (mb - 1) for b in range(mb)]          # 32 .. 128, evenly spread
+    prompt = torch.randint(0, V, (mb, Tp), generator=g)
+    for b, L in enumerate(lens):
+        prompt[b, L:] = 0
+    prompt = prompt.to(DEV)
+    buckets = {}
+    for b, L in enumerate(lens):
+        buckets.setdefault(L, []).append(b)
+    parts = [(torch.tensor(rows, device=DEV), prompt[rows, :L].contiguous()) for L, rows in sorted(buckets.items())]
+    say(f"== generate() on TextGenerationTransformer(768, 12 layers, 12 heads), bf16, V = {V}, greedy, {n} new tokens, "
+        f"{mb} prompts of lengths {lens[0]} .. {lens[-1]} ({len(buckets)} distinct), tokens/s (median of {passes}; "
+        "min .. max), host clock around work that ends in a device synchronise")
+    say(f"   ragged = one generate(promptLengths=...) on the [32, {Tp}] right-padded batch; bucketed = one generate() "
+        "per distinct length on the rows of that length, unpadded; same batch = one generate() on 32 full-length "
+        "prompts (no lengths), the cost of the batch without raggedness")
+
+    def ragged():
+        return net.generate(prompt, promptLengths=lens, maxNewTokens=n)
+
+    def bucketed():
+        toks = torch.empty(mb, n, dtype=torch.int64, device=DEV)
+        for rows, p in parts:
+            toks[rows] = net.generate(p, maxNewTokens=n).tokens
+        return toks
+
+    def full():
+        return net.generate(prompt, maxNewTokens=n)
+
+    a, b = ragged().tokens, bucketed()
+    full()
+    agree = (a == b).all(1).float().mean().item()
+    say(f"   rows whose {n} tokens are the same in both: {agree * 100:.1f} % (bf16: batch-size dependent GEMM kernels "
+        "may flip near-ties)")
+    tr, tb, tf = [], [], []
+    for _ in range(passes):
+        tr.append(_sync_time(ragged))
+        tb.append(_sync_time(bucketed))
+        tf.append(_sync_time(full))
+    tr, tb, tf = sorted(tr), sorted(tb), sorted(tf)
+    m = passes // 2
+    for name, t in (("ragged", tr), ("bucketed", tb), ("same batch, no lengths", tf)):
+        say(f"{name:24s}: {mb * n / t[m]:9.1f} ({mb * n / t[-1]:.1f} .. {mb * n / t[0]:.1f}) tok/s  "
+            f"{t[m] * 1e3:8.1f} ms per batch")
+    say(f"bucketed / ragged time: {tb[m] / tr[m]:5.2f}x   ragged / same batch time: {tr[m] / tf[m]:5.3f}x")
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sampler", action="store_true")
     ap.add_argument("--gather", action="store_true")
     ap.add_argument("--model", action="store_true")
+    ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--parent-lib", default=None, help="kernel library built from the parent commit (--ragged)")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--passes", type=int, default=5)
@@ -170,6 +297,9 @@ def main():
         gather_mode(a.passes, a.reps)
     if a.model:
         model_mode(a.batch, a.tokens, a.passes)
+    if a.ragged:
+        ragged_kernel_mode(a.passes, max(a.reps, 50), a.parent_lib)
+        ragged_model_mode(a.tokens, a.passes)
 
 
 if __name__ == "__main__":
