@@ -263,6 +263,139 @@ __global__ __launch_bounds__(256) void bn_apply(const T* __restrict__ x, const T
 }
 
 // -------------------------------------------------------------------------------------------- backward
+// Reduction tail of bn_bwd_partial (layers without a residual): the blocks finish the reduction themselves, so no
+// bn_fold launch sits between the partial pass and the apply pass. Two levels, because one last block reading all
+// nblk x C partials would read serially for longer than the launch it replaces:
+//   - BN_TAIL_G = 128 consecutive blocks form a group. Every block stores its row write-through (agent-scope relaxed
+//     atomic stores), drains them (vmcnt(0) in every wave, then a barrier) and draws from the group's ticket. The last
+//     arriver folds the group's rows over all C channels in float into one folded row;
+//   - it then draws from the launch's top-level ticket, and the last group-folder sums the <= 16 folded rows in double
+//     and writes dbeta / dgamma and the means.
+// A block that is not last returns at once: nothing waits, spins or polls, so the tail cannot hang whatever the
+// residency. The sums run in exactly bn_fold's order (a group is one bn_fold block of 128 rows: 16 interleaved row
+// groups in float, summed in group order; folded rows in row order in double), so the result is bitwise what the
+// separate launch gives, on every launch. The last arriver resets its counter, so a slot needs no memset and a slot
+// address baked into a captured graph stays valid on every replay. Memory ordering is bn_fold's: write-through
+// stores, drain, relaxed agent-scope fetch_add; the last arriver issues one agent-scope acquire and then reads with
+// plain loads.
+constexpr int BN_TAIL_G = 128;                          // partial rows per group = bn_fold's rows per block
+constexpr int BN_TAIL_TICKETS = 2048 / BN_TAIL_G + 1;   // per launch: [0] top level, [1 + g] group g (nblk <= 2048)
+
+struct BnBwdTail {
+  unsigned* ticket;                        // BN_TAIL_TICKETS counters; null: no tail (bn_fold is launched instead)
+  float* fold_db; float* fold_dg;          // [ceil(nblk / BN_TAIL_G), C] folded rows
+  long long M;
+  float* dbeta; float* dgamma;             // optional
+  float* cdb; float* cdg;                  // mean(d), mean(d * xhat): what the apply pass reads
+};
+
+typedef __attribute__((address_space(1))) unsigned bn_gq32;
+
+__device__ __forceinline__ void bn_st_wt(float* p, float v) {
+  __hip_atomic_store((bn_gq32*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Arrival of a block at a counter that n blocks draw from; true (in every thread) in the last arriver, which has then
+// acquired the other arrivers' write-through stores. lds: the kernel's existing LDS array carries "I am last".
+__device__ __forceinline__ bool bn_tail_arrive(unsigned* cnt, unsigned n, float* lds) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();                                   // every wave's stores drained; lds no longer read
+  if (threadIdx.x == 0) {
+    bool last = true;
+    if (n > 1) {
+      last = __hip_atomic_fetch_add((bn_gq32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n - 1;
+      if (last) __hip_atomic_store((bn_gq32*)cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (last) {
+      // one acquire for the block, then PLAIN loads that can all be in flight together
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    lds[0] = last ? 1.f : 0.f;
+  }
+  __syncthreads();
+  const bool last = lds[0] != 0.f;
+  __syncthreads();                                   // lds[0] read by every wave before the array is reused
+  return last;
+}
+
+__device__ __forceinline__ void bn_bwd_fin(int c, double a, double b, const BnBwdTail& t) {
+  if (t.dbeta) t.dbeta[c] = (float)a;
+  if (t.dgamma) t.dgamma[c] = (float)b;
+  t.cdb[c] = (float)(a / (double)t.M);
+  t.cdg[c] = (float)(b / (double)t.M);
+}
+
+// Called by every thread of the block once its partial row is stored (bn_st_wt) to part_db / part_dg[blockIdx.x].
+// rf: >= 2048 floats of LDS, free for reuse after the next barrier.
+__device__ __forceinline__ void bn_bwd_tail(const float* part_db, const float* part_dg, int C, float* rf,
+                                            const BnBwdTail& t) {
+  const int nb = gridDim.x, S = (nb + BN_TAIL_G - 1) / BN_TAIL_G, grp = blockIdx.x / BN_TAIL_G;
+  const int rbeg = grp * BN_TAIL_G, rend = rbeg + BN_TAIL_G < nb ? rbeg + BN_TAIL_G : nb;
+  if (!bn_tail_arrive(t.ticket + 1 + grp, rend - rbeg, rf)) return;
+  // the group's rows, 64 channels per trip, as one bn_fold block folds them: lane q = tid & 15 owns channels
+  // 4q..4q+3, row group g = tid >> 4 sums rows g, g+16, ... (8 rows x 2 arrays of float4 in flight), then the 16 row
+  // groups are summed in order through LDS
+  const int lq = threadIdx.x & 15, rg = threadIdx.x >> 4, ch = threadIdx.x & 63;
+  for (int c0 = 0; c0 < C; c0 += 64) {
+    const int c = c0 + 4 * lq;
+    float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) {                                       // C % 4 == 0 (C % 8 == 0 is host-checked)
+      float4 va[8], vb[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int r = rbeg + rg + 16 * u;
+        const long long o = (long long)(r < rend ? r : rbeg) * C + c;   // clamped: the loads never branch
+        va[u] = *reinterpret_cast<const float4*>(part_db + o);
+        vb[u] = *reinterpret_cast<const float4*>(part_dg + o);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool ok = rbeg + rg + 16 * u < rend;
+        sa[0] += ok ? va[u].x : 0.f; sa[1] += ok ? va[u].y : 0.f; sa[2] += ok ? va[u].z : 0.f; sa[3] += ok ? va[u].w : 0.f;
+        sb[0] += ok ? vb[u].x : 0.f; sb[1] += ok ? vb[u].y : 0.f; sb[2] += ok ? vb[u].z : 0.f; sb[3] += ok ? vb[u].w : 0.f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      rf[rg * 64 + 4 * lq + j] = sa[j];
+      rf[1024 + rg * 64 + 4 * lq + j] = sb[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 64 && c0 + ch < C) {
+      float ta = 0.f, tb = 0.f;
+#pragma unroll
+      for (int g = 0; g < 16; ++g) { ta += rf[g * 64 + ch]; tb += rf[1024 + g * 64 + ch]; }
+      if (S == 1) {
+        bn_bwd_fin(c0 + ch, (double)ta, (double)tb, t);
+      } else {
+        bn_st_wt(t.fold_db + (long long)grp * C + c0 + ch, ta);
+        bn_st_wt(t.fold_dg + (long long)grp * C + c0 + ch, tb);
+      }
+    }
+    __syncthreads();                                   // rf read before the next trip overwrites it
+  }
+  if (S == 1) return;
+  if (!bn_tail_arrive(t.ticket, S, rf)) return;
+  // the S <= 16 folded rows, in row order, in double (what bn_fold's reducer computes)
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float va[16], vb[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const long long o = (long long)(i < S ? i : 0) * C + c;
+      va[i] = t.fold_db[o];
+      vb[i] = t.fold_dg[o];
+    }
+    double a = 0.0, b = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      a += i < S ? (double)va[i] : 0.0;
+      b += i < S ? (double)vb[i] : 0.0;
+    }
+    bn_bwd_fin(c, a, b, t);
+  }
+}
+
 // RBN: the residual is the raw shortcut-conv output and its BN (rctx) was applied inside bn_apply: the same masked
 // d also feeds that BN's backward, so its sums sum(d) (= db) and sum(d * xhat_r) (part_dg2) come from this pass too.
 template <typename T, bool RELU, bool RES, bool RBN = false>
@@ -271,7 +404,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ x, c
                                                       long long rows_per_blk, const float* __restrict__ ctx,
                                                       float* __restrict__ part_db, float* __restrict__ part_dg,
                                                       const unsigned char* __restrict__ mask,
-                                                      const float* __restrict__ rctx, float* __restrict__ part_dg2) {
+                                                      const float* __restrict__ rctx, float* __restrict__ part_dg2,
+                                                      BnBwdTail tail) {
   const int T8 = C >> 3;
   const int R = 256 / T8;
   const int cg = threadIdx.x % T8, r0 = threadIdx.x / T8;
@@ -344,9 +478,10 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ x, c
       r = r2;
     }
   }
-  __shared__ float red1[256 * 9];   // row pitch 9 floats: conflict-free 8-float stores
+  __shared__ float red1[256 * 9];   // row pitch 9 floats: conflict-free 8-float stores; reused by the tail
   __shared__ float red2[256 * 9];
   __shared__ float red3[RBN ? 256 * 9 : 1];
+  const bool has_tail = !RES && tail.ticket != nullptr;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     red1[threadIdx.x * 9 + i] = (r0 < R) ? db[i] : 0.f;
@@ -362,9 +497,17 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ x, c
       b += red2[(rr * T8 + g) * 9 + k];
       if (RBN) e += red3[(rr * T8 + g) * 9 + k];
     }
-    part_db[(long long)blockIdx.x * C + c] = a;
-    part_dg[(long long)blockIdx.x * C + c] = b;
-    if (RBN) part_dg2[(long long)blockIdx.x * C + c] = e;
+    if (has_tail) {
+      bn_st_wt(part_db + (long long)blockIdx.x * C + c, a);
+      bn_st_wt(part_dg + (long long)blockIdx.x * C + c, b);
+    } else {
+      part_db[(long long)blockIdx.x * C + c] = a;
+      part_dg[(long long)blockIdx.x * C + c] = b;
+      if (RBN) part_dg2[(long long)blockIdx.x * C + c] = e;
+    }
+  }
+  if constexpr (!RES) {
+    if (has_tail) bn_bwd_tail(part_db, part_dg, C, red1, tail);
   }
 }
 
@@ -581,19 +724,25 @@ __global__ __launch_bounds__(256) void bn_fold(const float* __restrict__ p1, con
 // Ticket slots for bn_fold: 256 launches in flight x 32 channel columns (C <= 2048), one array per device.
 __device__ unsigned g_bn_ticket[256 * 32];
 
-static unsigned* bn_ticket_slot() {
-  static unsigned* base[64] = {nullptr};
-  static unsigned next = 0;
+// Ticket slots of bn_bwd_partial's tail: 256 launches in flight x BN_TAIL_TICKETS counters, one array per device.
+__device__ unsigned g_bn_tail_ticket[256 * BN_TAIL_TICKETS];
+
+// A pool's next slot of `stride` counters, drawn round-robin over its 256 slots (every counter is back at zero when
+// its launch ends, so a slot is reused without a memset).
+struct BnTicketPool { unsigned* base[64]; unsigned next; };
+static BnTicketPool g_bn_ticket_pool, g_bn_tail_ticket_pool;
+
+static unsigned* bn_ticket_slot(BnTicketPool& pool, const void* symbol, int stride) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
   if (dev < 0 || dev >= 64) return nullptr;
-  if (!base[dev]) {
+  if (!pool.base[dev]) {
     void* p = nullptr;
-    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_bn_ticket)) != hipSuccess) return nullptr;
-    base[dev] = (unsigned*)p;
+    if (hipGetSymbolAddress(&p, symbol) != hipSuccess) return nullptr;
+    pool.base[dev] = (unsigned*)p;
   }
-  const unsigned k = __atomic_fetch_add(&next, 1u, __ATOMIC_RELAXED) % 256u;
-  return base[dev] + 32 * k;
+  const unsigned k = __atomic_fetch_add(&pool.next, 1u, __ATOMIC_RELAXED) % 256u;
+  return pool.base[dev] + stride * k;
 }
 
 // Launches bn_fold over `nrows` partial rows; q: >= 2*ceil(nrows/32)*C floats of workspace.
@@ -612,7 +761,7 @@ static int bn_fold_launch(const float* p1, const float* p2, long long nrows, int
   if (S > 65535) return -1;
   f.ticket = nullptr;
   if (S > 1) {
-    f.ticket = bn_ticket_slot();
+    f.ticket = bn_ticket_slot(g_bn_ticket_pool, HIP_SYMBOL(g_bn_ticket), 32);
     if (!f.ticket) return -2;
   }
   hipLaunchKernelGGL((bn_fold<T, SRC, FIN>), dim3((C + 63) / 64, (unsigned)S), dim3(256), 0, s, p1, p2, nrows, C, q,
@@ -904,10 +1053,22 @@ static int bn_bwd_impl(const T* x, const T* res, const T* dy, T* dx, T* dres, lo
   float* q = p2 + (long long)nblk * C;
   float* cdb = q + 2LL * ((nblk + 31) / 32) * C;
   float* cdg = cdb + C;
+  // Layers without a residual finish the reduction inside bn_bwd_partial (bn_bwd_tail) while a group's 128 rows of both
+  // arrays are at most 512 KB for its one folding block (C <= 512); the result is bitwise the launch's. Measured on
+  // the ResNet-50 step (profiles/bn_bwd_tail.txt): there the separate fold waits 43-52 us for CU slots behind the
+  // side stream's weight-gradient workgroups, while behind the long residual kernels it runs in 7-16 us and an
+  // in-kernel tail measured 9-19 us slower than that, so residual layers (and wider rows, not measured) keep the launch.
+  BnBwdTail tail{nullptr, q, q + (long long)((nblk + BN_TAIL_G - 1) / BN_TAIL_G) * C, M, dbeta, dgamma, cdb, cdg};
+  if (!res && C <= 512) {
+    tail.ticket = bn_ticket_slot(g_bn_tail_ticket_pool, HIP_SYMBOL(g_bn_tail_ticket), BN_TAIL_TICKETS);
+    if (!tail.ticket) return -2;
+  }
   BN_DISPATCH3(bn_bwd_partial, T, relu, res, dim3(nblk), dim3(256), 0, s, x, res, dy, M, C, rpb, ctx, p1, p2, mask,
-               (const float*)nullptr, (float*)nullptr);
-  const int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, bn_fin_bwd(M, dbeta, dgamma, cdb, cdg), s);
-  if (rc) return rc;
+               (const float*)nullptr, (float*)nullptr, tail);
+  if (!tail.ticket) {
+    const int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, bn_fin_bwd(M, dbeta, dgamma, cdb, cdg), s);
+    if (rc) return rc;
+  }
   BN_DISPATCH3(bn_bwd_apply, T, relu, res, dim3(apply_grid(M, C)), dim3(256), 0, s, x, res, dy, dx, dres, M, C, ctx,
                cdb, cdg, mask, (const float*)nullptr, (const float*)nullptr);
   return (int)hipGetLastError();
@@ -938,7 +1099,7 @@ static int bn_bwd_rbn_impl(const T* x, const T* res, const T* dy, T* dx, T* dres
   float* cdb2 = cdg + C;
   float* cdg2 = cdb2 + C;
   hipLaunchKernelGGL((bn_bwd_partial<T, true, true, true>), dim3(nblk), dim3(256), 0, s, x, res, dy, M, C, rpb, ctx, p1,
-                     p2, mask, rctx, p3);
+                     p2, mask, rctx, p3, BnBwdTail{});
   int rc = bn_fold_launch<T, 0, 1>(p1, p2, nblk, C, q, bn_fin_bwd(M, dbeta, dgamma, cdb, cdg), s);
   if (rc) return rc;
   rc = bn_fold_launch<T, 0, 1>(p1, p3, nblk, C, q2, bn_fin_bwd(M, dbeta2, dgamma2, cdb2, cdg2), s);
