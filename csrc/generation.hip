@@ -483,6 +483,34 @@ __global__ void __launch_bounds__(256) gen_backtrack_kernel(const long long* __r
   }
 }
 
+// ------------------------------------------------------------------------------------------------- step commit
+// The end of one pinned generation step (nn/generation.py): every row's shortfall against the pinned capacity drops
+// by one (not below 0), so the next step's ragged append / attention / embedding run one position further with the
+// same launch arguments; with ``step`` the token and log-probability the sampler staged are filed as row *step of
+// the [N, rows] result buffers (nothing once *step >= N). The counter is read here by every thread and bumped by
+// gen_commit_bump_kernel, the next launch on the stream, so no thread can see the new value.
+__global__ void __launch_bounds__(256) gen_commit_kernel(int* __restrict__ shortfall, int mb,
+                                                         const int* __restrict__ step,
+                                                         const long long* __restrict__ stok,
+                                                         const float* __restrict__ slogp,
+                                                         long long* __restrict__ tokens, float* __restrict__ logps,
+                                                         int rows, int N) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (shortfall && i < mb) shortfall[i] = max(shortfall[i] - 1, 0);
+  if (step && i < rows) {
+    const int t = *step;
+    if (t >= 0 && t < N) {
+      tokens[(long long)t * rows + i] = stok[i];
+      logps[(long long)t * rows + i] = slogp[i];
+    }
+  }
+}
+
+__global__ void gen_commit_bump_kernel(int* __restrict__ step, int N) {
+  const int t = *step;
+  if (t >= 0 && t < N) *step = t + 1;
+}
+
 // ------------------------------------------------------------------------------------------------------ launch
 static int gen_count_l(const unsigned char* fin, int n, int* count, long long* advance, hipStream_t s) {
   if (!count && !advance) return (int)hipGetLastError();
@@ -570,5 +598,25 @@ DL4J_API int dl4j_gen_beam_backtrack(const long long* toks, const int* parents, 
   if (!toks || !parents || !best || !out || B < 1 || W < 1 || W > 16 || N < 1) return -1;
   if ((long long)B * W * N >= (1LL << 31)) return -1;
   hipLaunchKernelGGL(gen_backtrack_kernel, dim3((B + 255) / 256), dim3(256), 0, s, toks, parents, best, out, B, W, N);
+  return (int)hipGetLastError();
+}
+
+// One pinned generation step's bookkeeping, with constant arguments: shortfall[b] = max(shortfall[b] - 1, 0) for
+// b < mb (shortfall: int32 [mb], or null with mb == 0: off); with ``step`` (a device int32 word, null = off) the
+// staged stok int64 [rows] / slogp fp32 [rows] go to tokens[*step, :] / logps[*step, :] of the [N, rows] buffers and
+// *step becomes *step + 1; nothing is written and the counter stays once *step >= N.
+// -1 = nothing to do, a shortfall without rows, a record part with a null pointer or rows / N < 1.
+DL4J_API int dl4j_gen_step_commit(int* shortfall, int mb, int* step, const long long* stok, const float* slogp,
+                                  long long* tokens, float* logps, int rows, int N, hipStream_t s) {
+  if (!shortfall && !step) return -1;
+  if (shortfall ? mb < 1 : mb != 0) return -1;
+  if (step && (!stok || !slogp || !tokens || !logps || rows < 1 || N < 1)) return -1;
+  if (!step) rows = 0;
+  const int n = mb > rows ? mb : rows;
+  hipLaunchKernelGGL(gen_commit_kernel, dim3((n + 255) / 256), dim3(256), 0, s, shortfall, mb, step, stok, slogp,
+                     tokens, logps, rows, N);
+  const int rc = (int)hipGetLastError();
+  if (rc || !step) return rc;
+  hipLaunchKernelGGL(gen_commit_bump_kernel, dim3(1), dim3(1), 0, s, step, N);
   return (int)hipGetLastError();
 }

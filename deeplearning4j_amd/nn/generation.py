@@ -11,7 +11,14 @@ where every row finished only produce ``padToken``, so the result does not depen
 Prompts of different lengths go in right-padded with ``promptLengths``: the prompt runs once on the padded rectangle,
 ``rnnTrimState(lengths)`` lets every cached layer continue row b at its own position (a device array of per-row
 shortfalls, written once per sequence), row b's first distribution is read at time step ``lengths[b] - 1`` and the
-loops run unchanged."""
+loops run unchanged.
+
+Graph-replayed decoding (``pinPositions`` / ``useGraph``, sampling and greedy only): after the prompt
+``rnnPinState(Tp + maxNewTokens)`` fixes the host's bound at the capacity and lets that device array carry the
+positions, the sampler writes a staging row and the time step ends with one commit launch (``dl4j_gen_step_commit``)
+that lowers every shortfall and files the staging row under a device step counter. Every step then has the same
+launch arguments; ``useGraph`` runs it eagerly once, captures it into a HIP graph (nn/hipgraph.py) and replays it,
+with the eos read staying on the host between replays. The graph lives for the call."""
 import collections
 import dataclasses
 from typing import Optional
@@ -31,7 +38,10 @@ class GenerationConfig:
     it the result is a pure function of (parameters, prompt, config); None draws one from torch's generator.
     eosCheckEvery: steps between host reads of the device's unfinished count. inputEncoding: "ids" (token ids
     [mb, T]) or "onehot" ([mb, V, T], built on the device). tokenInput: for a graph, the network input that carries
-    the generated stream (default: the last one)."""
+    the generated stream (default: the last one). pinPositions: after the prompt the network's state is pinned
+    (``rnnPinState``) so that every step has the same launch arguments: positions advance on the device, the sampler
+    writes a staging row and one commit launch per step files it (not with numBeams > 1). useGraph: pinPositions, and
+    the step is captured once into a HIP graph and replayed (GPU only)."""
     maxNewTokens: int = 16
     doSample: bool = False
     temperature: float = 1.0
@@ -45,6 +55,8 @@ class GenerationConfig:
     eosCheckEvery: int = 16
     inputEncoding: str = "ids"
     tokenInput: Optional[str] = None
+    pinPositions: bool = False
+    useGraph: bool = False
 
     def validate(self):
         def bad(msg):
@@ -67,6 +79,9 @@ class GenerationConfig:
             bad(f'inputEncoding must be "ids" or "onehot", got {self.inputEncoding!r}')
         if self.eosToken is not None and int(self.eosToken) < 0:
             bad(f"eosToken must be >= 0 or None, got {self.eosToken}")
+        for f in ("useGraph", "pinPositions"):
+            if getattr(self, f) and int(self.numBeams) > 1:
+                bad(f"{f} cannot be combined with numBeams > 1 (beam search reorders the caches every step)")
         return self
 
 
@@ -111,6 +126,86 @@ def trim_layers(named, lengths):
                 l.rnnTrimState(n, dryRun=dry)
             except DL4JInvalidInputException as e:
                 raise DL4JInvalidInputException(f"{label}: {e}") from None
+
+
+def _labelled(label, fn, *a, **kw):
+    try:
+        return fn(*a, **kw)
+    except DL4JInvalidInputException as e:
+        raise DL4JInvalidInputException(f"{label}: {e}") from None
+
+
+def pinnable_layers(named):
+    """The (label, layer) pairs that keep rnnTimeStep state; a layer among them that cannot be pinned (LSTM family,
+    SimpleRnn, a wrapper around one) refuses, naming itself, before anything is changed."""
+    todo = [(label, l) for label, l in named if hasattr(l, "rnnClearPreviousState")]
+    for label, l in todo:
+        if not hasattr(l, "rnnPinState"):
+            from .layers.recurrent import cannot_pin
+            _labelled(label, cannot_pin, l)
+    return todo
+
+
+def pin_layers(net, named, capacity):
+    """rnnPinState of a network over its (label, layer) pairs: every layer is validated, then every layer is pinned
+    to ``capacity`` with one shared device array ``short[b] = capacity - 1 - len_b`` (len_b: the tokens row b holds).
+    ``net._rnn_pin`` keeps that array and the host's count of the steps left, ``capacity - max_b len_b``."""
+    capacity = int(capacity)
+    if net._rnn_pin is not None:
+        raise DL4JInvalidInputException("rnnPinState: the state is pinned already; call rnnClearPreviousState() to "
+                                        "start a new sequence")
+    live = [(label, l, l.rnnPinInfo()) for label, l in pinnable_layers(named)]
+    live = [(label, l, i) for label, l, i in live if i is not None]
+    if not live:
+        raise DL4JInvalidInputException("rnnPinState: no layer holds rnnTimeStep state; call it after the prompt has "
+                                        "gone through rnnTimeStep")
+    seen, mb, first = live[0][2]
+    for label, l, (s, m, sh) in live:
+        if (s, m, sh is None) != (seen, mb, first is None):
+            raise DL4JInvalidInputException(
+                f"rnnPinState: {label} has seen {s} tokens in {m} rows ({'un' if sh is None else ''}trimmed), "
+                f"{live[0][0]} {seen} in {mb} ({'un' if first is None else ''}trimmed); one position array cannot "
+                "serve both")
+        _labelled(label, l.rnnPinState, capacity, None, dryRun=True)
+    dev = net.device
+    if first is None:
+        longest = seen
+        short = torch.full((mb,), capacity - 1 - seen, dtype=torch.int32, device=dev)
+    else:
+        st = torch.stack([sh.to(dev) for _, _, (_, _, sh) in live])
+        differ, least = torch.stack([(st != st[0]).any().to(torch.int32), st[0].min()]).tolist()   # the one host read
+        if differ:
+            raise DL4JInvalidInputException("rnnPinState: the layers' per-row lengths differ; one position array "
+                                            "cannot serve them all")
+        longest = seen - int(least)
+        short = (st[0] + (capacity - 1 - seen)).to(torch.int32).contiguous()
+    for label, l, _ in live:
+        l.rnnPinState(capacity, short)
+    net._rnn_pin = {"short": short, "left": capacity - longest, "capacity": capacity, "record": None}
+
+
+def pin_step_begin(net):
+    """Before a pinned network's time step: refuse, with nothing launched, when the capacity is used up."""
+    pin = net._rnn_pin
+    if pin["left"] < 1:
+        raise DL4JInvalidInputException(
+            f"rnnTimeStep: the pinned state's capacity of {pin['capacity']} positions is used up; call "
+            "rnnClearPreviousState() to start a new sequence")
+
+
+def pin_step_commit(net):
+    """After a pinned network's last layer: the one launch that moves every layer one position on (and files the
+    staged token of a generate() call)."""
+    from ..ops import generation_native as GN
+    pin = net._rnn_pin
+    GN.step_commit(pin["short"], pin["record"])
+    pin["left"] -= 1
+
+
+def refuse_pinned(net, what):
+    if net._rnn_pin is not None:
+        raise DL4JInvalidInputException(f"{what}: the state is pinned (rnnPinState), its positions advance on the "
+                                        "device; call rnnClearPreviousState() first")
 
 
 class _Stepper:
@@ -183,6 +278,18 @@ class _Stepper:
     def step(self, tok):
         return self._run(self._encode(tok.reshape(-1, 1)), False)
 
+    def token_layers(self):
+        """(label, layer) of the layers the generated stream runs through."""
+        if self.graph:
+            return self.net._layers_downstream(self.names[self.tidx], "generate")
+        return [(f"layer {i}", l) for i, l in enumerate(self.net.layers)]
+
+    def pin(self, capacity):
+        if self.graph:
+            self.net.rnnPinState(capacity, self.names[self.tidx])
+        else:
+            self.net.rnnPinState(capacity)
+
 
 def _vocab(net):
     layer = net.layers_by_name[net.outputs[0]] if hasattr(net, "layers_by_name") else net.layers[-1]
@@ -208,6 +315,8 @@ def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=Fals
     ``config``: a GenerationConfig, and / or its fields as keywords. ``others``: for a graph, the remaining network
     inputs for the first call (e.g. the source of an encoder-decoder model) by name; ``masks``: as in
     ComputationGraph.rnnTimeStep, for the first call. ``useBeamPath`` runs numBeams == 1 through the beam search.
+    With ``pinPositions`` / ``useGraph`` the network stays pinned afterwards (``rnnClearPreviousState()`` unpins) and
+    ``net.lastGenerationStats`` tells how the steps ran: {"captures", "graphReplays", "eagerSteps"}.
     -> GenerationResult(tokens int64 [mb, maxNewTokens], lengths int64 [mb] (up to and including eos),
     scores fp32 [mb] (the sum of the chosen tokens' log-probabilities; for beam search divided by
     length**lengthPenalty))."""
@@ -218,6 +327,7 @@ def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=Fals
             raise DL4JInvalidConfigException(f"GenerationConfig has no field(s) {unknown}")
         cfg = dataclasses.replace(cfg, **configFields)
     cfg.validate()
+    net.lastGenerationStats = None
     prompt = _prompt_tensor(prompt, net.device)
     lengths = None
     if promptLengths is not None:
@@ -228,11 +338,25 @@ def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=Fals
                 f"generate: every prompt length must be in 1..{Tp} (the padded prompt's width), got "
                 f"{lengths.tolist()}")
     stepper = _Stepper(net, cfg, others, masks)
+    pinned = bool(cfg.pinPositions or cfg.useGraph)
+    if pinned:
+        if useBeamPath:
+            raise DL4JInvalidConfigException("GenerationConfig: useGraph / pinPositions cannot run the beam path")
+        if cfg.useGraph and net.device.type != "cuda":
+            raise DL4JInvalidConfigException(f"GenerationConfig: useGraph needs a GPU, the network is on "
+                                             f"{net.device}; pinPositions runs the same steps eagerly on any device")
+        pinnable_layers(stepper.token_layers())                  # refused before the prompt runs
     net.rnnClearPreviousState()
     with torch.no_grad():
         p = stepper.first(prompt, lengths)
         if int(cfg.numBeams) > 1 or useBeamPath:
             return _beam(net, stepper, p, cfg)
+        if pinned:
+            try:
+                return _sample_pinned(net, stepper, p, cfg, prompt.shape[1])
+            finally:
+                if net._rnn_pin is not None:
+                    net._rnn_pin["record"] = None                # the call's buffers are not the network's to keep
         return _sample(stepper, p, cfg)
 
 
@@ -259,6 +383,80 @@ def _sample(stepper, p, cfg):
     # summed in fp64 and rounded once: a row's score does not depend on how many rows the batch has (torch's fp32
     # column sum picks its order by the shape), so a ragged batch scores every row as the row alone
     return GenerationResult(toks, _lengths(toks, eos), logps.sum(0, dtype=torch.float64).float())
+
+
+def _pin_capacity(stepper, Tp, N):
+    """Tp + N positions; one less (the last token is sampled, never fed) where a position table ends there."""
+    limit = min([l.rnnPinLimit() for _, l in stepper.token_layers() if hasattr(l, "rnnPinLimit")], default=None)
+    return Tp + N - 1 if limit is not None and limit == Tp + N - 1 else Tp + N
+
+
+def _sample_pinned(net, stepper, p, cfg, Tp):
+    """``_sample`` with constant launch arguments per step: the state is pinned, the sampler reads the static
+    distribution buffer and writes the staging row, the time step runs on the staged token and its commit launch
+    lowers the shortfalls and files the staging row as row ``t`` of the results. With ``useGraph`` that body runs
+    eagerly once (autotuning, workspaces and the one-hot buffer settle), is captured once and replayed; the last
+    token takes the sampler and the commit alone, eagerly."""
+    from ..ops import generation_native as GN
+    mb, dev, N = p.shape[0], p.device, int(cfg.maxNewTokens)
+    eos = cfg.eosToken
+    stepper.pin(_pin_capacity(stepper, Tp, N))
+    pin = net._rnn_pin
+    tokens = torch.full((N, mb), int(cfg.padToken), dtype=torch.int64, device=dev)
+    logps = torch.zeros(N, mb, dtype=torch.float32, device=dev)
+    stok = torch.zeros(mb, dtype=torch.int64, device=dev)
+    slogp = torch.zeros(mb, dtype=torch.float32, device=dev)
+    record = (torch.zeros(1, dtype=torch.int32, device=dev), stok, slogp, tokens, logps)
+    pin["record"] = record
+    fin = count = None
+    if eos is not None:
+        fin = torch.zeros(mb, dtype=torch.uint8, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+    rng = _stream(cfg, dev) if cfg.doSample else None
+    pbuf = p.clone()
+    stats = {"captures": 0, "graphReplays": 0, "eagerSteps": 0}
+    net.lastGenerationStats = stats
+
+    def sample():
+        GN.sample_rows(pbuf, cfg.temperature, cfg.topK, cfg.topP, not cfg.doSample, rng, fin, eos, cfg.padToken,
+                       count, out=(stok, slogp), advance=True)
+
+    def body():
+        sample()
+        pbuf.copy_(stepper.step(stok))
+
+    graph = None
+    for t in range(N - 1):
+        if cfg.useGraph and graph is None and t >= 1:
+            graph = _capture_step(net, body)
+            pin["left"] += 1                                     # capturing ran the host's count, not the step
+            stats["captures"] += 1
+        if graph is not None:
+            pin_step_begin(net)
+            graph.replay()
+            pin["left"] -= 1
+            stats["graphReplays"] += 1
+        else:
+            body()
+            stats["eagerSteps"] += 1
+        if eos is not None and (t + 1) % int(cfg.eosCheckEvery) == 0 and int(count.item()) == 0:
+            break
+    else:
+        sample()
+        GN.step_commit(None, record)
+        stats["eagerSteps"] += 1
+    if graph is not None:
+        torch.cuda.current_stream(dev).synchronize()             # the graph and its pool go with this call
+    toks = tokens.t().contiguous()
+    return GenerationResult(toks, _lengths(toks, eos), logps.sum(0, dtype=torch.float64).float())
+
+
+def _capture_step(net, body):
+    from . import hipgraph
+    g = torch.cuda.CUDAGraph()
+    with hipgraph.capture_gc_guard():
+        hipgraph.capture(g, torch.cuda.graph_pool_handle(), body, net.device)
+    return g
 
 
 def _lengths(toks, eos):

@@ -720,6 +720,9 @@ class ComputationGraph(BaseNetwork):
         acts = {n: inputs[i] for i, n in enumerate(self.conf.networkInputs)}
         mm = {n: self._to_dev(masks[i]) for i, n in enumerate(self.conf.networkInputs)
               if masks is not None and i < len(masks) and masks[i] is not None and inputs[i] is not None}
+        if self._rnn_pin is not None:
+            from ..generation import pin_step_begin
+            pin_step_begin(self)
         with torch.no_grad():
             for name in self.topo:
                 v = self.conf.vertices[name]
@@ -761,9 +764,13 @@ class ComputationGraph(BaseNetwork):
                     acts[name], _ = v.forward(ins, False, ms if has_mask else None)
                     if has_mask:
                         mm[name] = v.feedForwardMask(ms)
+        if self._rnn_pin is not None:
+            from ..generation import pin_step_commit
+            pin_step_commit(self)
         return [acts[o] for o in self.outputs]
 
     def rnnClearPreviousState(self):
+        self._rnn_pin = None
         for l in self.layers_by_name.values():
             if hasattr(l, "rnnClearPreviousState"):
                 l.rnnClearPreviousState()
@@ -773,6 +780,8 @@ class ComputationGraph(BaseNetwork):
         [mbNew] on the network's device; mbNew may differ from the stored minibatch size). ``groupSize``: the caller
         promises parents[i] // groupSize == i // groupSize, so state that is equal within a group (the memory
         projection of a two-input layer) does not move."""
+        from ..generation import refuse_pinned
+        refuse_pinned(self, "rnnReorderState")
         parents = torch.as_tensor(parents, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
         for l in self.layers_by_name.values():
             if hasattr(l, "rnnReorderState"):
@@ -786,17 +795,34 @@ class ComputationGraph(BaseNetwork):
         inputs (the encoder of an encoder-decoder model) are left alone. Once per sequence. A downstream layer whose
         stored state cannot be trimmed (LSTM family, SimpleRnn) makes the call raise DL4JInvalidInputException before
         any layer is changed."""
-        from ..generation import trim_layers
+        from ..generation import refuse_pinned, trim_layers
+        refuse_pinned(self, "rnnTrimState")
+        trim_layers(self._layers_downstream(input, "rnnTrimState"), lengths)
+
+    def _layers_downstream(self, input, what):
+        """(label, layer) of every layer fed, directly or not, by network input ``input`` (default: the last one)."""
         names = list(self.conf.networkInputs)
         src = names[-1] if input is None else input
         if src not in names:
-            raise DL4JInvalidInputException(f"rnnTrimState: {src!r} is not one of the network inputs {names}")
+            raise DL4JInvalidInputException(f"{what}: {src!r} is not one of the network inputs {names}")
         reach = {src}
         for name in self.topo:
             if any(i in reach for i in self.vertex_inputs[name]):
                 reach.add(name)
-        trim_layers([(f"vertex {n!r}", self.layers_by_name[n]) for n in self.topo
-                     if n in reach and n in self.layers_by_name], lengths)
+        return [(f"vertex {n!r}", self.layers_by_name[n]) for n in self.topo
+                if n in reach and n in self.layers_by_name]
+
+    def rnnPinState(self, capacity, input=None):
+        """Fix the positions of the stored rnnTimeStep state of every layer downstream of network input ``input``
+        (a name; default: the last input) for graph-replayed decoding, as MultiLayerNetwork.rnnPinState: caches are
+        reserved for ``capacity`` rows, the cached layers share one int32 device array of per-row shortfalls against
+        ``capacity - 1`` that one launch per step lowers, and a step has constant launch arguments. Call it after the
+        prompt has gone through rnnTimeStep (and after rnnTrimState for ragged prompts). While pinned, rnnTimeStep
+        takes exactly one time step per call; rnnReorderState / rnnTrimState are refused; rnnClearPreviousState()
+        unpins. A downstream layer that keeps state it cannot pin (LSTM family, SimpleRnn) makes the call raise
+        DL4JInvalidInputException before any layer is changed."""
+        from ..generation import pin_layers
+        pin_layers(self, self._layers_downstream(input, "rnnPinState"), capacity)
 
     def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, **configFields):
         """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py); ``others``
@@ -816,6 +842,8 @@ class ComputationGraph(BaseNetwork):
         layer = self.layers_by_name[layerName] if isinstance(layerName, str) else self.getLayers()[layerName]
         if not hasattr(layer, "rnnSetPreviousState"):
             raise ValueError(f"layer {layerName} is not a recurrent layer")
+        from ..generation import refuse_pinned
+        refuse_pinned(self, "rnnSetPreviousState")
         layer.rnnSetPreviousState(state)
 
     def rnnGetPreviousStates(self):

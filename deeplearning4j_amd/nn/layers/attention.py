@@ -232,6 +232,13 @@ class CrossAttentionLayerImpl(MemoryKVState, LayerImpl):
     def rnnTrimState(self, lengths, dryRun=False):
         """The stored memory projection does not depend on how long the rows of the own stream are: nothing to do."""
 
+    def rnnPinInfo(self):
+        """The stored memory projection has no position that advances: nothing to pin."""
+        return None
+
+    def rnnPinState(self, capacity, short, dryRun=False):
+        pass
+
     def rnnGetPreviousState(self):
         return self.memoryGet()
 

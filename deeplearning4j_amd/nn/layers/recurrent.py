@@ -258,6 +258,15 @@ def cannot_trim(layer):
         "trimmed to per-row lengths, the padded time steps have already gone into it; feed rows of one common length")
 
 
+def cannot_pin(layer):
+    """rnnPinState on a layer that keeps rnnTimeStep state without positions a device array could carry (a
+    recurrence, or a wrapper around one): always refused, naming the layer."""
+    from ...exceptions import DL4JInvalidInputException
+    raise DL4JInvalidInputException(
+        f"rnnPinState on layer {layer.index} ({type(layer.conf).__name__}): this layer's rnnTimeStep state cannot be "
+        "pinned, only key/value caches and position embeddings advance on the device")
+
+
 def forward_trim(inner, lengths, dryRun):
     """rnnTrimState of a wrapper layer: the wrapped layer's, refused where that one keeps state it cannot trim."""
     if hasattr(inner, "rnnTrimState"):

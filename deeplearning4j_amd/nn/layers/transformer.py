@@ -250,10 +250,31 @@ class KVCacheState:
     _kv_len = 0
     _kv_alt = None      # rnnReorderState's second buffer (same shape as _kv, or None): the two are swapped per call
     _kv_short = None    # int32 [mb] shortfall of every row against _kv_len (None: every row is _kv_len long)
+    _kv_pinned = False  # rnnPinState: _kv_len is fixed at capacity - 1 and the network advances _kv_short on the device
 
     def rnnClearPreviousState(self):
         self._kv = self._kv_alt = self._kv_short = None
         self._kv_len = 0
+        self._kv_pinned = False
+
+    def rnnPinInfo(self):
+        """What the network's rnnPinState reads: None (no cache, nothing to pin), or (tokens seen, mb, shortfall or
+        None)."""
+        return None if self._kv is None else (self._kv_len, self._kv.shape[0], self._kv_short)
+
+    def rnnPinState(self, capacity, short, dryRun=False):
+        """Pin the positions (the network's rnnPinState): the cache is reserved for ``capacity`` rows, the host bound
+        becomes ``capacity - 1`` for good and ``short`` (int32 [mb] on the device, shared by every pinned layer of the
+        network, which lowers it once per step) carries the rows' real positions: row b stands at
+        ``capacity - 1 - short[b]``. ``dryRun`` only validates."""
+        if self._kv is None:
+            return
+        _pin_check(self, capacity, self._kv_len, self._kv_pinned)
+        if dryRun:
+            return
+        mb, _, E2 = self._kv.shape
+        self._kv_reserve(mb, E2, capacity, self._kv.dtype, self._kv.device)
+        self._kv_len, self._kv_short, self._kv_pinned = int(capacity) - 1, short, True
 
     def rnnTrimState(self, lengths, dryRun=False):
         """The rows of the stored chunk(s) were right-padded: row b holds ``lengths[b]`` real tokens (1 <= lengths[b]
@@ -261,6 +282,7 @@ class KVCacheState:
         only validates. A layer without a cache (a bidirectional block) has nothing to trim."""
         if self._kv is None:
             return
+        _refuse_pinned(self, "rnnTrimState", self._kv_pinned)
         short = _trim_shortfall(self, lengths, self._kv_len, self._kv.shape[0], self._kv_short is not None)
         if not dryRun:
             self._kv_short = short.to(self._kv.device)
@@ -272,6 +294,7 @@ class KVCacheState:
         kv = self._kv
         if kv is None:
             return
+        _refuse_pinned(self, "rnnReorderState", self._kv_pinned)
         from ...ops import generation_native as GN
         shape = (int(parents.numel()), kv.shape[1], kv.shape[2])
         alt = self._kv_alt
@@ -335,6 +358,8 @@ class KVCacheState:
         mb, Tn, E3 = qkv.shape
         E = E3 // 3
         pos, short = self._kv_len, self._kv_short
+        if self._kv_pinned:
+            _pinned_one_step(self, Tn)
         self._kv_reserve(mb, 2 * E, pos + Tn, qkv.dtype, qkv.device)
         kv = self._kv
         out = None
@@ -355,8 +380,41 @@ class KVCacheState:
                 kv[torch.arange(mb, device=kv.device).reshape(mb, 1), rows] = qkv[:, :, E:]
             out = TN.attention_decode_reference(qkv[:, :, :E], kv[:, :pos + Tn, :E], kv[:, :pos + Tn, E:], H, pos,
                                                 short=short)
-        self._kv_len = pos + Tn
+        if not self._kv_pinned:                  # pinned: the bound stays, the network lowers ``short`` on the device
+            self._kv_len = pos + Tn
         return out
+
+
+def _refuse_pinned(layer, what, pinned):
+    if pinned:
+        from ...exceptions import DL4JInvalidInputException
+        raise DL4JInvalidInputException(
+            f"{what} on layer {layer.index} ({type(layer.conf).__name__}): the state is pinned (rnnPinState), its "
+            "positions advance on the device; call rnnClearPreviousState() first")
+
+
+def _pinned_one_step(layer, Tn):
+    if Tn != 1:
+        from ...exceptions import DL4JInvalidInputException
+        raise DL4JInvalidInputException(
+            f"rnnTimeStep on layer {layer.index} ({type(layer.conf).__name__}): the state is pinned (rnnPinState) and "
+            f"takes exactly one time step per call, got {Tn}")
+
+
+def _pin_check(layer, capacity, seen, pinned, maxPositions=None):
+    """A layer's validation of rnnPinState(capacity) with ``seen`` tokens stored."""
+    from ...exceptions import DL4JInvalidInputException
+    who = f"rnnPinState on layer {layer.index} ({type(layer.conf).__name__})"
+    if pinned:
+        raise DL4JInvalidInputException(
+            f"{who}: the state is pinned already; call rnnClearPreviousState() to start a new sequence")
+    if int(capacity) < seen + 1:
+        raise DL4JInvalidInputException(
+            f"{who}: capacity {capacity} leaves no room for a step after the {seen} tokens seen")
+    if maxPositions is not None and int(capacity) > maxPositions:
+        raise DL4JInvalidInputException(
+            f"{who}: {seen} tokens seen + {int(capacity) - seen} new exceed maxPositions {maxPositions}; call "
+            "rnnClearPreviousState() to start a new sequence")
 
 
 def _trim_shortfall(layer, lengths, seen, mb, trimmed):
@@ -814,13 +872,33 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
     # rnnTrimState the shortfall of every row against that count (int32 [mb] on the device), as in KVCacheState
     _seen = None
     _short = None
+    _pinned = False     # rnnPinState: _seen stays (capacity - 1, mb) and the network advances _short on the device
 
     def rnnClearPreviousState(self):
         self._seen = self._short = None
+        self._pinned = False
+
+    def rnnPinInfo(self):
+        return None if self._seen is None else (self._seen[0], self._seen[1], self._short)
+
+    def rnnPinLimit(self):
+        """The largest capacity rnnPinState takes: the position table's rows."""
+        return int(self.W("Wpos").shape[0])
+
+    def rnnPinState(self, capacity, short, dryRun=False):
+        """Pin the positions as KVCacheState.rnnPinState does: the count of tokens seen becomes ``capacity - 1`` for
+        good and row b's next token takes position ``capacity - 1 - short[b]``. ``capacity`` beyond maxPositions is
+        refused here, once, instead of at the step that would reach it."""
+        if self._seen is None:
+            return
+        _pin_check(self, capacity, self._seen[0], self._pinned, self.W("Wpos").shape[0])
+        if not dryRun:
+            self._seen, self._short, self._pinned = (int(capacity) - 1, self._seen[1]), short, True
 
     def rnnTrimState(self, lengths, dryRun=False):
         """Row b of what has been fed so far holds ``lengths[b]`` real tokens, right-padded: its next token takes
         position ``lengths[b]``. Validated on the host, once per sequence; ``dryRun`` only validates."""
+        _refuse_pinned(self, "rnnTrimState", self._pinned)
         pos, mb = self._seen if self._seen is not None else (0, torch.as_tensor(lengths).numel())
         short = _trim_shortfall(self, lengths, pos, mb, self._short is not None)
         if not dryRun:
@@ -828,6 +906,7 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
 
     def rnnReorderState(self, parents, groupSize=None):
         if self._seen is not None:
+            _refuse_pinned(self, "rnnReorderState", self._pinned)
             self._seen = (self._seen[0], int(parents.numel()))
             self._short = _reorder_short(self._short, parents, groupSize)
 
@@ -861,6 +940,8 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
             raise DL4JInvalidInputException(
                 f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): minibatch size {B} differs "
                 f"from the stored state's {mb}; call rnnClearPreviousState() before changing it")
+        if self._pinned:
+            _pinned_one_step(self, T)
         maxp = self.W("Wpos").shape[0]
         if pos + T > maxp:
             raise DL4JInvalidInputException(
@@ -869,7 +950,8 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         self.training = False
         e = self._embed(idx, pos, self._short)
         y, _ = _ln_fwd(e, None, self.params["lng"], self.params["lnb"], self.conf.layerNormEps)
-        self._seen = (pos + T, B)
+        if not self._pinned:
+            self._seen = (pos + T, B)
         return y.reshape(B, T, -1).permute(0, 2, 1)
 
     def feedForwardMaskArray(self, mask, state, mb):

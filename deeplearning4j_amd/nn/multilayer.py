@@ -440,6 +440,9 @@ class MultiLayerNetwork(BaseNetwork):
         """rnnTimeStep with the output left in the compute dtype (what generate() reads: no fp32 copy per step)."""
         x = self._to_dev(x, self._feat_dtype())
         mb = x.shape[0]
+        if self._rnn_pin is not None:
+            from .generation import pin_step_begin
+            pin_step_begin(self)
         with torch.no_grad():
             for i, layer in enumerate(self.layers):
                 x = self._pp(i, x, mb, False)
@@ -448,17 +451,35 @@ class MultiLayerNetwork(BaseNetwork):
                     x = layer.rnnTimeStep(x)
                 else:
                     x = layer.activate(x, False)
+        if self._rnn_pin is not None:
+            from .generation import pin_step_commit
+            pin_step_commit(self)
         return x
 
     def rnnClearPreviousState(self):
+        self._rnn_pin = None
         for l in self.layers:
             if hasattr(l, "rnnClearPreviousState"):
                 l.rnnClearPreviousState()
+
+    def rnnPinState(self, capacity):
+        """Fix the positions of the stored rnnTimeStep state for graph-replayed decoding (after the prompt has gone
+        through rnnTimeStep, and after rnnTrimState for ragged prompts): every key/value cache is reserved for
+        ``capacity`` rows and every cached layer's host bound becomes ``capacity - 1``, while one int32 device array
+        shared by all of them holds what each row lacks against it and is lowered by one launch per step
+        (csrc/generation.hip). A step then has constant launch arguments. While pinned, rnnTimeStep takes exactly one
+        time step per call, at most ``capacity - (longest row)`` times; rnnReorderState / rnnTrimState are refused;
+        rnnClearPreviousState() unpins. A layer that keeps state it cannot pin (LSTM family, SimpleRnn) makes the call
+        raise DL4JInvalidInputException before any layer is changed."""
+        from .generation import pin_layers
+        pin_layers(self, [(f"layer {i}", l) for i, l in enumerate(self.layers)], capacity)
 
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32
         [mbNew] on the network's device; mbNew may differ from the stored minibatch size). ``groupSize``: the caller
         promises parents[i] // groupSize == i // groupSize, so state that is equal within a group does not move."""
+        from .generation import refuse_pinned
+        refuse_pinned(self, "rnnReorderState")
         parents = torch.as_tensor(parents, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
         for l in self.layers:
             if hasattr(l, "rnnReorderState"):
@@ -470,7 +491,8 @@ class MultiLayerNetwork(BaseNetwork):
         at its own position: key/value caches and position embeddings take per-row positions on the device. Once
         per sequence. A layer whose stored state cannot be trimmed (LSTM family, SimpleRnn: the padded steps have
         already gone into it) makes the call raise DL4JInvalidInputException before any layer is changed."""
-        from .generation import trim_layers
+        from .generation import refuse_pinned, trim_layers
+        refuse_pinned(self, "rnnTrimState")
         trim_layers([(f"layer {i}", l) for i, l in enumerate(self.layers)], lengths)
 
     def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, **configFields):
@@ -484,6 +506,8 @@ class MultiLayerNetwork(BaseNetwork):
         return self.layers[layer].rnnGetPreviousState()
 
     def rnnSetPreviousState(self, layer, state):
+        from .generation import refuse_pinned
+        refuse_pinned(self, "rnnSetPreviousState")
         self.layers[layer].rnnSetPreviousState(state)
 
     # ------------------------------------------------------------------------------ evaluation

@@ -83,6 +83,9 @@ def _apply_output_mask(out, m):
 
 
 class BaseNetwork:
+    _rnn_pin = None              # rnnPinState: the shared position array and the steps left (nn/generation.py)
+    lastGenerationStats = None   # generate(): {"captures", "graphReplays", "eagerSteps"} of the last pinned call
+
     def __init__(self, conf):
         self.conf = conf
         self.listeners = []

@@ -288,6 +288,50 @@ def cache_gather(src, dst, parent, L):
     return cache_gather_torch(src, dst, parent, L)
 
 
+def step_commit_torch(short=None, record=None):
+    """Torch implementation of the step commit (reads the step counter on the host)."""
+    if short is not None:
+        short.copy_((short - 1).clamp_(min=0))
+    if record is not None:
+        step, stok, slogp, tokens, logps = record
+        t = int(step.item())
+        if 0 <= t < tokens.shape[0]:
+            tokens[t].copy_(stok)
+            logps[t].copy_(slogp)
+            step.add_(1)
+
+
+def step_commit(short=None, record=None):
+    """The bookkeeping of one pinned generation step in one call with constant arguments (csrc/generation.hip):
+    ``short`` (int32 [mb] on the device, or None) drops by one per row, not below 0; ``record`` = (step int32 [1],
+    stok int64 [rows], slogp fp32 [rows], tokens int64 [N, rows], logps fp32 [N, rows]) or None files the staged
+    token / log-probability as row ``step`` of the result buffers and bumps ``step`` (nothing once step >= N)."""
+    if short is None and record is None:
+        return
+    ref = short if short is not None else record[0]
+    ok = use_native(ref, "generation")
+    if ok and short is not None:
+        ok = short.dtype == torch.int32 and short.dim() == 1 and short.is_contiguous() and short.numel() >= 1
+    if ok and record is not None:
+        step, stok, slogp, tokens, logps = record
+        N, rows = tokens.shape
+        ok = (step.dtype == torch.int32 and step.numel() == 1 and stok.dtype == tokens.dtype == torch.int64 and
+              slogp.dtype == logps.dtype == torch.float32 and stok.shape == slogp.shape == (rows,) and
+              logps.shape == tokens.shape and N >= 1 and rows >= 1 and
+              all(t.is_contiguous() and t.device == ref.device for t in record))
+    if ok:
+        step, stok, slogp, tokens, logps = record if record is not None else (None,) * 5
+        rc = native.load().dl4j_gen_step_commit(
+            _ptr(short), 0 if short is None else short.numel(), _ptr(step), _ptr(stok), _ptr(slogp), _ptr(tokens),
+            _ptr(logps), 0 if record is None else tokens.shape[1], 0 if record is None else tokens.shape[0],
+            _stream())
+        if rc != -1:
+            _check(rc, "gen_step_commit")
+            return
+    fallback.note(ref, "generation", "step commit: torch path")
+    step_commit_torch(short, record)
+
+
 def beam_backtrack(toks, parents, best, W):
     """The token sequence of each example's chosen beam: toks [N, mb*W] int64 and parents [N, mb*W] int32 as the beam
     steps wrote them, best [mb] (the final beam per example) -> [mb, N] int64. One kernel launch on the GPU."""

@@ -17,8 +17,17 @@
              evenly over [Tp/4, Tp] against the same prompts generated one length bucket at a time (rows grouped by
              their exact length, one generate() per group), same model as --model; the tokens of both are compared.
 
+  --graph    graph-replayed decoding: generate(useGraph=True) against generate() (useGraph=False) on the same network in
+             the same process, the two alternating within every pass; with --parent-lib also against generate() with
+             every kernel call going to a kernel library built from the parent commit. 12-layer, hidden-768 model at
+             batch 1 / 32, prefix 128 / 1024, greedy and temperature 0.8 / top-k 50 / top-p 0.9; the 32-prompt ragged
+             batch of --ragged; TransformerSeq2Seq (hidden 768, 6 + 6 layers, source 128) at batch 1. Also the
+             one-off cost of a graph call (its warm-up step and the capture) and the maxNewTokens from which the
+             graph call is the faster one.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
-       python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]"""
+       python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
+       python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]"""
 import argparse
 import sys
 import time
@@ -274,6 +283,114 @@ def ragged_model_mode(n, passes):
     say()
 
 
+def _parent_library(path):
+    """The parent commit's kernel library with the signatures of the entry points it has (it lacks the new ones)."""
+    import ctypes
+    from deeplearning4j_amd.ops import abi
+    lib = ctypes.CDLL(path)
+    for name, (args, res) in abi.signatures().items():
+        f = getattr(lib, name, None) if name.startswith("dl4j_") else None
+        if f is not None:
+            f.argtypes, f.restype = args, res
+    return lib
+
+
+def _graph_case(name, call, n, rows, passes, parent):
+    """``call(**kw)`` runs one generate(); kw selects the variant. The variants alternate within a pass."""
+    import contextlib
+    from deeplearning4j_amd.ops import native
+
+    @contextlib.contextmanager
+    def through(lib):
+        ours, native._lib = native._lib, lib
+        try:
+            yield
+        finally:
+            native._lib = ours
+
+    def eager():
+        return call()
+
+    def graph():
+        return call(useGraph=True)
+
+    def pinned():
+        return call(pinPositions=True)
+
+    def par():
+        with through(parent):
+            return call()
+
+    variants = [("eager", eager), ("graph", graph), ("pinned eager", pinned)] + ([("parent", par)] if parent else [])
+    outs = [fn() for _, fn in variants]
+    same = [bool((o.tokens == outs[0].tokens).all()) for o in outs]
+    times = [[] for _ in variants]
+    for _ in range(passes):
+        for i, (_, fn) in enumerate(variants):
+            times[i].append(_sync_time(fn))
+    med = [sorted(t)[len(t) // 2] for t in times]
+    # the one-off cost and the steady step of a graph call: a call's time is a + b * tokens, so time it at 3n too
+    long_n = 3 * n
+    tl = sorted(_sync_time(lambda: call(useGraph=True, maxNewTokens=long_n)) for _ in range(passes))[passes // 2]
+    el = sorted(_sync_time(lambda: call(maxNewTokens=long_n)) for _ in range(passes))[passes // 2]
+    gstep, estep = (tl - med[1]) / (long_n - n), (el - med[0]) / (long_n - n)
+    once = (med[1] - n * gstep) - (med[0] - n * estep)            # what a graph call pays on top, once
+    even = "never" if gstep >= estep else f"{max(1, int(once / (estep - gstep)) + 1)}"
+    line = f"{name:34s}:"
+    for (vn, _), t, m in zip(variants, times, med):
+        line += f"  {vn} {rows * n / m:8.1f} tok/s {m / n * 1e3:5.2f} ms/tok " \
+                f"({min(t) * 1e3:.0f} .. {max(t) * 1e3:.0f} ms)"
+    line += f"  graph/eager {med[0] / med[1]:5.2f}x"
+    if parent:
+        line += f"  graph/parent {med[3] / med[1]:5.2f}x  eager/parent {med[3] / med[0]:5.3f}x"
+    say(line)
+    say(f"{'':34s}   from the same calls with {long_n} tokens: replayed step {gstep * 1e3:5.2f} ms vs eager step "
+        f"{estep * 1e3:5.2f} ms; warm-up + capture "
+        f"{once * 1e3:6.1f} ms per call; graph call faster from maxNewTokens = {even}; tokens equal to eager's: "
+        + ", ".join(f"{vn} {ok}" for (vn, _), ok in zip(variants[1:], same[1:])))
+
+
+def graph_mode(batches, n, passes, parent_lib):
+    from deeplearning4j_amd.models import TextGenerationTransformer, TransformerSeq2Seq
+    from deeplearning4j_amd.nn.conf import DataType
+    V = 77
+    parent = _parent_library(parent_lib) if parent_lib else None
+    net = TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=768, layers=12, heads=12, maxPositions=2048,
+                                    dataType=DataType.BFLOAT16).init(device=DEV)
+    say(f"== generate(useGraph=True) against generate() on TextGenerationTransformer(768, 12 layers, 12 heads), bf16, "
+        f"V = {V}, {n} new tokens; whole calls (prompt included) on the host clock, ended by a device synchronise; "
+        f"median of {passes} passes (min .. max), the variants alternating within a pass")
+    say("   eager = useGraph=False; graph = one eager step, one capture, replays; pinned eager = pinPositions=True "
+        "(the graph call's launches, not captured)"
+        + ("; parent = eager with every kernel call going to the parent commit's kernel library" if parent else ""))
+    say("   one bound for the whole call: every step launches the split count of the final length")
+    sampling = dict(doSample=True, temperature=0.8, topK=50, topP=0.9, seed=1)
+    for mb in batches:
+        for P in (128, 1024):
+            prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb + P)).to(DEV)
+            for cname, kw in (("greedy", dict()), ("T.8 k50 p.9", sampling)):
+                def call(prompt=prompt, kw=kw, **over):
+                    return net.generate(prompt, **dict(dict(kw, maxNewTokens=n), **over))
+                _graph_case(f"batch {mb:2d} prefix {P:4d} {cname}", call, n, mb, passes, parent)
+    mb, Tp = 32, 128
+    lens = [Tp // 4 + (b * (Tp - Tp // 4)) // (mb - 1) for b in range(mb)]
+    prompt = torch.randint(0, V, (mb, Tp), generator=torch.Generator().manual_seed(mb)).to(DEV)
+
+    def ragged(**over):
+        return net.generate(prompt, promptLengths=lens, **dict(dict(maxNewTokens=n), **over))
+    _graph_case(f"32 ragged prompts {lens[0]}..{lens[-1]} greedy", ragged, n, mb, passes, parent)
+    del net
+    s2s = TransformerSeq2Seq(numLabels=V, inputShape=[128, 128], hidden=768, layers=6, heads=12, maxPositions=512,
+                             dataType=DataType.BFLOAT16).init(device=DEV)
+    src = torch.randint(0, V, (1, 128), generator=torch.Generator().manual_seed(5)).to(DEV)
+    start = torch.zeros(1, 1, dtype=torch.int64, device=DEV)
+
+    def seq2seq(**over):
+        return TransformerSeq2Seq.generate(s2s, src, start, **dict(dict(maxNewTokens=n), **over))
+    _graph_case("TransformerSeq2Seq 6+6 batch 1 greedy", seq2seq, n, 1, passes, parent)
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -281,7 +398,9 @@ def main():
     ap.add_argument("--gather", action="store_true")
     ap.add_argument("--model", action="store_true")
     ap.add_argument("--ragged", action="store_true")
-    ap.add_argument("--parent-lib", default=None, help="kernel library built from the parent commit (--ragged)")
+    ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--parent-lib", default=None,
+                    help="kernel library built from the parent commit (--ragged, --graph)")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--passes", type=int, default=5)
@@ -300,6 +419,8 @@ def main():
     if a.ragged:
         ragged_kernel_mode(a.passes, max(a.reps, 50), a.parent_lib)
         ragged_model_mode(a.tokens, a.passes)
+    if a.graph:
+        graph_mode(a.batch, a.tokens, a.passes, a.parent_lib)
 
 
 if __name__ == "__main__":
