@@ -24,27 +24,88 @@
 //    array shortfall[b] = what row b lacks against it, written once per sequence. The *_ragged_kernel variants run
 //    the same bodies at pos - shortfall[b]; for a row with at least S key blocks the result is the bits the uniform
 //    kernel gives that row alone at its own position with the same S.
+//  * FP8 cache (opt-in): kv8[B, Tcap, R] bytes, R = 2E + roundup16(2H). A group is the D values of one token, one
+//    head, K or V: amax = max |x|, ex the smallest integer with amax * 2^-ex <= 448 (0 for an all-zero group, clamped
+//    into [-126, 127]), code = e4m3fn(x * 2^-ex) (OCP, round to nearest even; the scaling is exact and nothing
+//    saturates), value = code * 2^ex. K codes of head h at byte h*D, V codes at E + h*D, K's scale byte ex + 127 at
+//    2E + h, V's at 2E + H + h, zero pad up to R. attn_kv_append_fp8_kernel quantises and writes; the decode body
+//    takes the cache side as a policy (KvCache16 / KvCacheFp8): the fp8 one loads 16 codes per 16-byte vector plus
+//    the row's two scale bytes and converts while staging (v_cvt_scalef32_pk_{bf16,f16}_fp8), writing the same Ks / Vt
+//    images — from the first barrier on the two are one code, so the fp8 kernel gives the bits of the 16-bit kernel
+//    on the dequantised cache.
 #include "attention_body.h"
+
+// ------------------------------------------------------------------------------------------------ cache policies
+// What attn_decode_body needs from a cache: elem (the pointer's element type), CPR 16-byte chunks per D columns of a
+// row, each CW elements wide and NV fragments of 8 hb, row_ld(E, H) the row stride in elements, chunk / scale_t as the
+// registers of one chunk in flight, load / zero. V sits E elements after K in both. With NV == 1 a chunk is the 8 hb
+// as they are staged; with NV > 1 it holds codes: load_scale gives the group's scale and piece(.., j) fragment j in hb.
+// The scale registers and the conversion are kept out of the NV == 1 instantiations at compile time (if constexpr):
+// with them in, dead as they are there, the compiler schedules those kernels differently.
+template <int D, typename hb> struct KvCache16 {
+  using elem = hb;
+  using chunk = V8<hb>;
+  struct scale_t {};
+  static constexpr int CPR = D / 8, NV = 1, CW = 8;
+  static __device__ __forceinline__ long long row_ld(int E, int) { return 2LL * E; }
+  static __device__ __forceinline__ chunk load(const hb* p) { return ld8(p); }
+  static __device__ __forceinline__ chunk zero() { return V8<hb>{0, 0, 0, 0, 0, 0, 0, 0}; }
+};
+
+__device__ __forceinline__ V8<__bf16> fp8x4x2_to(unsigned a, unsigned b, float sc, __bf16) {
+  const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, sc, false);
+  const auto p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, sc, true);
+  const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, sc, false);
+  const auto p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, sc, true);
+  return V8<__bf16>{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+__device__ __forceinline__ V8<_Float16> fp8x4x2_to(unsigned a, unsigned b, float sc, _Float16) {
+  const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(a, sc, false);
+  const auto p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(a, sc, true);
+  const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, sc, false);
+  const auto p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, sc, true);
+  return V8<_Float16>{(_Float16)p0[0], (_Float16)p0[1], (_Float16)p1[0], (_Float16)p1[1],
+                      (_Float16)p2[0], (_Float16)p2[1], (_Float16)p3[0], (_Float16)p3[1]};
+}
+
+// rows of R(E, H) bytes; the head's K codes at the row pointer, V codes E bytes on, the scale bytes at 2E - h*D
+template <int D, typename hb> struct KvCacheFp8 {
+  using elem = unsigned char;
+  using chunk = uint4;                                           // 16 codes
+  using scale_t = float;                                         // 2^ex
+  static constexpr int CPR = D / 16, NV = 2, CW = 16;
+  static __device__ __forceinline__ long long row_ld(int E, int H) { return 2LL * E + ((2 * H + 15) & ~15); }
+  static __device__ __forceinline__ chunk load(const elem* p) { return *reinterpret_cast<const uint4*>(p); }
+  static __device__ __forceinline__ chunk zero() { return make_uint4(0u, 0u, 0u, 0u); }
+  // row points at the head's K codes (byte h*D of the cache row)
+  static __device__ __forceinline__ scale_t load_scale(const elem* row, int E, int H, int h, bool v) {
+    return __uint_as_float((unsigned)row[2 * E - h * D + (v ? H : 0) + h] << 23);
+  }
+  static __device__ __forceinline__ V8<hb> piece(const chunk& v, scale_t sc, int j) {
+    return j == 0 ? fp8x4x2_to(v.x, v.y, sc, hb{}) : fp8x4x2_to(v.z, v.w, sc, hb{});
+  }
+};
 
 // partial workspace for S splits: acc[((bh*Tn + q)*S + s)*D + d] (16-byte aligned rows), then ml[(bh*Tn + q)*S + s][2]
 // holding (m, l)
 // The body takes the position of its own batch row: the uniform kernel passes the host's pos, the ragged one
 // pos - shortfall[b] (everything below — key-block count, split ranges, causal cut, zero staging — follows from it).
-template <int D, typename hb>
-__device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, const hb* __restrict__ kv,
+template <int D, typename hb, typename CP = KvCache16<D, hb>>
+__device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, const typename CP::elem* __restrict__ kv,
                                                  hb* __restrict__ out, float* __restrict__ ws, int Tn, int H, int pos,
                                                  int Tcap, int S, float scale2) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = BLK + 8;
-  constexpr int CPR = D / 8, PER = BLK * CPR / 256;              // 16-byte chunks per row / per thread per block
+  constexpr int CPR = CP::CPR, PER = BLK * CPR / 256;            // 16-byte chunks per row / per thread per block
+  constexpr int NV = CP::NV;                                     // fragments of 8 hb in a chunk
   __shared__ __attribute__((aligned(16))) hb Ks[BLK * LDK];
   __shared__ __attribute__((aligned(16))) hb Vt[D * LDV];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, hgrp = lane >> 4;
   const int split = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int E = H * D, L = pos + Tn;
-  const long long ld3 = 3LL * E, ld2 = 2LL * E;
+  const long long ld3 = 3LL * E, ld2 = CP::row_ld(E, H);
   const hb* qbase = qkv + (long long)b * Tn * ld3 + h * D;
-  const hb* kbase = kv + (long long)b * Tcap * ld2 + h * D;
+  const typename CP::elem* kbase = kv + (long long)b * Tcap * ld2 + h * D;
   const int q0 = blockIdx.z * BLK;
   const int qi = q0 + wave * 16 + col;                           // index in the chunk; its position is pos + qi
   const bool active = q0 + wave * 16 < Tn;                       // wave-uniform: any query of this wave's 16 exists
@@ -60,16 +121,21 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
   const int nkb = (L + BLK - 1) / BLK;
   const int kb_lo = (int)((long long)split * nkb / S);
   const int kb_hi = min((int)((long long)(split + 1) * nkb / S), (pos + min(q0 + BLK, Tn) - 1) / BLK + 1);
-  V8<hb> kr[PER], vr[PER];
+  typename CP::chunk kr[PER], vr[PER];
+  typename CP::scale_t ksc[PER], vsc[PER];
   auto fetch = [&](int kb) {
 #pragma unroll
     for (int it = 0; it < PER; ++it) {
       const int i = threadIdx.x + it * 256, r = i / CPR, c = i - r * CPR;
       const int row = kb * BLK + r;
       const bool ok = row < L;                                   // rows past the valid length are staged as zeros
-      const hb* src = kbase + (long long)(ok ? row : 0) * ld2 + c * 8;
-      kr[it] = ok ? ld8(src) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-      vr[it] = ok ? ld8(src + E) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+      const typename CP::elem* src = kbase + (long long)(ok ? row : 0) * ld2 + c * CP::CW;
+      kr[it] = ok ? CP::load(src) : CP::zero();
+      vr[it] = ok ? CP::load(src + E) : CP::zero();
+      if constexpr (NV > 1) {
+        ksc[it] = ok ? CP::load_scale(src - c * CP::CW, E, H, h, false) : typename CP::scale_t{};
+        vsc[it] = ok ? CP::load_scale(src - c * CP::CW, E, H, h, true) : typename CP::scale_t{};
+      }
     }
   };
   if (kb_lo < kb_hi) fetch(kb_lo);
@@ -78,9 +144,20 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
 #pragma unroll
     for (int it = 0; it < PER; ++it) {
       const int i = threadIdx.x + it * 256, r = i / CPR, c = i - r * CPR;
-      *reinterpret_cast<V8<hb>*>(Ks + r * LDK + c * 8) = kr[it];
+      if constexpr (NV == 1) {
+        *reinterpret_cast<V8<hb>*>(Ks + r * LDK + c * 8) = kr[it];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) Vt[(c * 8 + k) * LDV + r] = vr[it][k];
+        for (int k = 0; k < 8; ++k) Vt[(c * 8 + k) * LDV + r] = vr[it][k];
+      } else {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          const int cj = c * NV + j;                             // the 8-column fragment
+          *reinterpret_cast<V8<hb>*>(Ks + r * LDK + cj * 8) = CP::piece(kr[it], ksc[it], j);
+          const V8<hb> vj = CP::piece(vr[it], vsc[it], j);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) Vt[(cj * 8 + k) * LDV + r] = vj[k];
+        }
+      }
     }
     __syncthreads();
     if (kb + 1 < kb_hi) fetch(kb + 1);
@@ -166,6 +243,25 @@ __global__ void __launch_bounds__(256) attn_decode_ragged_kernel(const hb* __res
   attn_decode_body<D, hb>(qkv, kv, out, ws, Tn, H, pos - min(max(shortfall[b], 0), pos), Tcap, S, scale2);
 }
 
+// The same two kernels over the fp8 cache kv8[B, Tcap, R].
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_decode_fp8_kernel(const hb* __restrict__ qkv,
+                                                              const unsigned char* __restrict__ kv8,
+                                                              hb* __restrict__ out, float* __restrict__ ws, int Tn,
+                                                              int H, int pos, int Tcap, int S, float scale2) {
+  attn_decode_body<D, hb, KvCacheFp8<D, hb>>(qkv, kv8, out, ws, Tn, H, pos, Tcap, S, scale2);
+}
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_decode_fp8_ragged_kernel(const hb* __restrict__ qkv,
+                                                                     const unsigned char* __restrict__ kv8,
+                                                                     hb* __restrict__ out, float* __restrict__ ws,
+                                                                     int Tn, int H, int pos, int Tcap, int S,
+                                                                     float scale2, const int* __restrict__ shortfall) {
+  const int b = blockIdx.y / H;
+  attn_decode_body<D, hb, KvCacheFp8<D, hb>>(qkv, kv8, out, ws, Tn, H, pos - min(max(shortfall[b], 0), pos), Tcap, S,
+                                             scale2);
+}
+
 // out[b, q, h*D + d] = sum_s acc_s[d] 2^(m_s - M) / sum_s l_s 2^(m_s - M), M = max_s m_s, in the order s = 0 .. S-1;
 // one thread per (bh, q, 4 consecutive d)
 template <int D, typename hb>
@@ -247,6 +343,60 @@ __global__ void __launch_bounds__(256) attn_kv_append_ragged_kernel(const uint4*
   kv[(b * Tcap + pb + t) * (2LL * EC) + c] = qkv[bt * (3LL * EC) + EC + c];
 }
 
+// FP8 append: D / 16 lanes per (token, head, K|V) group, 16 values each. The group's amax is reduced across its lanes
+// (they sit in one wave: 4 or 8 consecutive lanes), every lane writes its 16 codes as one 16-byte vector and lane 0
+// the scale byte; the last group of a token also zeroes the pad bytes. shortfall: null (every row at pos) or the
+// per-row array, clamped into [0, pos] as in attn_kv_append_ragged_kernel.
+template <int D, typename hb>
+__global__ void __launch_bounds__(256) attn_kv_append_fp8_kernel(const hb* __restrict__ qkv,
+                                                                 unsigned char* __restrict__ kv8, long long total,
+                                                                 int Tn, int H, int pos, int Tcap,
+                                                                 const int* __restrict__ shortfall) {
+  constexpr int LPG = D / 16;                                    // lanes per group
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;                                        // whole groups leave: total is a multiple of LPG
+  const int c = (int)(i % LPG);
+  const long long gi = i / LPG;
+  const int g = (int)(gi % (2 * H));                             // K heads 0 .. H-1, then V heads
+  const long long bt = gi / (2 * H);                             // b*Tn + t
+  const int t = (int)(bt % Tn);
+  const long long b = bt / Tn;
+  const int E = H * D, tail = (2 * H + 15) & ~15;
+  const hb* src = qkv + bt * (3LL * E) + E + g * D + c * 16;
+  const V8<hb> lo = ld8(src), hi = ld8(src + 8);
+  float x[16];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    x[k] = (float)lo[k];
+    x[8 + k] = (float)hi[k];
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) amax = fmaxf(amax, fabsf(x[k]));
+#pragma unroll
+  for (int o = 1; o < LPG; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  // amax = m * 2^e, m in [0.5, 1): 448 = 0.875 * 2^9
+  int e;
+  const float m = frexpf(amax, &e);
+  int ex = amax > 0.f ? (m <= 0.875f ? e - 9 : e - 8) : 0;
+  ex = min(max(ex, -126), 127);
+  unsigned w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int v = __builtin_amdgcn_cvt_pk_fp8_f32(ldexpf(x[4 * k], -ex), ldexpf(x[4 * k + 1], -ex), 0, false);
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(ldexpf(x[4 * k + 2], -ex), ldexpf(x[4 * k + 3], -ex), v, true);
+    w[k] = (unsigned)v;
+  }
+  const int pb = shortfall ? pos - min(max(shortfall[b], 0), pos) : pos;
+  unsigned char* row = kv8 + (b * Tcap + pb + t) * (2LL * E + tail);
+  *reinterpret_cast<uint4*>(row + g * D + c * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+  if (c == 0) {
+    row[2 * E + g] = (unsigned char)(ex + 127);
+    if (g == 2 * H - 1)
+      for (int p = 2 * H; p < tail; ++p) row[2 * E + p] = 0;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ launch
 // Default split count, from the measurements of tools/bench_decode.py --kernel --sweep (profiles/decode_attention.txt):
 // a block's pass over its key blocks is a chain of dependent memory round trips, so short chains on many blocks win
@@ -314,6 +464,30 @@ DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, in
   return dl4j_attn_kv_append_ragged_dt(dt, qkv, kv, nullptr, B, Tn, H, D, pos, Tcap, s);
 }
 
+// The fp8 cache's append: kv8 [B,Tcap,R] bytes, R = 2*H*D + roundup16(2*H) (the layout at the top of this file);
+// quantises the K and V columns of qkv into rows [pos, pos+Tn) (row b at pos - shortfall[b] with a shortfall array).
+// Arguments and status codes of dl4j_attn_kv_append_ragged_dt.
+DL4J_API int dl4j_attn_kv_append_fp8_ragged_dt(int dt, const void* qkv, void* kv8, const int* shortfall, int B, int Tn,
+                                               int H, int D, int pos, int Tcap, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv8) return -1;
+  if (!attn_aligned16({qkv, kv8})) return -1;
+  const long long total = (long long)B * Tn * 2 * H * (D / 16);
+  if ((total + 255) / 256 > 0x7fffffffLL) return -1;
+  return attn_dispatch(dt, D, [&](auto d, auto e) {
+    constexpr int DD = decltype(d)::value;
+    using hb = typename decltype(e)::type;
+    hipLaunchKernelGGL((attn_kv_append_fp8_kernel<DD, hb>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                       (const hb*)qkv, (unsigned char*)kv8, total, Tn, H, pos, Tcap, shortfall);
+    return (int)hipGetLastError();
+  });
+}
+
+// Every batch row at pos.
+DL4J_API int dl4j_attn_kv_append_fp8_dt(int dt, const void* qkv, void* kv8, int B, int Tn, int H, int D, int pos,
+                                        int Tcap, hipStream_t s) {
+  return dl4j_attn_kv_append_fp8_ragged_dt(dt, qkv, kv8, nullptr, B, Tn, H, D, pos, Tcap, s);
+}
+
 // out [B,Tn,H*D]; rows [0, pos+Tn) of kv are the keys / values (the new rows already appended), query i sees keys
 // <= pos + i. splits >= 1 is clamped to the number of 64-key blocks; ws: fp32 workspace of
 // dl4j_attn_decode_ws_bytes(..., splits) bytes (may be null for one split). -1 = unsupported shape / dtype.
@@ -349,4 +523,39 @@ DL4J_API int dl4j_attn_decode_ragged_dt(int dt, const void* qkv, const void* kv,
 DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
                                  int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
   return dl4j_attn_decode_ragged_dt(dt, qkv, kv, out, ws, nullptr, B, Tn, H, D, pos, Tcap, splits, scale, s);
+}
+
+// dl4j_attn_decode_ragged_dt over the fp8 cache kv8 [B,Tcap,R] bytes: the same arguments, split clamp, workspace
+// (dl4j_attn_decode_ws_bytes) and status codes; for a given split count the result is bitwise what the 16-bit entry
+// gives on the dequantised cache.
+DL4J_API int dl4j_attn_decode_fp8_ragged_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws,
+                                            const int* shortfall, int B, int Tn, int H, int D, int pos, int Tcap,
+                                            int splits, float scale, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv8 || !out || splits < 1) return -1;
+  if (!attn_aligned16({qkv, kv8, out, ws})) return -1;
+  const int S = decode_clamp_splits(splits, pos + Tn);
+  if (S > 1 && !ws) return -1;
+  return attn_dispatch(dt, D, [&](auto d, auto e) {
+    constexpr int DD = decltype(d)::value;
+    using hb = typename decltype(e)::type;
+    const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
+    if (shortfall)
+      hipLaunchKernelGGL((attn_decode_fp8_ragged_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv,
+                         (const unsigned char*)kv8, (hb*)out, ws, Tn, H, pos, Tcap, S, scale * kLog2e, shortfall);
+    else
+      hipLaunchKernelGGL((attn_decode_fp8_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv,
+                         (const unsigned char*)kv8, (hb*)out, ws, Tn, H, pos, Tcap, S, scale * kLog2e);
+    if (S > 1) {
+      const long long n = (long long)B * H * Tn * (DD / 4);
+      hipLaunchKernelGGL((attn_decode_combine_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
+                         (hb*)out, (long long)B * H, Tn, H, S);
+    }
+    return (int)hipGetLastError();
+  });
+}
+
+// Every batch row at pos.
+DL4J_API int dl4j_attn_decode_fp8_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws, int B, int Tn,
+                                     int H, int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
+  return dl4j_attn_decode_fp8_ragged_dt(dt, qkv, kv8, out, ws, nullptr, B, Tn, H, D, pos, Tcap, splits, scale, s);
 }

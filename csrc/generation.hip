@@ -573,11 +573,11 @@ DL4J_API int dl4j_gen_beam_step_dt(int dt, const void* p, int B, int W, int V, f
   return rc ? rc : gen_count_l(finished, B * W, count, nullptr, s);
 }
 
-// dst[i, 0:L, :] = src[parent[i], 0:L, :], i < mbD; elemBytes 2 or 4; C*elemBytes must be a multiple of 16 and both
+// dst[i, 0:L, :] = src[parent[i], 0:L, :], i < mbD; elemBytes 1 (the fp8 key/value cache's byte rows), 2 or 4; C*elemBytes must be a multiple of 16 and both
 // buffers 16-byte aligned. -1 = refused (also src == dst, L beyond a capacity, null pointer).
 DL4J_API int dl4j_gen_cache_gather(const void* src, void* dst, const int* parent, int mbS, int mbD, int TcapS,
                                    int TcapD, int L, int C, int elemBytes, hipStream_t s) {
-  if (!src || !dst || !parent || src == dst || (elemBytes != 2 && elemBytes != 4)) return -1;
+  if (!src || !dst || !parent || src == dst || (elemBytes != 1 && elemBytes != 2 && elemBytes != 4)) return -1;
   if (mbS < 1 || mbD < 1 || C < 1 || L < 0 || L > TcapS || L > TcapD) return -1;
   if (((long long)C * elemBytes) & 15) return -1;
   if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) return -1;

@@ -969,11 +969,12 @@ class TextGenerationTransformer(ZooModel):
         return net.generate(prompt, promptLengths=promptLengths, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
-                 maxPositions=512, learningRate=1e-3, **kw):
+                 maxPositions=512, learningRate=1e-3, cacheDataType=None, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
         self.maxPositions, self.learningRate = maxPositions, learningRate
+        self.cacheDataType = cacheDataType      # None, or "fp8": the key/value cache format of every block
 
     def graphBuilder(self):
         from ..nn.conf import BertEmbeddingLayer, TransformerEncoderLayer
@@ -985,7 +986,8 @@ class TextGenerationTransformer(ZooModel):
         prev = "embeddings"
         for i in range(self.layers):
             g.addLayer(f"decoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
-                       .nHeads(self.heads).ffnSize(self.ffn).causal(True).build(), prev)
+                       .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
+                       .build(), prev)
             prev = f"decoder_{i}"
         g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
                    .nIn(self.hidden).nOut(self.numLabels).build(), prev)
@@ -1030,13 +1032,15 @@ class TransformerSeq2Seq(ZooModel):
                             promptLengths=startLengths, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, sourceVocabSize=None, hidden=256, layers=4, heads=4,
-                 ffn=None, maxPositions=512, learningRate=1e-3, hiddenDropout=0.0, attentionDropout=0.0, **kw):
+                 ffn=None, maxPositions=512, learningRate=1e-3, hiddenDropout=0.0, attentionDropout=0.0,
+                 cacheDataType=None, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.sourceVocabSize = int(sourceVocabSize) if sourceVocabSize else numLabels
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
         self.maxPositions, self.learningRate = maxPositions, learningRate
         self.hiddenDropout, self.attentionDropout = hiddenDropout, attentionDropout
+        self.cacheDataType = cacheDataType      # None, or "fp8": the self-attention cache format of the decoder blocks
 
     def graphBuilder(self):
         from ..nn.conf import BertEmbeddingLayer, TransformerDecoderLayer, TransformerEncoderLayer
@@ -1058,7 +1062,8 @@ class TransformerSeq2Seq(ZooModel):
         for i in range(self.layers):
             g.addLayer(f"decoder_{i}", TransformerDecoderLayer.Builder().nIn(self.hidden).nInMemory(self.hidden)
                        .nOut(self.hidden).nHeads(self.heads).ffnSize(self.ffn).hiddenDropout(self.hiddenDropout)
-                       .attentionDropout(self.attentionDropout).build(), prev, mem)
+                       .attentionDropout(self.attentionDropout).cacheDataType(self.cacheDataType)
+                       .build(), prev, mem)
             prev = f"decoder_{i}"
         g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
                    .nIn(self.hidden).nOut(self.numLabels).build(), prev)

@@ -131,6 +131,8 @@ class Config:
     FIELDS = {}
     _ALIASES = {}
     _CONVERTERS = {}
+    _OMIT_AT_DEFAULT = ()       # fields added after configurations were first written: left out of the dict (and the
+                                # JSON) while at their default, so the text of an earlier configuration does not change
     Builder = _BuilderDescriptor()
 
     def __init_subclass__(cls, **kw):
@@ -206,7 +208,10 @@ class Config:
     # --- serde -------------------------------------------------------------------------------
     def to_dict(self):
         d = {"@class": type(self).__name__}
-        for k in sorted(self._all_fields()):
+        fields = self._all_fields()
+        for k in sorted(fields):
+            if k in self._OMIT_AT_DEFAULT and getattr(self, k) == fields[k]:
+                continue
             d[k] = _encode(getattr(self, k))
         return d
 

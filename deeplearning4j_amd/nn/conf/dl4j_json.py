@@ -100,7 +100,10 @@ def _enc(v):
 
 def _fields(obj, rename=True):
     d = {}
-    for k in sorted(obj._all_fields()):
+    fields = obj._all_fields()
+    for k in sorted(fields):
+        if k in obj._OMIT_AT_DEFAULT and getattr(obj, k) == fields[k]:
+            continue
         d[FIELD_OUT.get(k, k) if rename else k] = _enc(getattr(obj, k))
     return d
 

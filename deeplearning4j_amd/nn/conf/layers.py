@@ -1383,6 +1383,15 @@ class SameDiffLayerConf(Layer):
             self.nIn = inputType.size if hasattr(inputType, "size") else inputType.arrayElementsPerExample()
 
 
+def _check_cache_dtype(layer):
+    """``cacheDataType``: the format of the layer's rnnTimeStep key/value cache. None = the compute dtype, "fp8" =
+    e4m3fn codes with one power-of-two scale per token, head and K | V (csrc/attention_decode.hip)."""
+    v = layer.cacheDataType
+    if v is not None and v != "fp8":
+        raise DL4JInvalidConfigException(
+            f"{type(layer).__name__}: cacheDataType is None (the compute dtype) or \"fp8\", got {v!r}")
+
+
 def _check_drop_prob(layer, name):
     """``name`` is a DROP probability in [0, 1) (HuggingFace's convention; 0.0 = off) — the opposite of the
     retain-probability ``dropOut`` of the reference's layers."""
@@ -1399,13 +1408,18 @@ class SelfAttentionLayer(FeedForwardLayer):
 
     ``attentionDropout``: DROP probability in [0, 1) of the attention probabilities, applied in training only
     (0.0 = off, the default; HuggingFace's ``attention_probs_dropout_prob``, NOT the reference's retain-probability
-    ``dropOut``). The mask is generated inside the flash-attention kernels and never stored."""
-    FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False, "attentionDropout": 0.0}
+    ``dropOut``). The mask is generated inside the flash-attention kernels and never stored.
+
+    ``cacheDataType``: None (the default: the rnnTimeStep key/value cache is kept in the compute dtype) or "fp8"."""
+    FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False, "attentionDropout": 0.0,
+              "cacheDataType": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType",)
     RUNTIME = "deeplearning4j_amd.nn.layers.attention:SelfAttentionLayerImpl"
 
     def _post_init(self):
         super()._post_init()
         _check_drop_prob(self, "attentionDropout")
+        _check_cache_dtype(self)
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1445,15 +1459,20 @@ class TransformerEncoderLayer(FeedForwardLayer):
     default (HuggingFace's ``hidden_dropout_prob`` / ``attention_probs_dropout_prob`` — the opposite of the
     reference's retain-probability ``dropOut``). Hidden dropout sits at BERT's two sites, LN(drop(ctx Wo + bo) + x)
     and LN(drop(ffn) + h1), fused into the LayerNorm forward kernel; attention dropout acts on the softmax
-    probabilities inside the flash-attention kernels. No mask is stored on the GPU."""
+    probabilities inside the flash-attention kernels. No mask is stored on the GPU.
+
+    ``cacheDataType``: None (the default: the rnnTimeStep key/value cache of a causal block is kept in the compute
+    dtype) or "fp8" (half the bytes per cached token; see ``KVCacheState``)."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
-              "attentionDropout": 0.0}
+              "attentionDropout": 0.0, "cacheDataType": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType",)
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
 
     def _post_init(self):
         super()._post_init()
         _check_drop_prob(self, "hiddenDropout")
         _check_drop_prob(self, "attentionDropout")
+        _check_cache_dtype(self)
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1539,14 +1558,20 @@ class TransformerDecoderLayer(_TwoInputLayer):
 
     ``hiddenDropout`` / ``attentionDropout``: DROP probabilities in [0, 1), training only, 0.0 = off (the convention
     of ``TransformerEncoderLayer``). ``hiddenDropout`` applies at all three LayerNorm sites; ``attentionDropout``
-    applies to the SELF-attention probabilities only: the cross-attention site has no probability dropout."""
-    FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "hiddenDropout": 0.0, "attentionDropout": 0.0}
+    applies to the SELF-attention probabilities only: the cross-attention site has no probability dropout.
+
+    ``cacheDataType``: None or "fp8", the format of the SELF-attention key/value cache of rnnTimeStep; the stored
+    cross-attention memory projection stays in the compute dtype."""
+    FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "hiddenDropout": 0.0, "attentionDropout": 0.0,
+              "cacheDataType": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType",)
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerDecoderLayerImpl"
 
     def _post_init(self):
         super()._post_init()
         _check_drop_prob(self, "hiddenDropout")
         _check_drop_prob(self, "attentionDropout")
+        _check_cache_dtype(self)
 
     def setNIn(self, inputType, override=False, memoryType=None):
         super().setNIn(inputType, override, memoryType)

@@ -128,6 +128,22 @@ def trim_layers(named, lengths):
                 raise DL4JInvalidInputException(f"{label}: {e}") from None
 
 
+def set_cache_data_type(named, value):
+    """rnnSetCacheDataType of a network over its (label, layer) pairs: every layer whose configuration has
+    ``cacheDataType`` takes ``value`` (None = the compute dtype, "fp8"). A layer that holds a key/value cache refuses,
+    named, before any layer is changed: the stored rows are in the old format."""
+    if value is not None and value != "fp8":
+        raise DL4JInvalidConfigException(f"rnnSetCacheDataType: None (the compute dtype) or \"fp8\", got {value!r}")
+    todo = [(label, l) for label, l in named if "cacheDataType" in type(l.conf)._all_fields()]
+    for label, l in todo:
+        if l.rnnPinInfo() is not None:
+            raise DL4JInvalidInputException(
+                f"rnnSetCacheDataType: {label} ({type(l.conf).__name__}) holds rnnTimeStep state; call "
+                "rnnClearPreviousState() first")
+    for _, l in todo:
+        l.conf.cacheDataType = value
+
+
 def _labelled(label, fn, *a, **kw):
     try:
         return fn(*a, **kw)

@@ -775,6 +775,13 @@ class ComputationGraph(BaseNetwork):
             if hasattr(l, "rnnClearPreviousState"):
                 l.rnnClearPreviousState()
 
+    def rnnSetCacheDataType(self, value):
+        """The format of the rnnTimeStep key/value caches from the next sequence on, as
+        MultiLayerNetwork.rnnSetCacheDataType: None (the compute dtype) or "fp8" on every layer that has
+        ``cacheDataType``. Refused, naming the vertex and changing nothing, while a layer holds state."""
+        from ..generation import set_cache_data_type
+        set_cache_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value)
+
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32
         [mbNew] on the network's device; mbNew may differ from the stored minibatch size). ``groupSize``: the caller

@@ -245,7 +245,15 @@ class KVCacheState:
 
     Ragged batches: after a right-padded chunk ``rnnTrimState(lengths)`` stores ``short[b] = seen - lengths[b]``
     (int32 on the cache's device). ``_kv_len`` stays the upper bound the host counts; row b continues at
-    ``_kv_len - short[b]``, overwriting what its padding left in the cache. The state then carries ``"short"``."""
+    ``_kv_len - short[b]``, overwriting what its padding left in the cache. The state then carries ``"short"``.
+
+    ``cacheDataType="fp8"`` on the layer's configuration: the cache is uint8 ``[mb, Tcap, R]`` in the fp8 row format of
+    csrc/attention_decode.hip (``ops.transformer_native.kv_fp8_row_bytes``), quantised by the append kernel and
+    converted by the decode kernel as it stages; off the kernels the torch path stores and reads the same format.
+    One tensor of 16-byte-multiple rows, so growth, trimming, reordering and pinning treat it as they treat the
+    16-bit cache. A chunk of >= 64 tokens into an empty cache attends over its own unquantised K / V (the flash
+    prompt path; only what it stores is quantised); every other chunk attends over what the cache holds, its own
+    new rows included. The state handed out is ``{"kv": uint8 [mb, L, R], "kvFormat": "fp8"}``."""
     _kv = None
     _kv_len = 0
     _kv_alt = None      # rnnReorderState's second buffer (same shape as _kv, or None): the two are swapped per call
@@ -305,19 +313,33 @@ class KVCacheState:
         self._kv = alt
         self._kv_short = _reorder_short(self._kv_short, parents, groupSize)
 
+    def _kv_fp8(self):
+        return getattr(self.conf, "cacheDataType", None) == "fp8"
+
     def rnnGetPreviousState(self):
         if self._kv is None:
             return {}
         st = {"kv": self._kv[:, :self._kv_len].clone()}
+        if self._kv.dtype == torch.uint8:
+            st["kvFormat"] = "fp8"
         if self._kv_short is not None:
             st["short"] = self._kv_short.clone()
         return st
 
     def rnnSetPreviousState(self, state):
+        """Takes the state in either format (16-bit / float ``kv [mb, L, 2E]``, or uint8 rows with
+        ``"kvFormat": "fp8"``) and converts it to the layer's own (plain torch: not a hot path)."""
         kv = state.get("kv") if state else None
         self.rnnClearPreviousState()
         if kv is None:
             return
+        from ...ops import transformer_native as TN
+        H = self.conf.nHeads
+        if state.get("kvFormat") == "fp8" and not self._kv_fp8():
+            pad = -(-2 * H // 16) * 16
+            kv = TN.kv_fp8_dequantize_reference(kv, H, (kv.shape[2] - pad) // (2 * H), self.compute_dtype)
+        elif state.get("kvFormat") != "fp8" and self._kv_fp8():
+            kv = TN.kv_fp8_quantize_reference(kv, H)
         mb, L, E2 = kv.shape
         self._kv_reserve(mb, E2, L, kv.dtype, kv.device)
         self._kv[:, :L] = kv
@@ -353,14 +375,19 @@ class KVCacheState:
         """Causal attention of the chunk qkv [mb, Tn, 3E] over everything seen since rnnClearPreviousState(): its K / V
         are appended to the cache, its queries attend over the cache. -> [mb, Tn, E]. The decode kernels on a GPU in
         bf16 / fp16 with head size 64 / 128 (the causal flash forward for a prompt of >= 64 tokens into an empty
-        cache), else the torch reference, counted as a fallback on a GPU."""
+        cache), else the torch reference, counted as a fallback on a GPU. With the fp8 cache both paths store the
+        quantised rows and attend over the dequantised cache, except for that prompt chunk."""
         from ...ops import transformer_native as TN
         mb, Tn, E3 = qkv.shape
         E = E3 // 3
         pos, short = self._kv_len, self._kv_short
         if self._kv_pinned:
             _pinned_one_step(self, Tn)
-        self._kv_reserve(mb, 2 * E, pos + Tn, qkv.dtype, qkv.device)
+        fp8 = self._kv_fp8()
+        if fp8:
+            self._kv_reserve(mb, TN.kv_fp8_row_bytes(H, E // H), pos + Tn, torch.uint8, qkv.device)
+        else:
+            self._kv_reserve(mb, 2 * E, pos + Tn, qkv.dtype, qkv.device)
         kv = self._kv
         out = None
         if _native(qkv, "attention") and qkv.is_contiguous() and TN.attn_decode_supported(qkv, kv, H):
@@ -373,13 +400,19 @@ class KVCacheState:
             if qkv.is_cuda:
                 from ...ops import fallback
                 fallback.record("attention", f"{what} head size {E // H} / dtype {qkv.dtype}: torch reference path")
+            new = TN.kv_fp8_quantize_reference(qkv[:, :, E:], H) if fp8 else qkv[:, :, E:]
             if short is None:
-                kv[:, pos:pos + Tn] = qkv[:, :, E:]
+                kv[:, pos:pos + Tn] = new
             else:
                 rows = (pos - short.to(torch.int64)).reshape(mb, 1) + torch.arange(Tn, device=kv.device).reshape(1, Tn)
-                kv[torch.arange(mb, device=kv.device).reshape(mb, 1), rows] = qkv[:, :, E:]
-            out = TN.attention_decode_reference(qkv[:, :, :E], kv[:, :pos + Tn, :E], kv[:, :pos + Tn, E:], H, pos,
-                                                short=short)
+                kv[torch.arange(mb, device=kv.device).reshape(mb, 1), rows] = new
+            if not fp8:
+                seen = kv[:, :pos + Tn]
+            elif pos == 0 and Tn >= 64:
+                seen = qkv[:, :, E:]
+            else:
+                seen = TN.kv_fp8_dequantize_reference(kv[:, :pos + Tn], H, E // H, qkv.dtype)
+            out = TN.attention_decode_reference(qkv[:, :, :E], seen[:, :, :E], seen[:, :, E:], H, pos, short=short)
         if not self._kv_pinned:                  # pinned: the bound stays, the network lowers ``short`` on the device
             self._kv_len = pos + Tn
         return out

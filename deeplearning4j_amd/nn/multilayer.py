@@ -474,6 +474,14 @@ class MultiLayerNetwork(BaseNetwork):
         from .generation import pin_layers
         pin_layers(self, [(f"layer {i}", l) for i, l in enumerate(self.layers)], capacity)
 
+    def rnnSetCacheDataType(self, value):
+        """The format of the rnnTimeStep key/value caches from the next sequence on: None (the compute dtype) or
+        "fp8", set on every layer that has ``cacheDataType`` — a trained or loaded model decodes with an fp8 cache
+        without rebuilding its configuration. Refused, naming the layer and changing nothing, while a layer holds
+        state."""
+        from .generation import set_cache_data_type
+        set_cache_data_type([(f"layer {i}", l) for i, l in enumerate(self.layers)], value)
+
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32
         [mbNew] on the network's device; mbNew may differ from the stored minibatch size). ``groupSize``: the caller

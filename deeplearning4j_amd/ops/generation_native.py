@@ -238,7 +238,7 @@ def cache_gather_native(src, dst, parent, L):
     if not (src.is_cuda and dst.is_cuda and parent.is_cuda and src.dim() == 3 and dst.dim() == 3 and
             src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous() and
             parent.dtype == torch.int32 and parent.is_contiguous() and parent.numel() == dst.shape[0] and
-            src.shape[2] == dst.shape[2] and src.element_size() in (2, 4)):
+            src.shape[2] == dst.shape[2] and src.element_size() in (1, 2, 4)):
         return None
     rc = native.load().dl4j_gen_cache_gather(_ptr(src), _ptr(dst), _ptr(parent), src.shape[0], dst.shape[0],
                                              src.shape[1], dst.shape[1], int(L), src.shape[2], src.element_size(),

@@ -10,7 +10,14 @@
             and 1024, for each minibatch size of ``--batch``: cached ``rnnTimeStep`` one token at a time against ``output()`` on the whole prefix per token
             (the only correct way without the cache). Host clock around work that ends in a device synchronise.
 
-Usage: python tools/bench_decode.py --kernel --model [--out profiles/decode_attention.txt]"""
+  --cache fp8  the fp8 key/value cache against the 16-bit one at the --kernel shapes, default splits, the variants
+            alternating within every pass: the decode attention for one new token (bytes read: L * R per batch row
+            against L * 4E) and the append of one new token; the fp8 output is compared bitwise with the 16-bit kernel
+            on the dequantised cache. With --parent-lib also the 16-bit kernels of a kernel library built from the
+            parent commit.
+
+Usage: python tools/bench_decode.py --kernel --model [--out profiles/decode_attention.txt]
+       python tools/bench_decode.py --cache fp8 [--parent-lib PATH] [--out FILE]"""
 import argparse
 import sys
 import time
@@ -61,6 +68,87 @@ def kernel_mode(passes, sweep, reps):
                 diff = (TN.attn_decode(qkv, kv, H, pos, splits=s).float() - ref).abs().max().item()
                 say(f"B={B:2d} H={H} D={D} L={L:4d} {name:12s}: " + " ".join(f"{v:7.2f}" for v in times[name]) +
                     f" us  median {med:7.2f} us  {nbytes / med / 1e3:7.1f} GB/s  (max diff vs splits=1 {diff:.1e})")
+    say()
+
+
+def _c_calls(lib):
+    """(append, decode) straight on a kernel library's C ABI, argument types set by hand so that the parent commit's
+    library can be driven too; ``fp8`` picks the fp8 entry points."""
+    import ctypes
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    ptr = lambda t: None if t is None else vp(t.data_ptr())      # noqa: E731
+
+    def append(fp8, qkv, kv, B, H, D, pos):
+        f = lib.dl4j_attn_kv_append_fp8_dt if fp8 else lib.dl4j_attn_kv_append_dt
+        f.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+        return f(1, ptr(qkv), ptr(kv), B, 1, H, D, pos, kv.shape[1], vp(torch.cuda.current_stream().cuda_stream))
+
+    def decode(fp8, qkv, kv, out, ws, B, H, D, pos, splits):
+        f = lib.dl4j_attn_decode_fp8_dt if fp8 else lib.dl4j_attn_decode_dt
+        f.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
+        return f(1, ptr(qkv), ptr(kv), ptr(out), ptr(ws), B, 1, H, D, pos, kv.shape[1], splits,
+                 ctypes.c_float(D ** -0.5), vp(torch.cuda.current_stream().cuda_stream))
+    return append, decode
+
+
+def cache_fp8_mode(passes, reps, parent_lib):
+    import ctypes
+    from deeplearning4j_amd.ops import native
+    dev, dt = torch.device("cuda", 0), torch.bfloat16
+    ours = _c_calls(ctypes.CDLL(native.KERNEL_LIB))
+    parent = _c_calls(ctypes.CDLL(parent_lib)) if parent_lib else None
+    say(f"== fp8 key/value cache against the 16-bit cache, Tn = 1, bf16, default splits, GPU time per call in us (mean "
+        f"of {reps} back-to-back launches; median of {passes} passes, min .. max; the variants alternate within a pass)")
+    say("   16-bit / fp8 = this tree's kernels" + ("; parent = the 16-bit kernels of the parent commit's library"
+                                                  if parent else ""))
+    say("   decode bandwidth = bytes of the valid cache rows (L * 4E, fp8 L * R per batch row) / time; a cache that "
+        "fits the last-level caches is re-read from them")
+    H, D = 12, 64
+    E, R = H * D, TN.kv_fp8_row_bytes(12, 64)
+    say(f"   H = {H}, D = {D}: R = {R} bytes per cached token against 4E = {4 * E}, ratio {R / (4 * E):.3f}")
+    for B in (1, 32):
+        for L in (128, 1024, 4096):
+            pos = L - 1
+            g = torch.Generator().manual_seed(L + B)
+            qkv = (torch.randn(B, 1, 3 * E, generator=g) * 0.8).to(dt).to(dev)
+            hist = (torch.randn(B, L, 3 * E, generator=g) * 0.8).to(dt).to(dev)
+            tcap = (L + 63) // 64 * 64
+            kv8 = torch.zeros(B, tcap, R, dtype=torch.uint8, device=dev)
+            assert TN.attn_kv_append(hist, kv8, H, 0) is kv8 and TN.attn_kv_append(qkv, kv8, H, pos) is kv8
+            kv16 = torch.zeros(B, tcap, 2 * E, dtype=dt, device=dev)
+            kv16[:, :L] = TN.kv_fp8_dequantize_reference(kv8[:, :L], H, D, dt)
+            splits = TN.attn_decode_splits(B, 1, H, D, L)
+            ws = torch.empty(max(1, B * H * splits * (D + 2)), dtype=torch.float32, device=dev)
+            variants = [("16-bit", ours, False, kv16), ("fp8", ours, True, kv8)]
+            if parent:
+                variants.insert(0, ("parent", parent, False, kv16))
+            outs = [torch.empty(B, 1, E, dtype=dt, device=dev) for _ in variants]
+            for (_, (_, dec), f8, kv), o in zip(variants, outs):
+                assert dec(f8, qkv, kv, o, ws, B, H, D, pos, splits) == 0
+            torch.cuda.synchronize()
+            same = all(torch.equal(outs[0], o) for o in outs[1:])
+            td, ta = [[] for _ in variants], [[] for _ in variants]
+            for _ in range(passes):
+                for i, (_, (app, dec), f8, kv) in enumerate(variants):
+                    td[i].append(gpu_time(lambda: dec(f8, qkv, kv, outs[i], ws, B, H, D, pos, splits), reps=reps,
+                                          warmup=3) * 1e3)
+                for i, (_, (app, dec), f8, kv) in enumerate(variants):
+                    ta[i].append(gpu_time(lambda: app(f8, qkv, kv, B, H, D, pos), reps=reps, warmup=3) * 1e3)
+            for what, times in (("decode", td), ("append", ta)):
+                line = f"{what} B={B:2d} L={L:4d} splits={splits:2d}:"
+                med = []
+                for (name, _, f8, _), t in zip(variants, times):
+                    t = sorted(t)
+                    med.append(t[len(t) // 2])
+                    line += f"  {name} {med[-1]:7.2f} ({t[0]:.2f} .. {t[-1]:.2f})"
+                    if what == "decode":
+                        line += f" {B * L * (R if f8 else 4 * E) / med[-1] / 1e3:7.1f} GB/s"
+                line += f"  16-bit / fp8 time {med[-2] / med[-1]:5.2f}x"
+                if parent:
+                    line += f"  16-bit / parent time {med[1] / med[0]:5.3f}x"
+                if what == "decode":
+                    line += f"  outputs bitwise equal: {same}"
+                say(line)
     say()
 
 
@@ -132,10 +220,13 @@ def main():
     ap.add_argument("--batch", default="1,32", help="--model: minibatch sizes, comma separated")
     ap.add_argument("--cached-steps", type=int, default=64)
     ap.add_argument("--full-steps", type=int, default=16)
+    ap.add_argument("--cache", choices=["fp8"], default=None,
+                    help="compare the fp8 key/value cache's kernels with the 16-bit ones")
+    ap.add_argument("--parent-lib", default=None, help="--cache: kernel library built from the parent commit")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args()
-    if not (a.kernel or a.model):
-        ap.error("give --kernel and / or --model")
+    if not (a.kernel or a.model or a.cache):
+        ap.error("give --kernel, --model and / or --cache fp8")
     if not torch.cuda.is_available():
         sys.exit("bench_decode.py measures on the GPU; no device found")
     global _out
@@ -146,6 +237,8 @@ def main():
         kernel_mode(a.passes, a.sweep, a.reps)
     if a.model:
         model_mode([int(b) for b in a.batch.split(",")], a.cached_steps, a.full_steps)
+    if a.cache:
+        cache_fp8_mode(max(a.passes, 5), a.reps, a.parent_lib)
     if _out is not None:
         _out.close()
 

@@ -25,9 +25,15 @@
              one-off cost of a graph call (its warm-up step and the capture) and the maxNewTokens from which the
              graph call is the faster one.
 
+  --cache fp8  generate() and generate(useGraph=True) with the fp8 key/value cache against the 16-bit cache on one
+             network (rnnSetCacheDataType switches it between the calls), the four variants alternating within every
+             pass: 12-layer, hidden-768 model with maxPositions 4096 at the batch sizes of --batch (default 32),
+             prefix 1024 and the longest prefix that leaves room for the new tokens; also the cache bytes per layer.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
-       python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]"""
+       python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]
+       python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]"""
 import argparse
 import sys
 import time
@@ -391,6 +397,67 @@ def graph_mode(batches, n, passes, parent_lib):
     say()
 
 
+def cache_fp8_mode(batches, n, passes):
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    from deeplearning4j_amd.ops import transformer_native as TN
+    V, MAXP, H, E = 77, 4096, 12, 768
+    net = TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=E, layers=12, heads=H, maxPositions=MAXP,
+                                    dataType=DataType.BFLOAT16).init(device=DEV)
+    R = TN.kv_fp8_row_bytes(H, E // H)
+    say(f"== generate() with the fp8 key/value cache against the 16-bit cache on TextGenerationTransformer(768, 12 "
+        f"layers, 12 heads, maxPositions {MAXP}), bf16, V = {V}, greedy, {n} new tokens; whole calls (prompt included) "
+        f"on the host clock, ended by a device synchronise; median of {passes} passes (min .. max), the variants "
+        "alternating within a pass; one network, rnnSetCacheDataType between the calls")
+    say(f"   cache bytes per cached token and layer: 16-bit {4 * E}, fp8 {R} ({R / (4 * E):.3f})")
+
+    def call(prompt, cache, **kw):
+        net.rnnClearPreviousState()
+        net.rnnSetCacheDataType(cache)
+        return net.generate(prompt, maxNewTokens=n, **kw)
+
+    for mb in batches:
+        for P in (1024, MAXP - n):
+            prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb + P)).to(DEV)
+            variants = [("16-bit eager", None, {}), ("fp8 eager", "fp8", {}),
+                        ("16-bit graph", None, dict(useGraph=True)), ("fp8 graph", "fp8", dict(useGraph=True))]
+            outs, held = [], []
+            for _, cache, kw in variants:
+                outs.append(call(prompt, cache, **kw).tokens)
+                kv = net.layers_by_name["decoder_0"]._kv
+                held.append(kv.numel() * kv.element_size())
+            agree = [(o == outs[0]).float().mean().item() for o in outs]
+            times = [[] for _ in variants]
+            for _ in range(passes):
+                for i, (_, cache, kw) in enumerate(variants):
+                    times[i].append(_sync_time(lambda: call(prompt, cache, **kw)))
+            med = [sorted(t)[len(t) // 2] for t in times]
+            say(f"batch {mb:2d} prefix {P:4d}: valid cache per layer 16-bit {mb * (P + n) * 4 * E / 1e6:7.1f} MB, fp8 "
+                f"{mb * (P + n) * R / 1e6:7.1f} MB; allocated per layer after the call "
+                + ", ".join(f"{vn} {b / 1e6:.1f} MB" for (vn, _, _), b in zip(variants, held)))
+            for (vn, _, _), t, m, ag in zip(variants, times, med, agree):
+                say(f"    {vn:13s}: {mb * n / m:9.1f} tok/s  {m * 1e3:8.1f} ms per call ({min(t) * 1e3:.1f} .. "
+                    f"{max(t) * 1e3:.1f})  tokens equal to 16-bit eager's: {ag * 100:5.1f} %")
+            say(f"    fp8 / 16-bit tokens/s: eager {med[0] / med[1]:5.3f}x  graph {med[2] / med[3]:5.3f}x   "
+                f"(whole calls: the prompt's forward is in both)")
+            # the steady step alone: a call's time is a + b * tokens, so time n / 4 tokens too
+            few = max(2, n // 4)
+            short = []
+            for _, cache, kw in variants:
+                net.rnnClearPreviousState()
+                net.rnnSetCacheDataType(cache)
+                fn = lambda: net.generate(prompt, maxNewTokens=few, **kw)              # noqa: E731
+                fn()
+                short.append(sorted(_sync_time(fn) for _ in range(passes))[passes // 2])
+            per = [(m - ts) / (n - few) * 1e3 for ts, m in zip(short, med)]
+            say(f"    step alone (against the same calls with {few} tokens): "
+                + ", ".join(f"{vn} {v:5.2f} ms" for (vn, _, _), v in zip(variants, per))
+                + f"; 16-bit / fp8 step time: eager {per[0] / per[1]:5.3f}x  graph {per[2] / per[3]:5.3f}x")
+    net.rnnClearPreviousState()
+    net.rnnSetCacheDataType(None)
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -399,6 +466,8 @@ def main():
     ap.add_argument("--model", action="store_true")
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--cache", choices=["fp8"], default=None,
+                    help="compare generate() with the fp8 key/value cache and with the 16-bit one")
     ap.add_argument("--parent-lib", default=None,
                     help="kernel library built from the parent commit (--ragged, --graph)")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
@@ -421,6 +490,8 @@ def main():
         ragged_model_mode(a.tokens, a.passes)
     if a.graph:
         graph_mode(a.batch, a.tokens, a.passes, a.parent_lib)
+    if a.cache:
+        cache_fp8_mode(a.batch, a.tokens, a.passes)
 
 
 if __name__ == "__main__":
