@@ -7,6 +7,16 @@
 // dqkv[B, T, 3*E] buffer — no permute copies around the kernels. Optional key-padding mask [B, T] (1 = keep), causal
 // masking and attention-probability dropout (the DROP = true instances).
 //
+// Grouped-query attention (the *_gqa_dt entry points): H query heads share Hkv key/value heads, G = H / Hkv an
+// integer, Ekv = Hkv*D; query head h uses kv head h / G. Layouts:
+//   qkv, dqkv [B, T, E + 2*Ekv]   Q of head h at column h*D, K of kv head j at E + j*D, V at E + Ekv + j*D; dqkv is
+//                                 fully written (dK / dV of a kv head are the sums over its group)
+//   out, dout [B, T, E];  lse, dq_dot [B, H, T] indexed by the query head
+//   dropout                       the mask stays keyed by b*H + h with the query head: the mask the multi-head kernel
+//                                 draws on the input whose K / V heads are repeated G times
+// Hkv = H is the layout above and runs the kernels above; Hkv < H runs the GQA = true instances of the same bodies.
+// The forward and dQ results are bitwise those of the multi-head kernels on the repeated input.
+//
 // The kernels here only place these operands; their bodies, the wave mapping, the numerics and the dropout mask are
 // in csrc/attention_body.h, shared with csrc/attention_cross.hip.
 #include "attention_body.h"
@@ -61,26 +71,68 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const hb* __restrict
                                   dqkv + H * D, T * ld3, ld3, T, T, H, scale2, scale, causal, da);
 }
 
+// The grouped forms: qkv rows of E + 2*Ekv columns, K at + E, V Ekv after K; the dK/dV grid is over kv heads.
+template <int D, typename hb, int NB, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_fwd_gqa_kernel(const hb* __restrict__ qkv, const float* __restrict__ mask,
+                                                           hb* __restrict__ out, float* __restrict__ lse, int T, int H,
+                                                           int Hkv, float scale2, int causal, DropArgs da) {
+  const long long ld = (long long)(H + 2 * Hkv) * D;
+  attn_fwd_body<D, hb, NB, DROP, true>(qkv, T * ld, ld, qkv + H * D, T * ld, ld, mask, out, lse, T, T, H, scale2,
+                                       causal, da, H / Hkv, Hkv * D);
+}
+
+template <int D, typename hb, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_bwd_dq_gqa_kernel(const hb* __restrict__ qkv, const hb* __restrict__ dout,
+                                                              const float* __restrict__ mask,
+                                                              const float* __restrict__ lse,
+                                                              const float* __restrict__ dq_dot, hb* __restrict__ dqkv,
+                                                              int T, int H, int Hkv, float scale2, float scale,
+                                                              int causal, DropArgs da) {
+  const long long ld = (long long)(H + 2 * Hkv) * D;
+  attn_bwd_dq_body<D, hb, DROP, true>(qkv, T * ld, ld, qkv + H * D, T * ld, ld, dout, mask, lse, dq_dot, dqkv, T * ld,
+                                      ld, T, T, H, scale2, scale, causal, da, H / Hkv, Hkv * D);
+}
+
+template <int D, typename hb, bool DROP = false>
+__global__ void __launch_bounds__(256) attn_bwd_dkdv_gqa_kernel(const hb* __restrict__ qkv,
+                                                                const hb* __restrict__ dout,
+                                                                const float* __restrict__ mask,
+                                                                const float* __restrict__ lse,
+                                                                const float* __restrict__ dq_dot,
+                                                                hb* __restrict__ dqkv, int T, int H, int Hkv,
+                                                                float scale2, float scale, int causal, DropArgs da) {
+  const long long ld = (long long)(H + 2 * Hkv) * D;
+  attn_bwd_dkdv_body<D, hb, DROP, true>(qkv, T * ld, ld, qkv + H * D, T * ld, ld, dout, mask, lse, dq_dot,
+                                        dqkv + H * D, T * ld, ld, T, T, H, scale2, scale, causal, da, H / Hkv,
+                                        Hkv * D);
+}
+
 // ------------------------------------------------------------------------------------------------ launch
+static bool gqa_heads_ok(int H, int Hkv) { return H >= 1 && Hkv >= 1 && H % Hkv == 0; }
+
 template <bool DROP>
-static int fwd_dispatch(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H, int D,
-                        float scale, int causal, DropArgs da, hipStream_t s) {
-  if (B < 1 || T < 1 || H < 1) return -1;
+static int fwd_dispatch(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H,
+                        int Hkv, int D, float scale, int causal, DropArgs da, hipStream_t s) {
+  if (B < 1 || T < 1 || !gqa_heads_ok(H, Hkv)) return -1;
   return attn_dispatch(dt, D, [&](auto d, auto e) {
     constexpr int DD = decltype(d)::value, NB = DD == 64 ? 2 : 1;
     using hb = typename decltype(e)::type;
     const dim3 grid((T + BLK - 1) / BLK, B * H);
-    hipLaunchKernelGGL((attn_fwd_kernel<DD, hb, NB, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, mask, (hb*)out, lse,
-                       T, H, scale * kLog2e, causal, da);
+    if (Hkv == H)
+      hipLaunchKernelGGL((attn_fwd_kernel<DD, hb, NB, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, mask, (hb*)out,
+                         lse, T, H, scale * kLog2e, causal, da);
+    else
+      hipLaunchKernelGGL((attn_fwd_gqa_kernel<DD, hb, NB, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, mask,
+                         (hb*)out, lse, T, H, Hkv, scale * kLog2e, causal, da);
     return (int)hipGetLastError();
   });
 }
 
 template <bool DROP>
 static int bwd_dispatch(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
-                        const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int D, float scale,
+                        const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int Hkv, int D, float scale,
                         int causal, DropArgs da, hipStream_t s) {
-  if (B < 1 || T < 1 || H < 1) return -1;
+  if (B < 1 || T < 1 || !gqa_heads_ok(H, Hkv)) return -1;
   return attn_dispatch(dt, D, [&](auto d, auto e) {
     constexpr int DD = decltype(d)::value;
     using hb = typename decltype(e)::type;
@@ -88,10 +140,18 @@ static int bwd_dispatch(int dt, const void* qkv, const void* out, const void* do
     hipLaunchKernelGGL((attn_bwd_pre_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                        (const hb*)out, (const hb*)dout, dq_dot, B, T, H);
     const dim3 grid((T + BLK - 1) / BLK, B * H);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout,
-                       mask, lse, dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal, da);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout,
-                       mask, lse, dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal, da);
+    if (Hkv == H) {
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout,
+                         mask, lse, dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal, da);
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)dout,
+                         mask, lse, dq_dot, (hb*)dqkv, T, H, scale * kLog2e, scale, causal, da);
+    } else {
+      const dim3 gridkv((T + BLK - 1) / BLK, B * Hkv);
+      hipLaunchKernelGGL((attn_bwd_dkdv_gqa_kernel<DD, hb, DROP>), gridkv, dim3(256), 0, s, (const hb*)qkv,
+                         (const hb*)dout, mask, lse, dq_dot, (hb*)dqkv, T, H, Hkv, scale * kLog2e, scale, causal, da);
+      hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<DD, hb, DROP>), grid, dim3(256), 0, s, (const hb*)qkv,
+                         (const hb*)dout, mask, lse, dq_dot, (hb*)dqkv, T, H, Hkv, scale * kLog2e, scale, causal, da);
+    }
     return (int)hipGetLastError();
   });
 }
@@ -112,14 +172,31 @@ static bool drop_args(float drop, unsigned long long seed, const long long* offs
 // -1 = unsupported shape / dtype.
 DL4J_API int dl4j_attn_fwd_dt(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H,
                               int D, float scale, int causal, hipStream_t s) {
-  return fwd_dispatch<false>(dt, qkv, mask, out, lse, B, T, H, D, scale, causal, DropArgs{}, s);
+  return fwd_dispatch<false>(dt, qkv, mask, out, lse, B, T, H, H, D, scale, causal, DropArgs{}, s);
+}
+
+// Grouped heads (the layouts at the top of this file): qkv [B,T,(H+2*Hkv)*D]; out, lse as above. -1 also for Hkv < 1,
+// H % Hkv != 0 or operands not 16-byte aligned.
+DL4J_API int dl4j_attn_fwd_gqa_dt(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T,
+                                  int H, int Hkv, int D, float scale, int causal, hipStream_t s) {
+  if (!attn_aligned16({qkv, out})) return -1;
+  return fwd_dispatch<false>(dt, qkv, mask, out, lse, B, T, H, Hkv, D, scale, causal, DropArgs{}, s);
 }
 
 // dout [B,T,H*D]; dq_dot: fp32 workspace [B,H,T]; dqkv [B,T,3*H*D] (fully written).
 DL4J_API int dl4j_attn_bwd_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
                               const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int D, float scale,
                               int causal, hipStream_t s) {
-  return bwd_dispatch<false>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, D, scale, causal, DropArgs{}, s);
+  return bwd_dispatch<false>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, H, D, scale, causal, DropArgs{}, s);
+}
+
+// Grouped heads: qkv, dqkv [B,T,(H+2*Hkv)*D] (dqkv fully written); dq_dot, lse [B,H,T]. Status as dl4j_attn_fwd_gqa_dt.
+DL4J_API int dl4j_attn_bwd_gqa_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                                  const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int Hkv, int D,
+                                  float scale, int causal, hipStream_t s) {
+  if (!attn_aligned16({qkv, out, dout, dqkv})) return -1;
+  return bwd_dispatch<false>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale, causal, DropArgs{},
+                             s);
 }
 
 // The same with attention-probability dropout (drop probability in [0, 1), see the mask definition in
@@ -130,7 +207,15 @@ DL4J_API int dl4j_attn_fwd_drop_dt(int dt, const void* qkv, const float* mask, v
                                    const long long* offset, hipStream_t s) {
   DropArgs da;
   if (!drop_args(drop, seed, offset, &da)) return -1;
-  return fwd_dispatch<true>(dt, qkv, mask, out, lse, B, T, H, D, scale, causal, da, s);
+  return fwd_dispatch<true>(dt, qkv, mask, out, lse, B, T, H, H, D, scale, causal, da, s);
+}
+
+DL4J_API int dl4j_attn_fwd_drop_gqa_dt(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T,
+                                       int H, int Hkv, int D, float scale, int causal, float drop,
+                                       unsigned long long seed, const long long* offset, hipStream_t s) {
+  DropArgs da;
+  if (!drop_args(drop, seed, offset, &da) || !attn_aligned16({qkv, out})) return -1;
+  return fwd_dispatch<true>(dt, qkv, mask, out, lse, B, T, H, Hkv, D, scale, causal, da, s);
 }
 
 DL4J_API int dl4j_attn_bwd_drop_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
@@ -139,7 +224,16 @@ DL4J_API int dl4j_attn_bwd_drop_dt(int dt, const void* qkv, const void* out, con
                                    const long long* offset, hipStream_t s) {
   DropArgs da;
   if (!drop_args(drop, seed, offset, &da)) return -1;
-  return bwd_dispatch<true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, D, scale, causal, da, s);
+  return bwd_dispatch<true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, H, D, scale, causal, da, s);
+}
+
+DL4J_API int dl4j_attn_bwd_drop_gqa_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                                       const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int Hkv,
+                                       int D, float scale, int causal, float drop, unsigned long long seed,
+                                       const long long* offset, hipStream_t s) {
+  DropArgs da;
+  if (!drop_args(drop, seed, offset, &da) || !attn_aligned16({qkv, out, dout, dqkv})) return -1;
+  return bwd_dispatch<true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale, causal, da, s);
 }
 
 // Test / debug only: keep [B*H, T, T] uint8 (1 = kept) of the mask the DROP kernels apply. Never part of a step.

@@ -10,6 +10,12 @@
 //   dQ / dK likewise, dV at dK + E;  out, dout [B,Tq,E];  mask [B,Tk] fp32 (1 = keep) or null;  lse, dq_dot [B,H,Tq].
 // Query rows are bounded by Tq and key rows by Tk, never one by the other; self attention passes Tq = Tk = T.
 //
+// Grouped-query attention (the GQA = true instances of the three bodies; csrc/attention.hip has the layouts): H query
+// heads share Hkv = H / G key/value heads, query head h uses kv head h / G. K of kv head j sits at kp + j*D and V
+// v_off elements after it (an operand, Ekv = Hkv*D in a cache, the same in the fused projection); dK likewise, dV at
+// dK + v_off. lse, dq_dot and the dropout mask stay indexed by the QUERY head. With GQA = false G is the constant 1
+// and v_off the constant E: those instances are the kernels as they were, not a run-time special case.
+//
 // CDNA4 mapping (per 64-wide wave, v_mfma_f32_16x16x32_{bf16,f16}):
 //  * forward / dQ: grid (ceil(Tq/64), B*H); a wave owns 16 queries. Scores are computed TRANSPOSED, Sᵀ = K·Qᵀ, so the
 //    query is the lane's accumulator column: the online-softmax state (running max m, sum l) is one scalar per lane and
@@ -103,12 +109,12 @@ __device__ __forceinline__ void attn_store_tile(hb* row, const f4_t (&acc)[D / 1
   }
 }
 
-// One 64-row block of K and V (V at K + E), D/32 16-byte chunks of each per thread of a 256-thread block: first into
-// registers (rows at or beyond `rows` read as zeros), then K row-major into Kj and V transposed into Vtj, so a caller
-// can keep the loads of one block in flight while it works on another.
+// One 64-row block of K and V (V at K + v_off), D/32 16-byte chunks of each per thread of a 256-thread block: first
+// into registers (rows at or beyond `rows` read as zeros), then K row-major into Kj and V transposed into Vtj, so a
+// caller can keep the loads of one block in flight while it works on another.
 template <int D, typename hb>
 __device__ __forceinline__ void attn_kv_fetch(V8<hb> (&kr)[D / 32], V8<hb> (&vr)[D / 32], const hb* kbase,
-                                              long long k_ld, int E, int row0, int rows) {
+                                              long long k_ld, int v_off, int row0, int rows) {
   constexpr int CPR = D / 8;
 #pragma unroll
   for (int it = 0; it < D / 32; ++it) {
@@ -116,7 +122,7 @@ __device__ __forceinline__ void attn_kv_fetch(V8<hb> (&kr)[D / 32], V8<hb> (&vr)
     const bool ok = row0 + r < rows;
     const hb* src = kbase + (long long)(ok ? row0 + r : 0) * k_ld + c * 8;
     kr[it] = ok ? ld8(src) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-    vr[it] = ok ? ld8(src + E) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+    vr[it] = ok ? ld8(src + v_off) : V8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
   }
 }
 template <int D, typename hb>
@@ -140,10 +146,11 @@ __device__ __forceinline__ void attn_kv_stash(hb* Kj, hb* Vtj, int ldv, const V8
 // The masking and online-softmax update is written out here: as a helper function it is optimised on its own before
 // it is inlined, its exp2 / add order changes, and the D = 64 instances go from 116-124 to 132-136 VGPRs, one wave per
 // SIMD less.
-template <int D, typename hb, int NB, bool DROP>
+template <int D, typename hb, int NB, bool DROP, bool GQA = false>
 __device__ __forceinline__ void attn_fwd_body(const hb* qp, long long q_bs, long long q_ld, const hb* kp,
                                               long long k_bs, long long k_ld, const float* mask, hb* out, float* lse,
-                                              int Tq, int Tk, int H, float scale2, int causal, DropArgs da) {
+                                              int Tq, int Tk, int H, float scale2, int causal, DropArgs da,
+                                              int Garg = 1, int v_off_arg = 0) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = NB * BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Ks[NB * BLK * LDK];
@@ -151,7 +158,8 @@ __device__ __forceinline__ void attn_fwd_body(const hb* qp, long long q_bs, long
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, hgrp = lane >> 4;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int E = H * D;
-  const hb* kbase = kp + (long long)b * k_bs + h * D;
+  const int v_off = GQA ? v_off_arg : E;
+  const hb* kbase = kp + (long long)b * k_bs + (GQA ? h / Garg : h) * D;
   const int q = blockIdx.x * BLK + wave * 16 + col;
   const int qc = min(q, Tq - 1);
   V8<hb> qf[KS];
@@ -169,7 +177,7 @@ __device__ __forceinline__ void attn_fwd_body(const hb* qp, long long q_bs, long
     __syncthreads();
     V8<hb> kr[NB][KS], vr[NB][KS];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) attn_kv_fetch<D>(kr[j], vr[j], kbase, k_ld, E, (kb0 + j) * BLK, rows);
+    for (int j = 0; j < NB; ++j) attn_kv_fetch<D>(kr[j], vr[j], kbase, k_ld, v_off, (kb0 + j) * BLK, rows);
 #pragma unroll
     for (int j = 0; j < NB; ++j) attn_kv_stash<D>(Ks + j * BLK * LDK, Vt + j * BLK, LDV, kr[j], vr[j]);
     __syncthreads();
@@ -253,12 +261,12 @@ __global__ void __launch_bounds__(256) attn_bwd_pre_kernel(const hb* __restrict_
 }
 
 // dQ per query block (forward orientation: query on the lane). DROP: dS = P o (D o dP - Delta), D in {0, 1/keep_eff}.
-template <int D, typename hb, bool DROP>
+template <int D, typename hb, bool DROP, bool GQA = false>
 __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, long long q_ld, const hb* kp,
                                                  long long k_bs, long long k_ld, const hb* dout, const float* mask,
                                                  const float* lse, const float* dq_dot, hb* dq, long long dq_bs,
                                                  long long dq_ld, int Tq, int Tk, int H, float scale2, float scale,
-                                                 int causal, DropArgs da) {
+                                                 int causal, DropArgs da, int Garg = 1, int v_off_arg = 0) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDT = BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Ks[BLK * LDK];
@@ -267,7 +275,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, hgrp = lane >> 4;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int E = H * D;
-  const hb* kbase = kp + (long long)b * k_bs + h * D;
+  const int v_off = GQA ? v_off_arg : E;
+  const hb* kbase = kp + (long long)b * k_bs + (GQA ? h / Garg : h) * D;
   const int q = blockIdx.x * BLK + wave * 16 + col;
   const int qc = min(q, Tq - 1);
   V8<hb> qf[KS], df[KS];
@@ -285,7 +294,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();
     stage_rows<D>(Ks, LDK, kbase, k_ld, kb * BLK, Tk);
-    stage_rows<D>(Vs, LDK, kbase + E, k_ld, kb * BLK, Tk);
+    stage_rows<D>(Vs, LDK, kbase + v_off, k_ld, kb * BLK, Tk);
     stage_rows_t<D>(Kt, LDT, kbase, k_ld, kb * BLK, Tk);
     __syncthreads();
     f4_t s[4], dp[4];
@@ -321,12 +330,15 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
 
 // dK, dV per key block (key on the lane), looping over the query blocks of Tq. DROP: dV = (P o D)^T dO (dropped P
 // zeroed, 1/keep_eff folded into the final store), dS as in the dQ body.
-template <int D, typename hb, bool DROP>
+// GQA: grid.y is B*Hkv; the block loads its K / V fragments once and runs the query-block loop for each query head
+// g = 0 .. G-1 of its group in that fixed order (that head's Q, dO, lse, dq_dot and dropout tile), dK and dV
+// accumulating in the same fp32 registers and stored once: no atomics, no workspace, bitwise reproducible.
+template <int D, typename hb, bool DROP, bool GQA = false>
 __device__ __forceinline__ void attn_bwd_dkdv_body(const hb* qp, long long q_bs, long long q_ld, const hb* kp,
                                                    long long k_bs, long long k_ld, const hb* dout, const float* mask,
                                                    const float* lse, const float* dq_dot, hb* dk_out, long long dk_bs,
                                                    long long dk_ld, int Tq, int Tk, int H, float scale2, float scale,
-                                                   int causal, DropArgs da) {
+                                                   int causal, DropArgs da, int Garg = 1, int v_off_arg = 0) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDQ = D + 8, LDT = BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Qs[BLK * LDQ];
@@ -335,10 +347,10 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const hb* qp, long long q_bs,
   __shared__ __attribute__((aligned(16))) hb Dt[D * LDT];
   __shared__ float Ls[BLK], Dd[BLK];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, hgrp = lane >> 4;
-  const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+  const int G = GQA ? Garg : 1, Hkv = GQA ? H / G : H;
+  const int bj = blockIdx.y, b = bj / Hkv, j = bj - b * Hkv;   // kv head j; without GQA it is the query head
   const int E = H * D;
-  const hb* qbase = qp + (long long)b * q_bs + h * D;
-  const hb* dbase = dout + (long long)b * Tq * E + h * D;
+  const int v_off = GQA ? v_off_arg : E;
   const int key = blockIdx.x * BLK + wave * 16 + col;
   const int kc = min(key, Tk - 1);
   unsigned drop_off = 0;
@@ -346,67 +358,73 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const hb* qp, long long q_bs,
   bool kvalid = key < Tk;
   if (kvalid && mask) kvalid = mask[(long long)b * Tk + key] != 0.f;
   V8<hb> kf[KS], vf[KS];
-  const hb* krow = kp + (long long)b * k_bs + (long long)kc * k_ld + h * D;
+  const hb* krow = kp + (long long)b * k_bs + (long long)kc * k_ld + j * D;
   attn_ld_frag<D>(kf, krow, hgrp);
-  attn_ld_frag<D>(vf, krow + E, hgrp);
+  attn_ld_frag<D>(vf, krow + v_off, hgrp);
   f4_t dk[DT], dv[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dk[dt] = dv[dt] = f4_t{0.f, 0.f, 0.f, 0.f};
   const int nqb = (Tq + BLK - 1) / BLK;
   const int qb0 = causal ? blockIdx.x : 0;                     // queries before the key block see none of it
-  for (int qb = qb0; qb < nqb; ++qb) {
-    __syncthreads();
-    stage_rows<D>(Qs, LDQ, qbase, q_ld, qb * BLK, Tq);
-    stage_rows<D>(Ds, LDQ, dbase, E, qb * BLK, Tq);
-    stage_rows_t<D>(Qt, LDT, qbase, q_ld, qb * BLK, Tq);
-    stage_rows_t<D>(Dt, LDT, dbase, E, qb * BLK, Tq);
-    if (threadIdx.x < BLK) {
-      const int qq = min(qb * BLK + (int)threadIdx.x, Tq - 1);
-      Ls[threadIdx.x] = lse[(long long)bh * Tq + qq];
-      Dd[threadIdx.x] = dq_dot[(long long)bh * Tq + qq];
-    }
-    __syncthreads();
-    f4_t s[4], dp[4], ds[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      s[mt] = attn_score_tile<D>(Qs, kf, mt, col, hgrp);
-      dp[mt] = attn_score_tile<D>(Ds, vf, mt, col, hgrp);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      uint4 dtile = make_uint4(0, 0, 0, 0);
-      if constexpr (DROP)
-        dtile = attn_drop_tile(da.seed, drop_off, (unsigned)bh, (unsigned)(qb * 16 + mt * 4 + hgrp),
-                               (unsigned)key >> 2);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int qi = mt * 16 + hgrp * 4 + r, q = qb * BLK + qi;
-        const bool ok = kvalid && q < Tq && (!causal || key <= q);
-        const float p = ok ? exp2f(s[mt][r] * scale2 - Ls[qi]) : 0.f;
-        float dpv = dp[mt][r];
-        bool keep = true;
-        if constexpr (DROP) {
-          keep = attn_drop_keep(attn_drop_word(dtile, r), key & 3, da.thr);
-          dpv = keep ? dpv * da.inv_keep : 0.f;
-        }
-        s[mt][r] = keep ? p : 0.f;
-        ds[mt][r] = p * (dpv - Dd[qi]);
+  for (int g = 0; g < G; ++g) {
+    const int h = GQA ? j * G + g : j;
+    const int bh = GQA ? b * H + h : bj;
+    const hb* qbase = qp + (long long)b * q_bs + h * D;
+    const hb* dbase = dout + (long long)b * Tq * E + h * D;
+    for (int qb = qb0; qb < nqb; ++qb) {
+      __syncthreads();
+      stage_rows<D>(Qs, LDQ, qbase, q_ld, qb * BLK, Tq);
+      stage_rows<D>(Ds, LDQ, dbase, E, qb * BLK, Tq);
+      stage_rows_t<D>(Qt, LDT, qbase, q_ld, qb * BLK, Tq);
+      stage_rows_t<D>(Dt, LDT, dbase, E, qb * BLK, Tq);
+      if (threadIdx.x < BLK) {
+        const int qq = min(qb * BLK + (int)threadIdx.x, Tq - 1);
+        Ls[threadIdx.x] = lse[(long long)bh * Tq + qq];
+        Dd[threadIdx.x] = dq_dot[(long long)bh * Tq + qq];
       }
-    }
+      __syncthreads();
+      f4_t s[4], dp[4], ds[4];
 #pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {                             // dVᵀ += dOᵀ·P, dKᵀ += Qᵀ·dS
-      attn_pv_half<D>(dv, pack2<hb>(s[2 * k2], s[2 * k2 + 1]), Dt + 32 * k2, LDT, col, hgrp);
-      attn_pv_half<D>(dk, pack2<hb>(ds[2 * k2], ds[2 * k2 + 1]), Qt + 32 * k2, LDT, col, hgrp);
+      for (int mt = 0; mt < 4; ++mt) {
+        s[mt] = attn_score_tile<D>(Qs, kf, mt, col, hgrp);
+        dp[mt] = attn_score_tile<D>(Ds, vf, mt, col, hgrp);
+      }
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        uint4 dtile = make_uint4(0, 0, 0, 0);
+        if constexpr (DROP)
+          dtile = attn_drop_tile(da.seed, drop_off, (unsigned)bh, (unsigned)(qb * 16 + mt * 4 + hgrp),
+                                 (unsigned)key >> 2);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qi = mt * 16 + hgrp * 4 + r, q = qb * BLK + qi;
+          const bool ok = kvalid && q < Tq && (!causal || key <= q);
+          const float p = ok ? exp2f(s[mt][r] * scale2 - Ls[qi]) : 0.f;
+          float dpv = dp[mt][r];
+          bool keep = true;
+          if constexpr (DROP) {
+            keep = attn_drop_keep(attn_drop_word(dtile, r), key & 3, da.thr);
+            dpv = keep ? dpv * da.inv_keep : 0.f;
+          }
+          s[mt][r] = keep ? p : 0.f;
+          ds[mt][r] = p * (dpv - Dd[qi]);
+        }
+      }
+#pragma unroll
+      for (int k2 = 0; k2 < 2; ++k2) {                           // dVᵀ += dOᵀ·P, dKᵀ += Qᵀ·dS
+        attn_pv_half<D>(dv, pack2<hb>(s[2 * k2], s[2 * k2 + 1]), Dt + 32 * k2, LDT, col, hgrp);
+        attn_pv_half<D>(dk, pack2<hb>(ds[2 * k2], ds[2 * k2 + 1]), Qt + 32 * k2, LDT, col, hgrp);
+      }
     }
   }
   if (key < Tk) {
-    hb* dst = dk_out + (long long)b * dk_bs + (long long)key * dk_ld + h * D;
+    hb* dst = dk_out + (long long)b * dk_bs + (long long)key * dk_ld + j * D;
     attn_store_tile<D>(dst, dk, scale, hgrp);
     if constexpr (DROP) {   // its own fp32 multiply: as the store's factor it fuses with the fp16 conversion
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) dv[dt] *= da.inv_keep;
     }
-    attn_store_tile<D>(dst + E, dv, 1.f, hgrp);
+    attn_store_tile<D>(dst + v_off, dv, 1.f, hgrp);
   }
 }
 

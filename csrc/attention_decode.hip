@@ -33,6 +33,24 @@
 //    the row's two scale bytes and converts while staging (v_cvt_scalef32_pk_{bf16,f16}_fp8), writing the same Ks / Vt
 //    images — from the first barrier on the two are one code, so the fp8 kernel gives the bits of the 16-bit kernel
 //    on the dequantised cache.
+//
+// Grouped-query attention (the *_gqa_dt entry points): H query heads share Hkv key/value heads, G = H / Hkv an
+// integer, Ekv = Hkv*D; query head h uses kv head h / G. Layouts:
+//   qkv [B, Tn, E + 2*Ekv]        Q of head h at column h*D, K of kv head j at E + j*D, V at E + Ekv + j*D
+//   kv [B, Tcap, 2*Ekv]           K of kv head j at column j*D, V at Ekv + j*D
+//   kv8 [B, Tcap, R] bytes        R = 2*Ekv + roundup16(2*Hkv): the fp8 format above with Hkv heads (same groups,
+//                                 scales and codes)
+//   out [B, Tn, E]
+//  * The append kernels take the source row width and the K column offset and copy / quantise 2*Ekv columns.
+//  * Decode: grid (splits, B*Hkv, ceil(Tn*G/64)). The 64 lane-columns of a block are SLOTS r = i*G + g, query-major:
+//    chunk query i = r / G, group member g = r % G. A lane loads the Q fragment of row i, head j*G + g, cuts at
+//    key <= pos + i and writes out[b, i, (j*G + g)*D ..]; the block stages each 64-key block of kv head j once for
+//    all of them, so the cache bytes read per step shrink by G and at Tn = 1 the G query heads fill lanes and waves
+//    that only staged. A wave is active when any of its 16 slots is below Tn*G; the tile's last visible key block
+//    follows from its largest i. Split partials go to the workspace slot of (b*H + h, i, split), so the merge kernel
+//    is the one above. Staging, prefetch, online softmax and the cache policies are the one body: G = 1 (GQA = false)
+//    is a compile-time constant there and gives the multi-head kernels as they were; for a given split count the GQA
+//    result is bitwise what those give on the cache with every kv head repeated G times.
 #include "attention_body.h"
 
 // ------------------------------------------------------------------------------------------------ cache policies
@@ -90,10 +108,11 @@ template <int D, typename hb> struct KvCacheFp8 {
 // holding (m, l)
 // The body takes the position of its own batch row: the uniform kernel passes the host's pos, the ragged one
 // pos - shortfall[b] (everything below — key-block count, split ranges, causal cut, zero staging — follows from it).
-template <int D, typename hb, typename CP = KvCache16<D, hb>>
+// GQA: the cache side (row stride, V offset, scale bytes) is that of Hkv heads, the lane-columns are slots.
+template <int D, typename hb, typename CP = KvCache16<D, hb>, bool GQA = false>
 __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, const typename CP::elem* __restrict__ kv,
                                                  hb* __restrict__ out, float* __restrict__ ws, int Tn, int H, int pos,
-                                                 int Tcap, int S, float scale2) {
+                                                 int Tcap, int S, float scale2, int Garg = 1) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = BLK + 8;
   constexpr int CPR = CP::CPR, PER = BLK * CPR / 256;            // 16-byte chunks per row / per thread per block
@@ -101,15 +120,20 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
   __shared__ __attribute__((aligned(16))) hb Ks[BLK * LDK];
   __shared__ __attribute__((aligned(16))) hb Vt[D * LDV];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, hgrp = lane >> 4;
-  const int split = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh - b * H;
-  const int E = H * D, L = pos + Tn;
-  const long long ld3 = 3LL * E, ld2 = CP::row_ld(E, H);
-  const hb* qbase = qkv + (long long)b * Tn * ld3 + h * D;
-  const typename CP::elem* kbase = kv + (long long)b * Tcap * ld2 + h * D;
+  const int G = GQA ? Garg : 1, Hkv = GQA ? H / G : H;           // the cache holds Hkv heads
+  const int split = blockIdx.x, bj = blockIdx.y, b = bj / Hkv, j = bj - b * Hkv;
+  const int E = H * D, Ekv = GQA ? Hkv * D : E, L = pos + Tn;
+  const long long ld3 = GQA ? (long long)E + 2LL * Ekv : 3LL * E, ld2 = CP::row_ld(Ekv, Hkv);
+  const typename CP::elem* kbase = kv + (long long)b * Tcap * ld2 + j * D;
   const int q0 = blockIdx.z * BLK;
-  const int qi = q0 + wave * 16 + col;                           // index in the chunk; its position is pos + qi
-  const bool active = q0 + wave * 16 < Tn;                       // wave-uniform: any query of this wave's 16 exists
+  const int slot = q0 + wave * 16 + col;                         // r = i*G + g
+  const int nslots = GQA ? Tn * G : Tn;
+  const int qi = GQA ? slot / G : slot;                          // index in the chunk; its position is pos + qi
+  const int h = GQA ? j * G + (slot - qi * G) : j;               // the lane's query head
+  const int bh = GQA ? b * H + h : bj;
+  const bool active = q0 + wave * 16 < nslots;                   // wave-uniform: any slot of this wave's 16 exists
   const int qc = min(qi, Tn - 1);
+  const hb* qbase = qkv + (long long)b * Tn * ld3 + h * D;
   V8<hb> qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) qf[ks] = ld8(qbase + (long long)qc * ld3 + ks * 32 + 8 * hgrp);
@@ -120,7 +144,8 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
   // this split's key blocks, cut at the last block any query of the tile can see
   const int nkb = (L + BLK - 1) / BLK;
   const int kb_lo = (int)((long long)split * nkb / S);
-  const int kb_hi = min((int)((long long)(split + 1) * nkb / S), (pos + min(q0 + BLK, Tn) - 1) / BLK + 1);
+  const int i_hi = GQA ? (min(q0 + BLK, nslots) - 1) / G : min(q0 + BLK, Tn) - 1;   // the tile's largest query
+  const int kb_hi = min((int)((long long)(split + 1) * nkb / S), (pos + i_hi) / BLK + 1);
   typename CP::chunk kr[PER], vr[PER];
   typename CP::scale_t ksc[PER], vsc[PER];
   auto fetch = [&](int kb) {
@@ -131,10 +156,10 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
       const bool ok = row < L;                                   // rows past the valid length are staged as zeros
       const typename CP::elem* src = kbase + (long long)(ok ? row : 0) * ld2 + c * CP::CW;
       kr[it] = ok ? CP::load(src) : CP::zero();
-      vr[it] = ok ? CP::load(src + E) : CP::zero();
+      vr[it] = ok ? CP::load(src + Ekv) : CP::zero();
       if constexpr (NV > 1) {
-        ksc[it] = ok ? CP::load_scale(src - c * CP::CW, E, H, h, false) : typename CP::scale_t{};
-        vsc[it] = ok ? CP::load_scale(src - c * CP::CW, E, H, h, true) : typename CP::scale_t{};
+        ksc[it] = ok ? CP::load_scale(src - c * CP::CW, Ekv, Hkv, j, false) : typename CP::scale_t{};
+        vsc[it] = ok ? CP::load_scale(src - c * CP::CW, Ekv, Hkv, j, true) : typename CP::scale_t{};
       }
     }
   };
@@ -213,13 +238,13 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
     }
     return;
   }
-  const long long slot = ((long long)bh * Tn + qi) * S + split;
-  const long long nslot = (long long)gridDim.y * Tn * S;
+  const long long wslot = ((long long)bh * Tn + qi) * S + split;
+  const long long nslot = (long long)gridDim.y * G * Tn * S;     // B*H*Tn*S
   if (hgrp == 0) {
-    ws[nslot * D + slot * 2] = m;
-    ws[nslot * D + slot * 2 + 1] = l;
+    ws[nslot * D + wslot * 2] = m;
+    ws[nslot * D + wslot * 2 + 1] = l;
   }
-  float* arow = ws + slot * D;
+  float* arow = ws + wslot * D;
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f4_t*>(arow + dt * 16 + hgrp * 4) = acc[dt];
 }
@@ -260,6 +285,19 @@ __global__ void __launch_bounds__(256) attn_decode_fp8_ragged_kernel(const hb* _
   const int b = blockIdx.y / H;
   attn_decode_body<D, hb, KvCacheFp8<D, hb>>(qkv, kv8, out, ws, Tn, H, pos - min(max(shortfall[b], 0), pos), Tcap, S,
                                              scale2);
+}
+
+// Grouped heads, all four variants (CP: 16-bit or fp8 cache; shortfall null = every row at pos): grid.y = B*Hkv,
+// grid.z tiles the Tn*G slots.
+template <int D, typename hb, typename CP>
+__global__ void __launch_bounds__(256) attn_decode_gqa_kernel(const hb* __restrict__ qkv,
+                                                              const typename CP::elem* __restrict__ kv,
+                                                              hb* __restrict__ out, float* __restrict__ ws, int Tn,
+                                                              int H, int Hkv, int pos, int Tcap, int S, float scale2,
+                                                              const int* __restrict__ shortfall) {
+  const int b = blockIdx.y / Hkv;
+  const int pb = shortfall ? pos - min(max(shortfall[b], 0), pos) : pos;
+  attn_decode_body<D, hb, CP, true>(qkv, kv, out, ws, Tn, H, pb, Tcap, S, scale2, H / Hkv);
 }
 
 // out[b, q, h*D + d] = sum_s acc_s[d] 2^(m_s - M) / sum_s l_s 2^(m_s - M), M = max_s m_s, in the order s = 0 .. S-1;
@@ -315,23 +353,25 @@ __global__ void __launch_bounds__(256) attn_decode_combine_kernel(const float* _
   *reinterpret_cast<V4<hb>*>(out + ((b * Tn + q) * H + h) * D + d4 * 4) = v;
 }
 
-// In 16-byte chunks (EC per E columns): chunk c of the 2E K|V columns of qkv row (b, t) -> kv row (b, pos + t)
+// In 16-byte chunks (EC per Ekv columns; the source row is LDC chunks wide with its K columns at chunk KC): chunk c
+// of the 2*Ekv K|V columns of qkv row (b, t) -> kv row (b, pos + t)
 __global__ void __launch_bounds__(256) attn_kv_append_kernel(const uint4* __restrict__ qkv, uint4* __restrict__ kv,
-                                                             long long total, int Tn, int EC, int pos, int Tcap) {
+                                                             long long total, int Tn, int EC, int LDC, int KC, int pos,
+                                                             int Tcap) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int c = (int)(i % (2 * EC));
   const long long bt = i / (2 * EC);                             // b*Tn + t
   const int t = (int)(bt % Tn);
   const long long b = bt / Tn;
-  kv[(b * Tcap + pos + t) * (2LL * EC) + c] = qkv[bt * (3LL * EC) + EC + c];
+  kv[(b * Tcap + pos + t) * (2LL * EC) + c] = qkv[bt * (long long)LDC + KC + c];
 }
 
 // The same copy to rows [pos - shortfall[b], pos - shortfall[b] + Tn) of batch row b; the shortfall is clamped into
 // [0, pos], so whatever the array holds no write leaves rows [0, pos + Tn) of its own batch row.
 __global__ void __launch_bounds__(256) attn_kv_append_ragged_kernel(const uint4* __restrict__ qkv,
                                                                     uint4* __restrict__ kv, long long total, int Tn,
-                                                                    int EC, int pos, int Tcap,
+                                                                    int EC, int LDC, int KC, int pos, int Tcap,
                                                                     const int* __restrict__ shortfall) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -340,17 +380,18 @@ __global__ void __launch_bounds__(256) attn_kv_append_ragged_kernel(const uint4*
   const int t = (int)(bt % Tn);
   const long long b = bt / Tn;
   const int pb = pos - min(max(shortfall[b], 0), pos);
-  kv[(b * Tcap + pb + t) * (2LL * EC) + c] = qkv[bt * (3LL * EC) + EC + c];
+  kv[(b * Tcap + pb + t) * (2LL * EC) + c] = qkv[bt * (long long)LDC + KC + c];
 }
 
 // FP8 append: D / 16 lanes per (token, head, K|V) group, 16 values each. The group's amax is reduced across its lanes
 // (they sit in one wave: 4 or 8 consecutive lanes), every lane writes its 16 codes as one 16-byte vector and lane 0
 // the scale byte; the last group of a token also zeroes the pad bytes. shortfall: null (every row at pos) or the
-// per-row array, clamped into [0, pos] as in attn_kv_append_ragged_kernel.
+// per-row array, clamped into [0, pos] as in attn_kv_append_ragged_kernel. H is the number of heads the cache holds
+// (Hkv); the source row is ld elements wide with its K columns at koff.
 template <int D, typename hb>
 __global__ void __launch_bounds__(256) attn_kv_append_fp8_kernel(const hb* __restrict__ qkv,
                                                                  unsigned char* __restrict__ kv8, long long total,
-                                                                 int Tn, int H, int pos, int Tcap,
+                                                                 int Tn, int H, int ld, int koff, int pos, int Tcap,
                                                                  const int* __restrict__ shortfall) {
   constexpr int LPG = D / 16;                                    // lanes per group
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -362,7 +403,7 @@ __global__ void __launch_bounds__(256) attn_kv_append_fp8_kernel(const hb* __res
   const int t = (int)(bt % Tn);
   const long long b = bt / Tn;
   const int E = H * D, tail = (2 * H + 15) & ~15;
-  const hb* src = qkv + bt * (3LL * E) + E + g * D + c * 16;
+  const hb* src = qkv + bt * (long long)ld + koff + g * D + c * 16;
   const V8<hb> lo = ld8(src), hi = ld8(src + 8);
   float x[16];
 #pragma unroll
@@ -412,104 +453,144 @@ static constexpr int kDecodeMaxSplits = 16;
 static int decode_nkb(int L) { return (L + BLK - 1) / BLK; }
 static int decode_clamp_splits(int splits, int L) { return splits < decode_nkb(L) ? splits : decode_nkb(L); }
 
-static bool decode_shape_ok(int dt, int B, int Tn, int H, int D, int pos, int Tcap) {
+static bool decode_shape_ok(int dt, int B, int Tn, int H, int Hkv, int D, int pos, int Tcap) {
   if (B < 1 || Tn < 1 || H < 1 || pos < 0 || Tcap < 1 || (dt != 1 && dt != 2) || (D != 64 && D != 128)) return false;
+  if (Hkv < 1 || H % Hkv) return false;
   if (Tcap % BLK || (long long)pos + Tn > Tcap) return false;
-  if ((long long)B * H > 65535 || (Tn + BLK - 1) / BLK > 65535) return false;   // grid.y / grid.z
+  const long long tiles = ((long long)Tn * (H / Hkv) + BLK - 1) / BLK;
+  if ((long long)B * Hkv > 65535 || tiles > 65535) return false;               // grid.y / grid.z
   return true;
 }
 
 // Default split count for keys [0, L) (see the constants above): min(16, key blocks / 2), one split when the
-// (batch x head x query tile) grid fills the device by itself. A pure function of its arguments (no timing), so a
+// (batch x kv head x slot tile) grid fills the device by itself. A pure function of its arguments (no timing), so a
 // run is reproducible across processes.
-DL4J_API int dl4j_attn_decode_splits(int B, int Tn, int H, int D, int L) {
-  if (B < 1 || Tn < 1 || H < 1 || L < 1 || (D != 64 && D != 128)) return 1;
-  const long long base = (long long)B * H * ((Tn + BLK - 1) / BLK);
+DL4J_API int dl4j_attn_decode_splits_gqa(int B, int Tn, int H, int Hkv, int D, int L) {
+  if (B < 1 || Tn < 1 || H < 1 || Hkv < 1 || H % Hkv || L < 1 || (D != 64 && D != 128)) return 1;
+  const long long base = (long long)B * Hkv * (((long long)Tn * (H / Hkv) + BLK - 1) / BLK);
   if (base >= (long long)kDecodeCUs * kDecodeResidentPerCU) return 1;
   int s = decode_nkb(L) / kDecodeMinBlocksPerSplit;
   if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
   return s < 1 ? 1 : s;
 }
-
-// fp32 workspace of dl4j_attn_decode_dt for a requested split count (enough for any clamped one); 0 for one split
-DL4J_API long long dl4j_attn_decode_ws_bytes(int B, int Tn, int H, int D, int splits) {
-  if (B < 1 || Tn < 1 || H < 1 || D < 1 || splits <= 1) return 0;
-  return (long long)B * H * Tn * splits * (D + 2) * (long long)sizeof(float);
+DL4J_API int dl4j_attn_decode_splits(int B, int Tn, int H, int D, int L) {
+  return dl4j_attn_decode_splits_gqa(B, Tn, H, H, D, L);
 }
 
-// dt: 1 = bf16, 2 = fp16. qkv [B,Tn,3*H*D]; kv [B,Tcap,2*H*D]; pos = tokens already in the cache (host integer, the
-// same for every batch row). Copies the K and V columns of qkv to cache rows [pos, pos+Tn).
-// -1 = unsupported shape / dtype, pos + Tn > Tcap, or operands not 16-byte aligned.
+// fp32 workspace of dl4j_attn_decode_dt for a requested split count (enough for any clamped one); 0 for one split.
+// The partials are per QUERY head, so the size does not depend on Hkv (0 for an Hkv that does not divide H).
+DL4J_API long long dl4j_attn_decode_ws_bytes_gqa(int B, int Tn, int H, int Hkv, int D, int splits) {
+  if (B < 1 || Tn < 1 || H < 1 || Hkv < 1 || H % Hkv || D < 1 || splits <= 1) return 0;
+  return (long long)B * H * Tn * splits * (D + 2) * (long long)sizeof(float);
+}
+DL4J_API long long dl4j_attn_decode_ws_bytes(int B, int Tn, int H, int D, int splits) {
+  return dl4j_attn_decode_ws_bytes_gqa(B, Tn, H, H, D, splits);
+}
+
+// dt: 1 = bf16, 2 = fp16. qkv [B,Tn,(H+2*Hkv)*D]; kv [B,Tcap,2*Hkv*D]; pos = tokens already in the cache (host
+// integer, the same for every batch row). Copies the K and V columns of qkv to cache rows [pos, pos+Tn).
+// -1 = unsupported shape / dtype, Hkv < 1 or H % Hkv != 0, pos + Tn > Tcap, or operands not 16-byte aligned.
 // shortfall: null, or int32 [B] on the device: row b is pos - shortfall[b] long instead of pos (clamped into
 // [0, pos]) and its new rows go to [pos - shortfall[b], pos - shortfall[b] + Tn).
-DL4J_API int dl4j_attn_kv_append_ragged_dt(int dt, const void* qkv, void* kv, const int* shortfall, int B, int Tn,
-                                           int H, int D, int pos, int Tcap, hipStream_t s) {
-  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv) return -1;
+DL4J_API int dl4j_attn_kv_append_ragged_gqa_dt(int dt, const void* qkv, void* kv, const int* shortfall, int B, int Tn,
+                                               int H, int Hkv, int D, int pos, int Tcap, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, Hkv, D, pos, Tcap) || !qkv || !kv) return -1;
   if (!attn_aligned16({qkv, kv})) return -1;
-  const int EC = H * D / 8;                                      // 16-byte chunks of E columns
+  const int EC = Hkv * D / 8, KC = H * D / 8, LDC = KC + 2 * EC;  // 16-byte chunks of Ekv / E / a source row
   const long long total = (long long)B * Tn * 2 * EC;
   const dim3 grid((unsigned)((total + 255) / 256));
   if (shortfall)
     hipLaunchKernelGGL(attn_kv_append_ragged_kernel, grid, dim3(256), 0, s, (const uint4*)qkv, (uint4*)kv, total, Tn,
-                       EC, pos, Tcap, shortfall);
+                       EC, LDC, KC, pos, Tcap, shortfall);
   else
-    hipLaunchKernelGGL(attn_kv_append_kernel, grid, dim3(256), 0, s, (const uint4*)qkv, (uint4*)kv, total, Tn, EC, pos,
-                       Tcap);
+    hipLaunchKernelGGL(attn_kv_append_kernel, grid, dim3(256), 0, s, (const uint4*)qkv, (uint4*)kv, total, Tn, EC, LDC,
+                       KC, pos, Tcap);
   return (int)hipGetLastError();
+}
+DL4J_API int dl4j_attn_kv_append_ragged_dt(int dt, const void* qkv, void* kv, const int* shortfall, int B, int Tn,
+                                           int H, int D, int pos, int Tcap, hipStream_t s) {
+  return dl4j_attn_kv_append_ragged_gqa_dt(dt, qkv, kv, shortfall, B, Tn, H, H, D, pos, Tcap, s);
 }
 
 // Every batch row at pos.
+DL4J_API int dl4j_attn_kv_append_gqa_dt(int dt, const void* qkv, void* kv, int B, int Tn, int H, int Hkv, int D,
+                                        int pos, int Tcap, hipStream_t s) {
+  return dl4j_attn_kv_append_ragged_gqa_dt(dt, qkv, kv, nullptr, B, Tn, H, Hkv, D, pos, Tcap, s);
+}
 DL4J_API int dl4j_attn_kv_append_dt(int dt, const void* qkv, void* kv, int B, int Tn, int H, int D, int pos, int Tcap,
                                     hipStream_t s) {
-  return dl4j_attn_kv_append_ragged_dt(dt, qkv, kv, nullptr, B, Tn, H, D, pos, Tcap, s);
+  return dl4j_attn_kv_append_ragged_gqa_dt(dt, qkv, kv, nullptr, B, Tn, H, H, D, pos, Tcap, s);
 }
 
-// The fp8 cache's append: kv8 [B,Tcap,R] bytes, R = 2*H*D + roundup16(2*H) (the layout at the top of this file);
+// The fp8 cache's append: kv8 [B,Tcap,R] bytes, R = 2*Hkv*D + roundup16(2*Hkv) (the layout at the top of this file);
 // quantises the K and V columns of qkv into rows [pos, pos+Tn) (row b at pos - shortfall[b] with a shortfall array).
-// Arguments and status codes of dl4j_attn_kv_append_ragged_dt.
-DL4J_API int dl4j_attn_kv_append_fp8_ragged_dt(int dt, const void* qkv, void* kv8, const int* shortfall, int B, int Tn,
-                                               int H, int D, int pos, int Tcap, hipStream_t s) {
-  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv8) return -1;
+// Arguments and status codes of dl4j_attn_kv_append_ragged_gqa_dt.
+DL4J_API int dl4j_attn_kv_append_fp8_ragged_gqa_dt(int dt, const void* qkv, void* kv8, const int* shortfall, int B,
+                                                   int Tn, int H, int Hkv, int D, int pos, int Tcap, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, Hkv, D, pos, Tcap) || !qkv || !kv8) return -1;
   if (!attn_aligned16({qkv, kv8})) return -1;
-  const long long total = (long long)B * Tn * 2 * H * (D / 16);
+  const long long total = (long long)B * Tn * 2 * Hkv * (D / 16);
   if ((total + 255) / 256 > 0x7fffffffLL) return -1;
   return attn_dispatch(dt, D, [&](auto d, auto e) {
     constexpr int DD = decltype(d)::value;
     using hb = typename decltype(e)::type;
     hipLaunchKernelGGL((attn_kv_append_fp8_kernel<DD, hb>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       (const hb*)qkv, (unsigned char*)kv8, total, Tn, H, pos, Tcap, shortfall);
+                       (const hb*)qkv, (unsigned char*)kv8, total, Tn, Hkv, (H + 2 * Hkv) * DD, H * DD, pos, Tcap,
+                       shortfall);
     return (int)hipGetLastError();
   });
 }
-
-// Every batch row at pos.
-DL4J_API int dl4j_attn_kv_append_fp8_dt(int dt, const void* qkv, void* kv8, int B, int Tn, int H, int D, int pos,
-                                        int Tcap, hipStream_t s) {
-  return dl4j_attn_kv_append_fp8_ragged_dt(dt, qkv, kv8, nullptr, B, Tn, H, D, pos, Tcap, s);
+DL4J_API int dl4j_attn_kv_append_fp8_ragged_dt(int dt, const void* qkv, void* kv8, const int* shortfall, int B, int Tn,
+                                               int H, int D, int pos, int Tcap, hipStream_t s) {
+  return dl4j_attn_kv_append_fp8_ragged_gqa_dt(dt, qkv, kv8, shortfall, B, Tn, H, H, D, pos, Tcap, s);
 }
 
-// out [B,Tn,H*D]; rows [0, pos+Tn) of kv are the keys / values (the new rows already appended), query i sees keys
-// <= pos + i. splits >= 1 is clamped to the number of 64-key blocks; ws: fp32 workspace of
-// dl4j_attn_decode_ws_bytes(..., splits) bytes (may be null for one split). -1 = unsupported shape / dtype.
-// shortfall: null, or int32 [B] on the device: the keys of row b are rows [0, pos - shortfall[b] + Tn) and its query i
-// sees keys <= pos - shortfall[b] + i. The grid and the split count still follow the upper bound pos.
-DL4J_API int dl4j_attn_decode_ragged_dt(int dt, const void* qkv, const void* kv, void* out, float* ws,
-                                        const int* shortfall, int B, int Tn, int H, int D, int pos, int Tcap,
-                                        int splits, float scale, hipStream_t s) {
-  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv || !out || splits < 1) return -1;
+// Every batch row at pos.
+DL4J_API int dl4j_attn_kv_append_fp8_gqa_dt(int dt, const void* qkv, void* kv8, int B, int Tn, int H, int Hkv, int D,
+                                            int pos, int Tcap, hipStream_t s) {
+  return dl4j_attn_kv_append_fp8_ragged_gqa_dt(dt, qkv, kv8, nullptr, B, Tn, H, Hkv, D, pos, Tcap, s);
+}
+DL4J_API int dl4j_attn_kv_append_fp8_dt(int dt, const void* qkv, void* kv8, int B, int Tn, int H, int D, int pos,
+                                        int Tcap, hipStream_t s) {
+  return dl4j_attn_kv_append_fp8_ragged_gqa_dt(dt, qkv, kv8, nullptr, B, Tn, H, H, D, pos, Tcap, s);
+}
+
+// The decode launch of all eight variants: FP8 picks the cache policy, Hkv == H the multi-head kernels.
+template <bool FP8>
+static int decode_launch(int dt, const void* qkv, const void* kv, void* out, float* ws, const int* shortfall, int B,
+                         int Tn, int H, int Hkv, int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, Hkv, D, pos, Tcap) || !qkv || !kv || !out || splits < 1) return -1;
   if (!attn_aligned16({qkv, kv, out, ws})) return -1;
   const int S = decode_clamp_splits(splits, pos + Tn);
   if (S > 1 && !ws) return -1;
   return attn_dispatch(dt, D, [&](auto d, auto e) {
     constexpr int DD = decltype(d)::value;
     using hb = typename decltype(e)::type;
-    const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
-    if (shortfall)
-      hipLaunchKernelGGL((attn_decode_ragged_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv,
-                         (hb*)out, ws, Tn, H, pos, Tcap, S, scale * kLog2e, shortfall);
-    else
-      hipLaunchKernelGGL((attn_decode_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const hb*)kv, (hb*)out,
-                         ws, Tn, H, pos, Tcap, S, scale * kLog2e);
+    using CP = std::conditional_t<FP8, KvCacheFp8<DD, hb>, KvCache16<DD, hb>>;
+    using ce = typename CP::elem;
+    const float scale2 = scale * kLog2e;
+    if (Hkv != H) {
+      const dim3 grid(S, B * Hkv, (Tn * (H / Hkv) + BLK - 1) / BLK);
+      hipLaunchKernelGGL((attn_decode_gqa_kernel<DD, hb, CP>), grid, dim3(256), 0, s, (const hb*)qkv, (const ce*)kv,
+                         (hb*)out, ws, Tn, H, Hkv, pos, Tcap, S, scale2, shortfall);
+    } else {
+      const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
+      if constexpr (FP8) {
+        if (shortfall)
+          hipLaunchKernelGGL((attn_decode_fp8_ragged_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv,
+                             (const ce*)kv, (hb*)out, ws, Tn, H, pos, Tcap, S, scale2, shortfall);
+        else
+          hipLaunchKernelGGL((attn_decode_fp8_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const ce*)kv,
+                             (hb*)out, ws, Tn, H, pos, Tcap, S, scale2);
+      } else {
+        if (shortfall)
+          hipLaunchKernelGGL((attn_decode_ragged_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const ce*)kv,
+                             (hb*)out, ws, Tn, H, pos, Tcap, S, scale2, shortfall);
+        else
+          hipLaunchKernelGGL((attn_decode_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv, (const ce*)kv,
+                             (hb*)out, ws, Tn, H, pos, Tcap, S, scale2);
+      }
+    }
     if (S > 1) {
       const long long n = (long long)B * H * Tn * (DD / 4);
       hipLaunchKernelGGL((attn_decode_combine_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
@@ -519,43 +600,54 @@ DL4J_API int dl4j_attn_decode_ragged_dt(int dt, const void* qkv, const void* kv,
   });
 }
 
-// Every batch row at pos.
-DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
-                                 int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
-  return dl4j_attn_decode_ragged_dt(dt, qkv, kv, out, ws, nullptr, B, Tn, H, D, pos, Tcap, splits, scale, s);
+// out [B,Tn,H*D]; rows [0, pos+Tn) of kv [B,Tcap,2*Hkv*D] are the keys / values (the new rows already appended), query
+// i sees keys <= pos + i. splits >= 1 is clamped to the number of 64-key blocks; ws: fp32 workspace of
+// dl4j_attn_decode_ws_bytes_gqa(..., splits) bytes (may be null for one split). -1 = unsupported shape / dtype,
+// Hkv < 1, H % Hkv != 0 or operands not 16-byte aligned.
+// shortfall: null, or int32 [B] on the device: the keys of row b are rows [0, pos - shortfall[b] + Tn) and its query i
+// sees keys <= pos - shortfall[b] + i. The grid and the split count still follow the upper bound pos.
+DL4J_API int dl4j_attn_decode_ragged_gqa_dt(int dt, const void* qkv, const void* kv, void* out, float* ws,
+                                            const int* shortfall, int B, int Tn, int H, int Hkv, int D, int pos,
+                                            int Tcap, int splits, float scale, hipStream_t s) {
+  return decode_launch<false>(dt, qkv, kv, out, ws, shortfall, B, Tn, H, Hkv, D, pos, Tcap, splits, scale, s);
+}
+DL4J_API int dl4j_attn_decode_ragged_dt(int dt, const void* qkv, const void* kv, void* out, float* ws,
+                                        const int* shortfall, int B, int Tn, int H, int D, int pos, int Tcap,
+                                        int splits, float scale, hipStream_t s) {
+  return decode_launch<false>(dt, qkv, kv, out, ws, shortfall, B, Tn, H, H, D, pos, Tcap, splits, scale, s);
 }
 
-// dl4j_attn_decode_ragged_dt over the fp8 cache kv8 [B,Tcap,R] bytes: the same arguments, split clamp, workspace
-// (dl4j_attn_decode_ws_bytes) and status codes; for a given split count the result is bitwise what the 16-bit entry
-// gives on the dequantised cache.
+// Every batch row at pos.
+DL4J_API int dl4j_attn_decode_gqa_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn,
+                                     int H, int Hkv, int D, int pos, int Tcap, int splits, float scale,
+                                     hipStream_t s) {
+  return decode_launch<false>(dt, qkv, kv, out, ws, nullptr, B, Tn, H, Hkv, D, pos, Tcap, splits, scale, s);
+}
+DL4J_API int dl4j_attn_decode_dt(int dt, const void* qkv, const void* kv, void* out, float* ws, int B, int Tn, int H,
+                                 int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
+  return decode_launch<false>(dt, qkv, kv, out, ws, nullptr, B, Tn, H, H, D, pos, Tcap, splits, scale, s);
+}
+
+// The same over the fp8 cache kv8 [B,Tcap,R] bytes: the same arguments, split clamp, workspace and status codes; for
+// a given split count the result is bitwise what the 16-bit entry gives on the dequantised cache.
+DL4J_API int dl4j_attn_decode_fp8_ragged_gqa_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws,
+                                                const int* shortfall, int B, int Tn, int H, int Hkv, int D, int pos,
+                                                int Tcap, int splits, float scale, hipStream_t s) {
+  return decode_launch<true>(dt, qkv, kv8, out, ws, shortfall, B, Tn, H, Hkv, D, pos, Tcap, splits, scale, s);
+}
 DL4J_API int dl4j_attn_decode_fp8_ragged_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws,
                                             const int* shortfall, int B, int Tn, int H, int D, int pos, int Tcap,
                                             int splits, float scale, hipStream_t s) {
-  if (!decode_shape_ok(dt, B, Tn, H, D, pos, Tcap) || !qkv || !kv8 || !out || splits < 1) return -1;
-  if (!attn_aligned16({qkv, kv8, out, ws})) return -1;
-  const int S = decode_clamp_splits(splits, pos + Tn);
-  if (S > 1 && !ws) return -1;
-  return attn_dispatch(dt, D, [&](auto d, auto e) {
-    constexpr int DD = decltype(d)::value;
-    using hb = typename decltype(e)::type;
-    const dim3 grid(S, B * H, (Tn + BLK - 1) / BLK);
-    if (shortfall)
-      hipLaunchKernelGGL((attn_decode_fp8_ragged_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv,
-                         (const unsigned char*)kv8, (hb*)out, ws, Tn, H, pos, Tcap, S, scale * kLog2e, shortfall);
-    else
-      hipLaunchKernelGGL((attn_decode_fp8_kernel<DD, hb>), grid, dim3(256), 0, s, (const hb*)qkv,
-                         (const unsigned char*)kv8, (hb*)out, ws, Tn, H, pos, Tcap, S, scale * kLog2e);
-    if (S > 1) {
-      const long long n = (long long)B * H * Tn * (DD / 4);
-      hipLaunchKernelGGL((attn_decode_combine_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
-                         (hb*)out, (long long)B * H, Tn, H, S);
-    }
-    return (int)hipGetLastError();
-  });
+  return decode_launch<true>(dt, qkv, kv8, out, ws, shortfall, B, Tn, H, H, D, pos, Tcap, splits, scale, s);
 }
 
 // Every batch row at pos.
+DL4J_API int dl4j_attn_decode_fp8_gqa_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws, int B, int Tn,
+                                         int H, int Hkv, int D, int pos, int Tcap, int splits, float scale,
+                                         hipStream_t s) {
+  return decode_launch<true>(dt, qkv, kv8, out, ws, nullptr, B, Tn, H, Hkv, D, pos, Tcap, splits, scale, s);
+}
 DL4J_API int dl4j_attn_decode_fp8_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws, int B, int Tn,
                                      int H, int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
-  return dl4j_attn_decode_fp8_ragged_dt(dt, qkv, kv8, out, ws, nullptr, B, Tn, H, D, pos, Tcap, splits, scale, s);
+  return decode_launch<true>(dt, qkv, kv8, out, ws, nullptr, B, Tn, H, H, D, pos, Tcap, splits, scale, s);
 }

@@ -969,12 +969,13 @@ class TextGenerationTransformer(ZooModel):
         return net.generate(prompt, promptLengths=promptLengths, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
-                 maxPositions=512, learningRate=1e-3, cacheDataType=None, **kw):
+                 maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
         self.maxPositions, self.learningRate = maxPositions, learningRate
         self.cacheDataType = cacheDataType      # None, or "fp8": the key/value cache format of every block
+        self.nKVHeads = nKVHeads                # None, or a divisor of heads: grouped-query attention in every block
 
     def graphBuilder(self):
         from ..nn.conf import BertEmbeddingLayer, TransformerEncoderLayer
@@ -987,7 +988,7 @@ class TextGenerationTransformer(ZooModel):
         for i in range(self.layers):
             g.addLayer(f"decoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
                        .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
-                       .build(), prev)
+                       .nKVHeads(self.nKVHeads).build(), prev)
             prev = f"decoder_{i}"
         g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
                    .nIn(self.hidden).nOut(self.numLabels).build(), prev)

@@ -1392,6 +1392,28 @@ def _check_cache_dtype(layer):
             f"{type(layer).__name__}: cacheDataType is None (the compute dtype) or \"fp8\", got {v!r}")
 
 
+def _who(layer):
+    name = getattr(layer, "layerName", None)
+    return f"{type(layer).__name__} '{name}'" if name else type(layer).__name__
+
+
+def _check_kv_heads(layer, grouped=True):
+    """``nKVHeads``: the key/value heads of grouped-query attention, shared by the ``nHeads`` query heads in groups of
+    nHeads / nKVHeads (1 = multi-query attention). None (the default) = ``nHeads``, plain multi-head attention. It
+    must divide ``nHeads``; a layer that is not ``grouped`` (the cross-attention family) takes ``nHeads`` only."""
+    v = layer.nKVHeads
+    if v is None:
+        return
+    ok = isinstance(v, int) and not isinstance(v, bool) and v >= 1
+    if not ok or layer.nHeads % v:
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: nKVHeads must be a positive integer that divides nHeads = {layer.nHeads}, got {v!r}")
+    if not grouped and v != layer.nHeads:
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: grouped key/value heads are not supported by this layer; nKVHeads must be None or "
+            f"nHeads = {layer.nHeads}, got {v!r}")
+
+
 def _check_drop_prob(layer, name):
     """``name`` is a DROP probability in [0, 1) (HuggingFace's convention; 0.0 = off) — the opposite of the
     retain-probability ``dropOut`` of the reference's layers."""
@@ -1410,16 +1432,24 @@ class SelfAttentionLayer(FeedForwardLayer):
     (0.0 = off, the default; HuggingFace's ``attention_probs_dropout_prob``, NOT the reference's retain-probability
     ``dropOut``). The mask is generated inside the flash-attention kernels and never stored.
 
-    ``cacheDataType``: None (the default: the rnnTimeStep key/value cache is kept in the compute dtype) or "fp8"."""
+    ``cacheDataType``: None (the default: the rnnTimeStep key/value cache is kept in the compute dtype) or "fp8".
+
+    ``nKVHeads``: None (the default: one key/value head per query head) or a divisor of ``nHeads``: grouped-query
+    attention, ``nHeads / nKVHeads`` query heads share a key/value head (1 = multi-query). ``Wk`` / ``Wv`` are then
+    [nIn, nKVHeads * headSize] and the rnnTimeStep cache holds the key/value heads only."""
     FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False, "attentionDropout": 0.0,
-              "cacheDataType": None}
-    _OMIT_AT_DEFAULT = ("cacheDataType",)
+              "cacheDataType": None, "nKVHeads": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads")
     RUNTIME = "deeplearning4j_amd.nn.layers.attention:SelfAttentionLayerImpl"
 
     def _post_init(self):
         super()._post_init()
         _check_drop_prob(self, "attentionDropout")
         _check_cache_dtype(self)
+        _check_kv_heads(self)
+
+    def kvHeads(self):
+        return self.nHeads if self.nKVHeads is None else self.nKVHeads
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1437,13 +1467,13 @@ class SelfAttentionLayer(FeedForwardLayer):
 
     def param_specs(self):
         hs = self.headSize or (self.nOut // self.nHeads)
-        d = self.nHeads * hs
+        d, dkv = self.nHeads * hs, self.kvHeads() * hs
         return [ParamSpec("Wq", [self.nIn, d], "c", "weight", self.nIn, d),
-                ParamSpec("Wk", [self.nIn, d], "c", "weight", self.nIn, d),
-                ParamSpec("Wv", [self.nIn, d], "c", "weight", self.nIn, d),
+                ParamSpec("Wk", [self.nIn, dkv], "c", "weight", self.nIn, dkv),
+                ParamSpec("Wv", [self.nIn, dkv], "c", "weight", self.nIn, dkv),
                 ParamSpec("Wo", [d, self.nOut], "c", "weight", d, self.nOut),
-                ParamSpec("bq", [1, d], "c", "bias"), ParamSpec("bk", [1, d], "c", "bias"),
-                ParamSpec("bv", [1, d], "c", "bias"), ParamSpec("bo", [1, self.nOut], "c", "bias")]
+                ParamSpec("bq", [1, d], "c", "bias"), ParamSpec("bk", [1, dkv], "c", "bias"),
+                ParamSpec("bv", [1, dkv], "c", "bias"), ParamSpec("bo", [1, self.nOut], "c", "bias")]
 
     def is_bias(self, key):
         return key.startswith("b")
@@ -1462,10 +1492,15 @@ class TransformerEncoderLayer(FeedForwardLayer):
     probabilities inside the flash-attention kernels. No mask is stored on the GPU.
 
     ``cacheDataType``: None (the default: the rnnTimeStep key/value cache of a causal block is kept in the compute
-    dtype) or "fp8" (half the bytes per cached token; see ``KVCacheState``)."""
+    dtype) or "fp8" (half the bytes per cached token; see ``KVCacheState``).
+
+    ``nKVHeads``: None (the default: one key/value head per query head) or a divisor of ``nHeads``: grouped-query
+    attention, ``nHeads / nKVHeads`` query heads share a key/value head (1 = multi-query). The fused projection is
+    then ``Wqkv [E, E + 2*Ekv]`` with ``Ekv = nKVHeads * E / nHeads`` and the rnnTimeStep cache of a causal block
+    holds the key/value heads only (``nKVHeads / nHeads`` of the bytes; stacks with "fp8")."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
-              "attentionDropout": 0.0, "cacheDataType": None}
-    _OMIT_AT_DEFAULT = ("cacheDataType",)
+              "attentionDropout": 0.0, "cacheDataType": None, "nKVHeads": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads")
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
 
     def _post_init(self):
@@ -1473,6 +1508,10 @@ class TransformerEncoderLayer(FeedForwardLayer):
         _check_drop_prob(self, "hiddenDropout")
         _check_drop_prob(self, "attentionDropout")
         _check_cache_dtype(self)
+        _check_kv_heads(self)
+
+    def kvHeads(self):
+        return self.nHeads if self.nKVHeads is None else self.nKVHeads
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1489,7 +1528,8 @@ class TransformerEncoderLayer(FeedForwardLayer):
 
     def param_specs(self):
         E, F = self.nIn, self.ffnSize
-        return [ParamSpec("Wqkv", [E, 3 * E], "c", "weight", E, E), ParamSpec("bqkv", [1, 3 * E], "c", "bias"),
+        Q = E + 2 * (E // self.nHeads) * self.kvHeads()          # E + 2*Ekv columns of the fused projection
+        return [ParamSpec("Wqkv", [E, Q], "c", "weight", E, E), ParamSpec("bqkv", [1, Q], "c", "bias"),
                 ParamSpec("Wo", [E, E], "c", "weight", E, E), ParamSpec("bo", [1, E], "c", "bias"),
                 ParamSpec("ln1g", [1, E], "c", "const", value=1.0), ParamSpec("ln1b", [1, E], "c", "const", value=0.0),
                 ParamSpec("W1", [E, F], "c", "weight", E, F), ParamSpec("b1", [1, F], "c", "bias"),
@@ -1527,8 +1567,13 @@ class CrossAttentionLayer(_TwoInputLayer):
     the first input [mb, nIn, Tq], the keys and values from the second, the memory [mb, nInMemory, Tk]. The first
     input's feature mask zeroes masked query rows; the memory's mask is the key-padding mask. There is no causal flag
     (it has no meaning across two sequences) and no attention dropout. Graph-only: ``MultiLayerNetwork`` refuses it."""
-    FIELDS = {"nHeads": 1, "headSize": 0}
+    FIELDS = {"nHeads": 1, "headSize": 0, "nKVHeads": None}
+    _OMIT_AT_DEFAULT = ("nKVHeads",)
     RUNTIME = "deeplearning4j_amd.nn.layers.attention:CrossAttentionLayerImpl"
+
+    def _post_init(self):
+        super()._post_init()
+        _check_kv_heads(self, grouped=False)
 
     def setNIn(self, inputType, override=False, memoryType=None):
         super().setNIn(inputType, override, memoryType)
@@ -1563,8 +1608,8 @@ class TransformerDecoderLayer(_TwoInputLayer):
     ``cacheDataType``: None or "fp8", the format of the SELF-attention key/value cache of rnnTimeStep; the stored
     cross-attention memory projection stays in the compute dtype."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "hiddenDropout": 0.0, "attentionDropout": 0.0,
-              "cacheDataType": None}
-    _OMIT_AT_DEFAULT = ("cacheDataType",)
+              "cacheDataType": None, "nKVHeads": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads")
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerDecoderLayerImpl"
 
     def _post_init(self):
@@ -1572,6 +1617,7 @@ class TransformerDecoderLayer(_TwoInputLayer):
         _check_drop_prob(self, "hiddenDropout")
         _check_drop_prob(self, "attentionDropout")
         _check_cache_dtype(self)
+        _check_kv_heads(self, grouped=False)
 
     def setNIn(self, inputType, override=False, memoryType=None):
         super().setNIn(inputType, override, memoryType)

@@ -281,7 +281,9 @@ def layer_memory_report(lc, inputType, outputType, name=None, compute_bytes=None
         wvt = outE // 2 if outE else 0    # 1-byte argmax per output element (units of 2-byte elements)
     elif bt == "SelfAttentionLayer":
         T = getattr(inputType, "timeSeriesLength", 1) or 1
-        wvi = wvt = 3 * outE + getattr(base, "nHeads", 1) * T * T
+        H = getattr(base, "nHeads", 1) or 1
+        Hkv = getattr(base, "nKVHeads", None) or H               # grouped heads: K / V are Hkv / H of a Q block
+        wvi = wvt = outE + 2 * outE * Hkv // H + H * T * T
     elif bt in ("CrossAttentionLayer", "TransformerDecoderLayer"):
         # q / context / output rows of the own stream, the memory's kv projection; the flash kernels keep lse only
         Tq = max(getattr(inputType, "timeSeriesLength", 1) or 1, 1)

@@ -14,6 +14,9 @@ hand-derived backward (no torch.autograd):
 Feature masks [mb, T] mask padded keys; masked query rows produce zeros.
 ``attentionDropout`` (a DROP probability, training only): the keep mask is generated inside the flash kernels from
 the layer's PhiloxStream and regenerated in the backward; the explicit path takes its mask from ``dropoutKeep``.
+``nKVHeads`` (grouped-query attention): Wk / Wv project to the nKVHeads key/value heads only, the buffer is
+[mb*T, d + 2*dkv] (Q | K | V, dkv = nKVHeads * headSize), the kernels share each key/value head between the
+nHeads / nKVHeads query heads of its group and dK / dV come back summed over the group.
 ``rnnTimeStep`` on a causal layer appends the chunk's K / V to a per-layer cache and attends over it
 (``KVCacheState`` in transformer.py, csrc/attention_decode.hip).
 
@@ -38,23 +41,39 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         hs = c.headSize or (c.nOut // c.nHeads)
         return c.nHeads, hs, c.nHeads * hs
 
+    def _kv_dims(self):
+        """(key/value heads, dkv = their columns, the column blocks of Q | K | V in the fused buffer)."""
+        H, hs, d = self._dims()
+        Hkv = self.conf.kvHeads()
+        dkv = Hkv * hs
+        return Hkv, dkv, ((0, d), (d, d + dkv), (d + dkv, d + 2 * dkv))
+
+    def _project(self, X, n, device):
+        """QKV [n, d + 2*dkv]: three GEMMs writing the column blocks of one buffer, bias in the epilogue."""
+        _, dkv, blocks = self._kv_dims()
+        qkv = torch.empty(n, blocks[2][1], dtype=X.dtype, device=device)
+        for (lo, hi), (wk, bk) in zip(blocks, (("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
+            mmul(X, self.W(wk), out=qkv[:, lo:hi], bias=self.Wbias(bk).reshape(-1))
+        return qkv
+
     def _attn_fwd(self, qkv, mb, T, H, mask, drop=0.0):
         from ...ops import transformer_native as TN
         from ...ops import use_native
         q3 = qkv.reshape(mb, T, -1)
+        Hkv = self.conf.kvHeads()
         if q3.is_cuda and q3.dtype in (torch.bfloat16, torch.float16) and use_native(q3, "attention") \
-                and TN.attn_supported(q3, H):
+                and TN.attn_supported(q3, H, Hkv):
             if drop > 0.0:
                 st = self.dropoutStream("attention")
-                out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), dropout=drop, rng=st)
+                out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), dropout=drop, rng=st, Hkv=Hkv)
                 return out, ("native", out, lse, drop, st)
-            out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal))
+            out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), Hkv=Hkv)
             return out, ("native", out, lse)
         if q3.is_cuda:
             from ...ops import fallback
-            fallback.record("attention", f"SelfAttentionLayer head size {q3.shape[-1] // (3 * H)} / {q3.dtype}")
+            fallback.record("attention", f"SelfAttentionLayer head size {q3.shape[-1] // (H + 2 * Hkv)} / {q3.dtype}")
         keep = self.dropoutKeep("attention", (mb, H, T, T), drop, q3) if drop > 0.0 else None
-        out, ctx = TN.attention_fwd_explicit(q3, H, mask, bool(self.conf.causal), keep=keep)
+        out, ctx = TN.attention_fwd_explicit(q3, H, mask, bool(self.conf.causal), keep=keep, Hkv=Hkv)
         return out, ("explicit", ctx)
 
     def _attn_bwd(self, qkv, do, mb, T, H, mask, ctx):
@@ -62,7 +81,7 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         if ctx[0] == "native":
             kw = dict(dropout=ctx[3], rng=ctx[4]) if len(ctx) > 3 else {}
             return TN.attn_bwd(qkv.reshape(mb, T, -1), ctx[1], ctx[2], do.reshape(mb, T, -1), H, mask,
-                               bool(self.conf.causal), **kw)
+                               bool(self.conf.causal), Hkv=self.conf.kvHeads(), **kw)
         return TN.attention_bwd_explicit(ctx[1], do.reshape(mb, T, -1), qkv.dtype)
 
     def activate(self, x, training=False, mask=None, **kw):
@@ -71,9 +90,7 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         H, hs, d = self._dims()
         dt = self.W("Wq").dtype
         X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
-        qkv = torch.empty(mb * T, 3 * d, dtype=dt, device=x.device)
-        for i, (wk, bk) in enumerate((("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
-            mmul(X, self.W(wk), out=qkv[:, i * d:(i + 1) * d], bias=self.Wbias(bk).reshape(-1))
+        qkv = self._project(X, mb * T, x.device)
         m = mask.reshape(mb, T) if mask is not None else None
         drop = float(self.conf.attentionDropout) if training else 0.0
         if drop > 0.0:
@@ -105,10 +122,8 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         H, hs, d = self._dims()
         dt = self.W("Wq").dtype
         X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
-        qkv = torch.empty(mb * T, 3 * d, dtype=dt, device=x.device)
-        for i, (wk, bk) in enumerate((("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
-            mmul(X, self.W(wk), out=qkv[:, i * d:(i + 1) * d], bias=self.Wbias(bk).reshape(-1))
-        o = self.cachedAttention(qkv.reshape(mb, T, 3 * d), H, "SelfAttentionLayer rnnTimeStep")
+        qkv = self._project(X, mb * T, x.device)
+        o = self.cachedAttention(qkv.reshape(mb, T, -1), H, "SelfAttentionLayer rnnTimeStep", self.conf.kvHeads())
         Y = matmul(o.reshape(mb * T, d), self.W("Wo"), bias=self.Wbias("bo"))
         z = Y.reshape(mb, T, -1).permute(0, 2, 1)
         y = self.conf.activation.getActivation(z, False) if self.conf.activation is not None else z
@@ -127,13 +142,14 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         weight_grad_(self.grads["Wo"], o2.t(), dY)
         bias_grad_(self.grads["bo"], dY)
         dO = matmul(dY, self.W("Wo").t())
-        dqkv = self._attn_bwd(qkv, dO, mb, T, H, m, actx).reshape(mb * T, 3 * d)
+        blocks = self._kv_dims()[2]
+        dqkv = self._attn_bwd(qkv, dO, mb, T, H, m, actx).reshape(mb * T, blocks[2][1])
         if not dqkv.is_contiguous():
             dqkv = dqkv.contiguous()
         Xt = X.t()
         dX = None
-        for i, (wk, bk) in enumerate((("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
-            g = dqkv[:, i * d:(i + 1) * d]
+        for (lo, hi), (wk, bk) in zip(blocks, (("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):
+            g = dqkv[:, lo:hi]
             weight_grad_(self.grads[wk], Xt, g)
             bias_grad_(self.grads[bk], g.contiguous() if g.is_cuda else g)
             if dX is None:

@@ -28,6 +28,10 @@ its K / V appended, its queries attend over the cache (csrc/attention_decode.hip
 kernels) and the rest of the block runs as in the inference forward; the embedding layer continues its positions.
 A bidirectional block cannot stream and runs ``activate`` on the chunk.
 
+Grouped-query attention (``nKVHeads`` on the encoder block): Wqkv projects to [B*T, E + 2*Ekv] (Q | K | V with the
+nKVHeads key/value heads only), the flash kernels share each of them between the query heads of its group, the
+backward returns dK / dV summed over the group, and the cache holds 2*Ekv columns (or the fp8 rows of nKVHeads heads).
+
 Decoder block (``TransformerDecoderLayerImpl``, a two-input graph layer: decoder stream + encoder memory): causal
 self-attention as above, then cross-attention of q2 = h1·Wq2 over kv2 = memory·Wkv2 (one GEMM straight into the
 kv [mb, Tk, 2E] layout of csrc/attention_cross.hip), then the FFN, each followed by LayerNorm(+residual). Its
@@ -208,31 +212,33 @@ def _drop_bwd(d, dctx):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def _attn_fwd(qkv, B, T, H, mask, causal, drop=0.0, owner=None):
+def _attn_fwd(qkv, B, T, H, mask, causal, drop=0.0, owner=None, Hkv=None):
     from ...ops import transformer_native as TN
+    Hkv = H if Hkv is None else Hkv
     if _native(qkv, "attention"):
         q3 = qkv.reshape(B, T, -1)
-        if TN.attn_supported(q3, H):
+        if TN.attn_supported(q3, H, Hkv):
             if drop > 0.0:
                 st = owner.dropoutStream("attention")
-                out, lse = TN.attn_fwd(q3, H, mask, causal, dropout=drop, rng=st)
+                out, lse = TN.attn_fwd(q3, H, mask, causal, dropout=drop, rng=st, Hkv=Hkv)
                 return out.reshape(B * T, -1), ("native", out, lse, drop, st)
-            out, lse = TN.attn_fwd(q3, H, mask, causal)
+            out, lse = TN.attn_fwd(q3, H, mask, causal, Hkv=Hkv)
             return out.reshape(B * T, -1), ("native", out, lse)
     if qkv.is_cuda:
         from ...ops import fallback
-        fallback.record("attention", f"head size {qkv.shape[-1] // (3 * H)} / dtype {qkv.dtype}: explicit torch path")
+        fallback.record("attention",
+                        f"head size {qkv.shape[-1] // (H + 2 * Hkv)} / dtype {qkv.dtype}: explicit torch path")
     keep = owner.dropoutKeep("attention", (B, H, T, T), drop, qkv) if drop > 0.0 else None
-    o, ctx = TN.attention_fwd_explicit(qkv.reshape(B, T, -1), H, mask, causal, keep=keep)
+    o, ctx = TN.attention_fwd_explicit(qkv.reshape(B, T, -1), H, mask, causal, keep=keep, Hkv=Hkv)
     return o.reshape(B * T, -1), ("explicit", ctx)
 
 
-def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx):
+def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx, Hkv=None):
     from ...ops import transformer_native as TN
     if ctx[0] == "native":
         kw = dict(dropout=ctx[3], rng=ctx[4]) if len(ctx) > 3 else {}
         return TN.attn_bwd(qkv.reshape(B, T, -1), ctx[1], ctx[2], dctx.reshape(B, T, -1), H, mask,
-                           causal, **kw).reshape(B * T, -1)
+                           causal, Hkv=Hkv, **kw).reshape(B * T, -1)
     return TN.attention_bwd_explicit(ctx[1], dctx.reshape(B, T, -1), qkv.dtype).reshape(B * T, -1)
 
 
@@ -240,6 +246,8 @@ def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx):
 class KVCacheState:
     """rnnTimeStep state of a causal attention layer: one key/value cache ``kv [mb, Tcap, 2E]`` in the compute dtype
     (K of head h at column h*D, V at E + h*D; the layout of csrc/attention_decode.hip) and the number of valid rows.
+    With grouped heads (``nKVHeads`` on the configuration) the cache holds the key/value heads only: 2*Ekv columns,
+    or the fp8 rows of nKVHeads heads; everything below that moves whole rows does not care.
     Tcap is a multiple of 64 and grows geometrically, so a steady-state step neither allocates nor copies. The stored
     state handed out / taken in is ``{"kv": [mb, L, 2E]}`` trimmed to the valid length.
 
@@ -316,6 +324,10 @@ class KVCacheState:
     def _kv_fp8(self):
         return getattr(self.conf, "cacheDataType", None) == "fp8"
 
+    def _kv_heads(self):
+        """The heads the cache holds: nKVHeads, or nHeads without grouping."""
+        return getattr(self.conf, "nKVHeads", None) or self.conf.nHeads
+
     def rnnGetPreviousState(self):
         if self._kv is None:
             return {}
@@ -334,7 +346,7 @@ class KVCacheState:
         if kv is None:
             return
         from ...ops import transformer_native as TN
-        H = self.conf.nHeads
+        H = self._kv_heads()
         if state.get("kvFormat") == "fp8" and not self._kv_fp8():
             pad = -(-2 * H // 16) * 16
             kv = TN.kv_fp8_dequantize_reference(kv, H, (kv.shape[2] - pad) // (2 * H), self.compute_dtype)
@@ -371,36 +383,39 @@ class KVCacheState:
         self._kv = new
         self._kv_alt = None         # the second buffer follows the new capacity at the next rnnReorderState
 
-    def cachedAttention(self, qkv, H, what="rnnTimeStep"):
-        """Causal attention of the chunk qkv [mb, Tn, 3E] over everything seen since rnnClearPreviousState(): its K / V
+    def cachedAttention(self, qkv, H, what="rnnTimeStep", Hkv=None):
+        """Causal attention of the chunk qkv [mb, Tn, 3E] ([mb, Tn, E + 2*Ekv] with ``Hkv`` key/value heads, which
+        are what the cache then holds) over everything seen since rnnClearPreviousState(): its K / V
         are appended to the cache, its queries attend over the cache. -> [mb, Tn, E]. The decode kernels on a GPU in
         bf16 / fp16 with head size 64 / 128 (the causal flash forward for a prompt of >= 64 tokens into an empty
         cache), else the torch reference, counted as a fallback on a GPU. With the fp8 cache both paths store the
         quantised rows and attend over the dequantised cache, except for that prompt chunk."""
         from ...ops import transformer_native as TN
         mb, Tn, E3 = qkv.shape
-        E = E3 // 3
+        Hkv = H if Hkv is None else Hkv
+        D = E3 // (H + 2 * Hkv)
+        E, Ekv = H * D, Hkv * D
         pos, short = self._kv_len, self._kv_short
         if self._kv_pinned:
             _pinned_one_step(self, Tn)
         fp8 = self._kv_fp8()
         if fp8:
-            self._kv_reserve(mb, TN.kv_fp8_row_bytes(H, E // H), pos + Tn, torch.uint8, qkv.device)
+            self._kv_reserve(mb, TN.kv_fp8_row_bytes(Hkv, D), pos + Tn, torch.uint8, qkv.device)
         else:
-            self._kv_reserve(mb, 2 * E, pos + Tn, qkv.dtype, qkv.device)
+            self._kv_reserve(mb, 2 * Ekv, pos + Tn, qkv.dtype, qkv.device)
         kv = self._kv
         out = None
-        if _native(qkv, "attention") and qkv.is_contiguous() and TN.attn_decode_supported(qkv, kv, H):
-            if TN.attn_kv_append(qkv, kv, H, pos, short) is not None:
+        if _native(qkv, "attention") and qkv.is_contiguous() and TN.attn_decode_supported(qkv, kv, H, Hkv):
+            if TN.attn_kv_append(qkv, kv, H, pos, short, Hkv=Hkv) is not None:
                 if pos == 0 and Tn >= 64:
-                    out = TN.attn_fwd(qkv, H, None, True)[0]
+                    out = TN.attn_fwd(qkv, H, None, True, Hkv=Hkv)[0]
                 else:
-                    out = TN.attn_decode(qkv, kv, H, pos, short=short)
+                    out = TN.attn_decode(qkv, kv, H, pos, short=short, Hkv=Hkv)
         if out is None:
             if qkv.is_cuda:
                 from ...ops import fallback
                 fallback.record("attention", f"{what} head size {E // H} / dtype {qkv.dtype}: torch reference path")
-            new = TN.kv_fp8_quantize_reference(qkv[:, :, E:], H) if fp8 else qkv[:, :, E:]
+            new = TN.kv_fp8_quantize_reference(qkv[:, :, E:], Hkv) if fp8 else qkv[:, :, E:]
             if short is None:
                 kv[:, pos:pos + Tn] = new
             else:
@@ -411,8 +426,9 @@ class KVCacheState:
             elif pos == 0 and Tn >= 64:
                 seen = qkv[:, :, E:]
             else:
-                seen = TN.kv_fp8_dequantize_reference(kv[:, :pos + Tn], H, E // H, qkv.dtype)
-            out = TN.attention_decode_reference(qkv[:, :, :E], seen[:, :, :E], seen[:, :, E:], H, pos, short=short)
+                seen = TN.kv_fp8_dequantize_reference(kv[:, :pos + Tn], Hkv, D, qkv.dtype)
+            out = TN.attention_decode_reference(qkv[:, :, :E], seen[:, :, :Ekv], seen[:, :, Ekv:], H, pos, short=short,
+                                                Hkv=Hkv)
         if not self._kv_pinned:                  # pinned: the bound stays, the network lowers ``short`` on the device
             self._kv_len = pos + Tn
         return out
@@ -501,7 +517,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         if pa > 0.0 or ph > 0.0:
             self.dropoutBegin(x.device)
         qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
-        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self)
+        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads())
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, ln1, a, d1 = _ln_fwd_drop(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps, ph, self,
                                       "hidden1")
@@ -532,7 +548,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         B, E, T = x.shape
         xt = _token_major(x).to(self.W("Wqkv").dtype)
         qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
-        ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads).reshape(B * T, -1)
+        ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads, Hkv=c.kvHeads()).reshape(B * T, -1)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
         f = matmul(h1, self.W("W1"), bias=self.Wbias("b1"), act="gelu")
@@ -574,7 +590,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
             _bsum(g["bo"], da)
         _wgrad(g["Wo"], ctx, da)
         dctx = matmul(da, self.W("Wo").t())
-        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx)
+        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads())
         _wgrad(g["Wqkv"], xt, dqkv)
         _bsum(g["bqkv"], dqkv)
         dx = mmul(dqkv, self.W("Wqkv").t(), out=ds1, beta=1.0)

@@ -16,8 +16,16 @@
             on the dequantised cache. With --parent-lib also the 16-bit kernels of a kernel library built from the
             parent commit.
 
+  --kv-heads N[,N..]  grouped-query attention: the decode attention and the append of one new token with 12 query
+            heads of 64 over N key/value heads (12, the multi-head row, is always measured and is the baseline), at
+            the --kernel shapes, 16-bit and fp8 cache, default splits, all variants alternating within every pass.
+            Each row is reported against the 12-head row of the same run next to the ratio of the cache bytes read,
+            which bounds the gain. With --parent-lib also the parent commit's multi-head decode, forward and
+            backward kernels against this tree's (twice per pass: the spread of the parent alone is the yardstick).
+
 Usage: python tools/bench_decode.py --kernel --model [--out profiles/decode_attention.txt]
-       python tools/bench_decode.py --cache fp8 [--parent-lib PATH] [--out FILE]"""
+       python tools/bench_decode.py --cache fp8 [--parent-lib PATH] [--out FILE]
+       python tools/bench_decode.py --kv-heads 4,1 [--parent-lib PATH] [--out FILE]"""
 import argparse
 import sys
 import time
@@ -152,6 +160,123 @@ def cache_fp8_mode(passes, reps, parent_lib):
     say()
 
 
+def _stats(t):
+    t = sorted(t)
+    return t[len(t) // 2], t[0], t[-1]
+
+
+def gqa_mode(kv_heads, passes, reps, parent_lib):
+    """12 query heads of 64 over Hkv key/value heads, Tn = 1: decode and append, 16-bit and fp8 cache."""
+    import ctypes
+    dev, dt = torch.device("cuda", 0), torch.bfloat16
+    H, D = 12, 64
+    E = H * D
+    heads = [H] + [h for h in kv_heads if h != H]
+    parent = _c_calls(ctypes.CDLL(parent_lib)) if parent_lib else None
+    say(f"== grouped-query decode, H = {H} query heads of {D}, Tn = 1, bf16, default splits, GPU time per call in us "
+        f"(mean of {reps} back-to-back launches; median of {passes} passes, min .. max; all variants alternate within "
+        "a pass)")
+    say("   x = time of the Hkv = 12 row of the same cache format / this row's time; bytes = this row's cache bytes "
+        "read / the 12-head row's (the bound on 1/x); GB/s = valid cache bytes / time")
+    for B in (1, 32):
+        for L in (128, 1024, 4096):
+            pos, tcap = L - 1, (L + 63) // 64 * 64
+            variants = []                                        # (name, Hkv, fp8, run decode, run append, bytes)
+            for fp8 in (False, True):
+                for Hkv in heads:
+                    Ekv = Hkv * D
+                    g = torch.Generator().manual_seed(L + B + Hkv)
+                    qkv = (torch.randn(B, 1, E + 2 * Ekv, generator=g) * 0.8).to(dt).to(dev)
+                    hist = (torch.randn(B, L, E + 2 * Ekv, generator=g) * 0.8).to(dt).to(dev)
+                    R = TN.kv_fp8_row_bytes(Hkv, D) if fp8 else 4 * Ekv
+                    kv = torch.zeros(B, tcap, R if fp8 else 2 * Ekv, dtype=torch.uint8 if fp8 else dt, device=dev)
+                    assert TN.attn_kv_append(hist, kv, H, 0, Hkv=Hkv) is kv
+                    assert TN.attn_kv_append(qkv, kv, H, pos, Hkv=Hkv) is kv
+                    splits = TN.attn_decode_splits(B, 1, H, D, L, Hkv=Hkv)
+                    assert TN.attn_decode(qkv, kv, H, pos, splits=splits, Hkv=Hkv) is not None
+                    variants.append((f"{'fp8' if fp8 else '16-bit'} Hkv={Hkv:2d} S={splits:2d}", Hkv, fp8,
+                                     lambda q=qkv, c=kv, k=Hkv, s=splits: TN.attn_decode(q, c, H, pos, splits=s, Hkv=k),
+                                     lambda q=qkv, c=kv, k=Hkv: TN.attn_kv_append(q, c, H, pos, Hkv=k), B * L * R))
+            td, ta = [[] for _ in variants], [[] for _ in variants]
+            for _ in range(passes):
+                for i, v in enumerate(variants):
+                    td[i].append(gpu_time(v[3], reps=reps, warmup=3) * 1e3)
+                for i, v in enumerate(variants):
+                    ta[i].append(gpu_time(v[4], reps=reps, warmup=3) * 1e3)
+            base = {}
+            for i, (name, Hkv, fp8, _, _, nbytes) in enumerate(variants):
+                md, lo, hi = _stats(td[i])
+                ma, _, _ = _stats(ta[i])
+                if Hkv == H:
+                    base[fp8] = (md, nbytes)
+                bd, bb = base[fp8]
+                say(f"B={B:2d} L={L:4d} {name}: decode {md:7.2f} ({lo:.2f} .. {hi:.2f}) us  x {bd / md:5.2f}  bytes "
+                    f"{nbytes / bb:5.3f}  {nbytes / md / 1e3:7.1f} GB/s | append {ma:6.2f} us")
+    say()
+    if parent is None:
+        return
+    from deeplearning4j_amd.ops import native
+    ours = _c_calls(ctypes.CDLL(native.KERNEL_LIB))
+    say("== the multi-head kernels of this tree against the parent commit's library, alternating on one device: "
+        "parent, ours, parent again in every pass; 'parent spread' = (max - min) / median over ALL parent timings, "
+        "ours / parent = ratio of the medians (above 1 = slower)")
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+
+    def flash(lib, B, T):
+        """(forward, backward) closures on a library's multi-head entry points."""
+        g = torch.Generator().manual_seed(T)
+        qkv = (torch.randn(B, T, 3 * E, generator=g) * 0.8).to(dt).to(dev)
+        dout = torch.randn(B, T, E, generator=g).to(dt).to(dev)
+        out, dq = torch.empty(B, T, E, dtype=dt, device=dev), torch.empty_like(qkv)
+        lse, dd = torch.empty(B, H, T, device=dev), torch.empty(B, H, T, device=dev)
+        st = lambda: vp(torch.cuda.current_stream().cuda_stream)                 # noqa: E731
+        fw, bw = lib.dl4j_attn_fwd_dt, lib.dl4j_attn_bwd_dt
+        fw.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ci, vp]
+        bw.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ci, vp]
+        sc = ctypes.c_float(D ** -0.5)
+        f = lambda: fw(1, qkv.data_ptr(), None, out.data_ptr(), lse.data_ptr(), B, T, H, D, sc, 1, st())  # noqa: E731
+        b = lambda: bw(1, qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), None, lse.data_ptr(),  # noqa: E731
+                       dd.data_ptr(), dq.data_ptr(), B, T, H, D, sc, 1, st())
+        assert f() == 0 and b() == 0
+        return f, b, dq
+
+    def ab(label, run_parent, run_ours):
+        tp, to = [], []
+        for _ in range(passes):
+            tp.append(gpu_time(run_parent, reps=reps, warmup=3) * 1e3)
+            to.append(gpu_time(run_ours, reps=reps, warmup=3) * 1e3)
+            tp.append(gpu_time(run_parent, reps=reps, warmup=3) * 1e3)
+        mp, lp, hp = _stats(tp)
+        mo, lo, ho = _stats(to)
+        say(f"{label}: parent {mp:8.2f} ({lp:.2f} .. {hp:.2f}) us, spread {(hp - lp) / mp * 100:4.1f} %  "
+            f"ours {mo:8.2f} ({lo:.2f} .. {ho:.2f}) us  ours / parent {mo / mp:6.3f}x")
+
+    for B, T in ((8, 512), (32, 128)):
+        fp, bp, dqp = flash(ctypes.CDLL(parent_lib), B, T)
+        fo, bo, dqo = flash(ctypes.CDLL(native.KERNEL_LIB), B, T)
+        torch.cuda.synchronize()
+        say(f"flash B={B} T={T} causal: backward outputs bitwise equal: {torch.equal(dqp, dqo)}")
+        ab(f"forward  B={B:2d} T={T:3d}", fp, fo)
+        ab(f"backward B={B:2d} T={T:3d}", bp, bo)
+    for B in (1, 32):
+        for L in (128, 1024, 4096):
+            pos, tcap = L - 1, (L + 63) // 64 * 64
+            g = torch.Generator().manual_seed(L + B)
+            qkv = (torch.randn(B, 1, 3 * E, generator=g) * 0.8).to(dt).to(dev)
+            kv = (torch.randn(B, tcap, 2 * E, generator=g) * 0.8).to(dt).to(dev)
+            splits = TN.attn_decode_splits(B, 1, H, D, L)
+            ws = torch.empty(max(1, B * H * splits * (D + 2)), dtype=torch.float32, device=dev)
+            o1, o2 = torch.empty(B, 1, E, dtype=dt, device=dev), torch.empty(B, 1, E, dtype=dt, device=dev)
+            assert parent[1](False, qkv, kv, o1, ws, B, H, D, pos, splits) == 0
+            assert ours[1](False, qkv, kv, o2, ws, B, H, D, pos, splits) == 0
+            torch.cuda.synchronize()
+            same = torch.equal(o1, o2)
+            ab(f"decode   B={B:2d} L={L:4d} splits={splits:2d} (bitwise equal: {same})",
+               lambda: parent[1](False, qkv, kv, o1, ws, B, H, D, pos, splits),
+               lambda: ours[1](False, qkv, kv, o2, ws, B, H, D, pos, splits))
+    say()
+
+
 def _sync_time(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -222,11 +347,18 @@ def main():
     ap.add_argument("--full-steps", type=int, default=16)
     ap.add_argument("--cache", choices=["fp8"], default=None,
                     help="compare the fp8 key/value cache's kernels with the 16-bit ones")
-    ap.add_argument("--parent-lib", default=None, help="--cache: kernel library built from the parent commit")
+    ap.add_argument("--kv-heads", default=None,
+                    help="grouped-query attention: key/value head counts (divisors of 12, comma separated) to compare "
+                         "with the 12-head row")
+    ap.add_argument("--parent-lib", default=None,
+                    help="--cache / --kv-heads: kernel library built from the parent commit")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args()
-    if not (a.kernel or a.model or a.cache):
-        ap.error("give --kernel, --model and / or --cache fp8")
+    if not (a.kernel or a.model or a.cache or a.kv_heads):
+        ap.error("give --kernel, --model, --cache fp8 and / or --kv-heads N")
+    kv_heads = [int(h) for h in a.kv_heads.split(",")] if a.kv_heads else []
+    if any(h < 1 or 12 % h for h in kv_heads):
+        ap.error("--kv-heads: every count must divide the 12 query heads")
     if not torch.cuda.is_available():
         sys.exit("bench_decode.py measures on the GPU; no device found")
     global _out
@@ -239,6 +371,8 @@ def main():
         model_mode([int(b) for b in a.batch.split(",")], a.cached_steps, a.full_steps)
     if a.cache:
         cache_fp8_mode(max(a.passes, 5), a.reps, a.parent_lib)
+    if kv_heads:
+        gqa_mode(kv_heads, max(a.passes, 5), a.reps, a.parent_lib)
     if _out is not None:
         _out.close()
 

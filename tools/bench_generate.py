@@ -30,10 +30,15 @@
              pass: 12-layer, hidden-768 model with maxPositions 4096 at the batch sizes of --batch (default 32),
              prefix 1024 and the longest prefix that leaves room for the new tokens; also the cache bytes per layer.
 
+  --kv-heads N[,N..]  grouped-query attention: generate() and generate(useGraph=True) of the 12-layer, hidden-768
+             model built with nKVHeads = N against the 12-head model (one network per count), prefix 1024, the
+             variants alternating within every pass; also the cache bytes per cached token and layer.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
        python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]
-       python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]"""
+       python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]
+       python tools/bench_generate.py --kv-heads 4 [--batch 32] [--out FILE]"""
 import argparse
 import sys
 import time
@@ -458,6 +463,54 @@ def cache_fp8_mode(batches, n, passes):
     say()
 
 
+def kv_heads_mode(kv_heads, batches, n, passes):
+    """generate() and generate(useGraph=True) of the 12-layer, hidden-768 model with nKVHeads key/value heads against
+    the 12-head model: one network per head count (the projection shapes differ), the variants alternating."""
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, MAXP, H, E, P = 77, 2048, 12, 768, 1024
+    D = E // H
+    heads = [H] + [h for h in kv_heads if h != H]
+    nets = {h: TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=E, layers=12, heads=H, nKVHeads=h,
+                                         maxPositions=MAXP, dataType=DataType.BFLOAT16).init(device=DEV) for h in heads}
+    say(f"== generate() with grouped key/value heads on TextGenerationTransformer(768, 12 layers, 12 query heads, "
+        f"maxPositions {MAXP}), bf16, V = {V}, greedy, prefix {P}, {n} new tokens; whole calls (prompt included) on "
+        f"the host clock, ended by a device synchronise; median of {passes} passes (min .. max), the variants alternating "
+        "within a pass; x = tokens/s against the 12-head model's same mode")
+    say("   16-bit cache bytes per cached token and layer: "
+        + ", ".join(f"nKVHeads {h}: {4 * h * D} ({h / H:.3f})" for h in heads)
+        + "; parameters: " + ", ".join(f"nKVHeads {h}: {nets[h].numParams()}" for h in heads))
+    for mb in batches:
+        prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb + P)).to(DEV)
+        variants = [(f"nKVHeads {h:2d} {mode}", nets[h], kw)
+                    for mode, kw in (("eager", {}), ("graph", dict(useGraph=True))) for h in heads]
+
+        def call(net, kw, tokens=n):
+            net.rnnClearPreviousState()
+            return net.generate(prompt, maxNewTokens=tokens, **kw)
+
+        for _, net, kw in variants:
+            call(net, kw)
+        times = [[] for _ in variants]
+        for _ in range(passes):
+            for i, (_, net, kw) in enumerate(variants):
+                times[i].append(_sync_time(lambda: call(net, kw)))
+        med = [sorted(t)[len(t) // 2] for t in times]
+        few = max(2, n // 4)
+        short = []
+        for _, net, kw in variants:
+            call(net, kw, few)
+            short.append(sorted(_sync_time(lambda: call(net, kw, few)) for _ in range(passes))[passes // 2])
+        per = [(m - ts) / (n - few) * 1e3 for ts, m in zip(short, med)]
+        for i, ((vn, _, _), t, m) in enumerate(zip(variants, times, med)):
+            b = (i // len(heads)) * len(heads)                   # the 12-head row of the same mode
+            say(f"batch {mb:2d} {vn}: {mb * n / m:9.1f} tok/s  {m * 1e3:8.1f} ms per call ({min(t) * 1e3:.1f} .. "
+                f"{max(t) * 1e3:.1f})  x {med[b] / m:5.3f} | step alone {per[i]:6.2f} ms  x {per[b] / per[i]:5.3f}")
+    for net in nets.values():
+        net.rnnClearPreviousState()
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -468,6 +521,8 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--cache", choices=["fp8"], default=None,
                     help="compare generate() with the fp8 key/value cache and with the 16-bit one")
+    ap.add_argument("--kv-heads", default=None,
+                    help="grouped-query attention: nKVHeads values (divisors of 12, comma separated) against 12")
     ap.add_argument("--parent-lib", default=None,
                     help="kernel library built from the parent commit (--ragged, --graph)")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
@@ -492,6 +547,8 @@ def main():
         graph_mode(a.batch, a.tokens, a.passes, a.parent_lib)
     if a.cache:
         cache_fp8_mode(a.batch, a.tokens, a.passes)
+    if a.kv_heads:
+        kv_heads_mode([int(h) for h in a.kv_heads.split(",")], a.batch, a.tokens, a.passes)
 
 
 if __name__ == "__main__":
