@@ -176,7 +176,8 @@ __global__ __launch_bounds__(256) void emb_scatter_kernel(const T* __restrict__ 
 // BERT input embedding: e[r, :] = Wword[idx[r], :] + Wpos[pos0 + r % T, :] + Wtype[0, :] for r = b*T + t, summed in
 // fp32 and rounded once (three gathers and two adds of the imported graph in one pass). Rows are 16-byte vectors.
 // pos0: position of the chunk's first token (0 for a whole sequence, the tokens already seen in rnnTimeStep).
-// posrow(r): the position-table row of output row r.
+// posrow(r): the position-table row of output row r. Wp may be null (a model whose positions enter elsewhere, e.g.
+// through rotary attention): that addend is skipped.
 template <typename T, typename PosRow>
 __device__ __forceinline__ void bert_embed_fwd_rows(const T* __restrict__ Ww, const T* __restrict__ Wp,
                                                     const T* __restrict__ Wt, const long long* __restrict__ idx,
@@ -187,15 +188,15 @@ __device__ __forceinline__ void bert_embed_fwd_rows(const T* __restrict__ Ww, co
     const long long k = idx[r];
     const bool ok = k >= 0 && k < V;
     const T* a = Ww + (ok ? k : 0) * sw;
-    const T* p = Wp + (long long)posrow(r) * sp;
+    const T* p = Wp ? Wp + (long long)posrow(r) * sp : nullptr;
     T* dst = out + (long long)r * E;
     for (int c = lane * 8; c < E; c += 512) {
-      float va[8], vp[8], vt[8];
+      float va[8], vp[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vt[8];
       Vec8<T>::load(a + c, va);
-      Vec8<T>::load(p + c, vp);
+      if (p) Vec8<T>::load(p + c, vp);
       Vec8<T>::load(Wt + c, vt);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) va[e] = (ok ? va[e] : 0.f) + vp[e] + vt[e];
+      for (int e = 0; e < 8; ++e) va[e] = p ? (ok ? va[e] : 0.f) + vp[e] + vt[e] : (ok ? va[e] : 0.f) + vt[e];
       Vec8<T>::store(dst + c, va);
     }
   }
@@ -412,7 +413,8 @@ DL4J_API int dl4j_emb_scatter_add(int dt, const void* g, const long long* idx, f
 }
 
 // Wword / Wpos: row strides sw / sp with unit column stride; Wtype row 0 contiguous; E % 8 == 0, 16-byte aligned.
-// Positions pos0 .. pos0 + Tn - 1 (the caller checks them against Wpos' rows).
+// Positions pos0 .. pos0 + Tn - 1 (the caller checks them against Wpos' rows). Wp null: no position addend (sp, pos0
+// and the ragged entry's shortfall / P are then not used).
 DL4J_API int dl4j_bert_embed_fwd_pos(int dt, const void* Ww, const void* Wp, const void* Wt, const long long* idx,
                                      void* out, int rows, int Tn, int E, long long sw, long long sp, int V, int pos0,
                                      hipStream_t s) {
@@ -432,6 +434,7 @@ DL4J_API int dl4j_bert_embed_fwd_ragged(int dt, const void* Ww, const void* Wp, 
                                         long long sp, int V, int pos0, int P, hipStream_t s) {
   if (!shortfall) return dl4j_bert_embed_fwd_pos(dt, Ww, Wp, Wt, idx, out, rows, Tn, E, sw, sp, V, pos0, s);
   if (rows <= 0) return 0;
+  if (!Wp) return dl4j_bert_embed_fwd_pos(dt, Ww, Wp, Wt, idx, out, rows, Tn, E, sw, sp, V, pos0, s);
   if (Tn <= 0 || pos0 < 0 || P < 1 || E % 8 || sw % 8 || sp % 8) return -1;
   for (const void* q : {Ww, Wp, Wt, (const void*)out})
     if (reinterpret_cast<uintptr_t>(q) & 15) return -1;

@@ -969,13 +969,17 @@ class TextGenerationTransformer(ZooModel):
         return net.generate(prompt, promptLengths=promptLengths, **cfg)
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
-                 maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, **kw):
+                 maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, positionEncoding=None,
+                 ropeTheta=10000.0, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
         self.maxPositions, self.learningRate = maxPositions, learningRate
         self.cacheDataType = cacheDataType      # None, or "fp8": the key/value cache format of every block
         self.nKVHeads = nKVHeads                # None, or a divisor of heads: grouped-query attention in every block
+        # None: learned positions in the embedding (at most maxPositions tokens); "rotary": every block rotates its
+        # Q / K heads with base ropeTheta, the embedding has no position table and maxPositions is unused
+        self.positionEncoding, self.ropeTheta = positionEncoding, ropeTheta
 
     def graphBuilder(self):
         from ..nn.conf import BertEmbeddingLayer, TransformerEncoderLayer
@@ -983,12 +987,14 @@ class TextGenerationTransformer(ZooModel):
              .graphBuilder())
         g.addInputs("tokens")
         g.addLayer("embeddings", BertEmbeddingLayer.Builder().nIn(self.numLabels).nOut(self.hidden)
-                   .maxPositions(self.maxPositions).inputLength(self.inputShape[0]).build(), "tokens")
+                   .maxPositions(self.maxPositions).inputLength(self.inputShape[0])
+                   .positionEmbeddings(self.positionEncoding is None).build(), "tokens")
         prev = "embeddings"
         for i in range(self.layers):
             g.addLayer(f"decoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
                        .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
-                       .nKVHeads(self.nKVHeads).build(), prev)
+                       .nKVHeads(self.nKVHeads).positionEncoding(self.positionEncoding)
+                       .ropeTheta(self.ropeTheta).build(), prev)
             prev = f"decoder_{i}"
         g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
                    .nIn(self.hidden).nOut(self.numLabels).build(), prev)

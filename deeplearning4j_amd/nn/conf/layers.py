@@ -1414,6 +1414,27 @@ def _check_kv_heads(layer, grouped=True):
             f"nHeads = {layer.nHeads}, got {v!r}")
 
 
+ROTARY = "rotary"
+
+
+def _check_position_encoding(layer, headSize=None):
+    """``positionEncoding``: None (the default: positions enter through the embedding layer only) or "rotary" (RoPE:
+    the Q and K heads are rotated by their positions before attention, half-split pairs with ``ropeTheta`` as the
+    base; csrc/attention_rope.hip). ``headSize``: checked to be even once it is known."""
+    v, th = layer.positionEncoding, layer.ropeTheta
+    if v is not None and v != ROTARY:
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: positionEncoding is None or \"{ROTARY}\", got {v!r}")
+    ok = isinstance(th, (int, float)) and not isinstance(th, bool) and math.isfinite(th) and th > 0
+    if not ok:
+        raise DL4JInvalidConfigException(f"{_who(layer)}: ropeTheta must be a finite positive number, got {th!r}")
+    layer.ropeTheta = float(th)
+    if v == ROTARY and headSize and headSize % 2:
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: positionEncoding \"{ROTARY}\" rotates pairs of columns and needs an even head size, got "
+            f"{headSize}")
+
+
 def _check_drop_prob(layer, name):
     """``name`` is a DROP probability in [0, 1) (HuggingFace's convention; 0.0 = off) — the opposite of the
     retain-probability ``dropOut`` of the reference's layers."""
@@ -1436,10 +1457,14 @@ class SelfAttentionLayer(FeedForwardLayer):
 
     ``nKVHeads``: None (the default: one key/value head per query head) or a divisor of ``nHeads``: grouped-query
     attention, ``nHeads / nKVHeads`` query heads share a key/value head (1 = multi-query). ``Wk`` / ``Wv`` are then
-    [nIn, nKVHeads * headSize] and the rnnTimeStep cache holds the key/value heads only."""
+    [nIn, nKVHeads * headSize] and the rnnTimeStep cache holds the key/value heads only.
+
+    ``positionEncoding``: None (the default) or "rotary": rotary position embeddings (RoPE) on the Q and K heads, with
+    base ``ropeTheta`` (default 10000). A token's position is its index in the sequence, in ``rnnTimeStep`` the index
+    of its cache row; the cache then holds rotated keys. The head size must be even."""
     FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False, "attentionDropout": 0.0,
-              "cacheDataType": None, "nKVHeads": None}
-    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads")
+              "cacheDataType": None, "nKVHeads": None, "positionEncoding": None, "ropeTheta": 10000.0}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta")
     RUNTIME = "deeplearning4j_amd.nn.layers.attention:SelfAttentionLayerImpl"
 
     def _post_init(self):
@@ -1447,9 +1472,17 @@ class SelfAttentionLayer(FeedForwardLayer):
         _check_drop_prob(self, "attentionDropout")
         _check_cache_dtype(self)
         _check_kv_heads(self)
+        self._check_rope()
+
+    def _check_rope(self):
+        hs = self.headSize or (self.nOut // self.nHeads if self.nOut else 0)
+        _check_position_encoding(self, hs)
 
     def kvHeads(self):
         return self.nHeads if self.nKVHeads is None else self.nKVHeads
+
+    def rotary(self):
+        return self.positionEncoding == ROTARY
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1461,6 +1494,7 @@ class SelfAttentionLayer(FeedForwardLayer):
         self.nIn = inputType.size
         if not self.nOut:
             self.nOut = self.nIn
+        self._check_rope()
 
     def getPreProcessorForInputType(self, inputType):
         return None
@@ -1497,10 +1531,15 @@ class TransformerEncoderLayer(FeedForwardLayer):
     ``nKVHeads``: None (the default: one key/value head per query head) or a divisor of ``nHeads``: grouped-query
     attention, ``nHeads / nKVHeads`` query heads share a key/value head (1 = multi-query). The fused projection is
     then ``Wqkv [E, E + 2*Ekv]`` with ``Ekv = nKVHeads * E / nHeads`` and the rnnTimeStep cache of a causal block
-    holds the key/value heads only (``nKVHeads / nHeads`` of the bytes; stacks with "fp8")."""
+    holds the key/value heads only (``nKVHeads / nHeads`` of the bytes; stacks with "fp8").
+
+    ``positionEncoding``: None (the default) or "rotary": rotary position embeddings (RoPE) on the Q and K columns of
+    the fused projection, with base ``ropeTheta`` (default 10000). A token's position is its index in the sequence,
+    in ``rnnTimeStep`` the index of its cache row; the cache then holds rotated keys. The head size must be even."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
-              "attentionDropout": 0.0, "cacheDataType": None, "nKVHeads": None}
-    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads")
+              "attentionDropout": 0.0, "cacheDataType": None, "nKVHeads": None, "positionEncoding": None,
+              "ropeTheta": 10000.0}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta")
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
 
     def _post_init(self):
@@ -1509,9 +1548,16 @@ class TransformerEncoderLayer(FeedForwardLayer):
         _check_drop_prob(self, "attentionDropout")
         _check_cache_dtype(self)
         _check_kv_heads(self)
+        self._check_rope()
+
+    def _check_rope(self):
+        _check_position_encoding(self, self.nIn // self.nHeads if self.nIn else 0)
 
     def kvHeads(self):
         return self.nHeads if self.nKVHeads is None else self.nKVHeads
+
+    def rotary(self):
+        return self.positionEncoding == ROTARY
 
     def getOutputType(self, layerIndex, inputType):
         T = inputType.timeSeriesLength if isinstance(inputType, InputTypeRecurrent) else -1
@@ -1522,6 +1568,7 @@ class TransformerEncoderLayer(FeedForwardLayer):
             return
         self.nIn = inputType.size
         self.nOut = self.nIn
+        self._check_rope()
 
     def getPreProcessorForInputType(self, inputType):
         return None
@@ -1645,8 +1692,13 @@ class TransformerDecoderLayer(_TwoInputLayer):
 class BertEmbeddingLayer(FeedForwardLayer):
     """Token ids [mb, T] -> LayerNorm(word + position + token-type(0) embeddings) as [mb, nOut, T]
     (nIn = vocabulary size). ``hiddenDropout``: DROP probability in [0, 1) applied after the LayerNorm in training
-    (0.0 = off, the default; HuggingFace's ``hidden_dropout_prob``, not a retain probability)."""
-    FIELDS = {"maxPositions": 512, "typeVocabSize": 2, "layerNormEps": 1e-12, "inputLength": -1, "hiddenDropout": 0.0}
+    (0.0 = off, the default; HuggingFace's ``hidden_dropout_prob``, not a retain probability).
+    ``positionEmbeddings``: True (the default), or False for a model whose positions enter elsewhere (rotary
+    attention blocks): no ``Wpos`` parameter, LayerNorm(word + token-type(0)), ``maxPositions`` unused and no limit on
+    the length of a generated sequence."""
+    FIELDS = {"maxPositions": 512, "typeVocabSize": 2, "layerNormEps": 1e-12, "inputLength": -1, "hiddenDropout": 0.0,
+              "positionEmbeddings": True}
+    _OMIT_AT_DEFAULT = ("positionEmbeddings",)
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:BertEmbeddingLayerImpl"
 
     def _post_init(self):
@@ -1664,8 +1716,9 @@ class BertEmbeddingLayer(FeedForwardLayer):
 
     def param_specs(self):
         E = self.nOut
-        return [ParamSpec("Wword", [self.nIn, E], "c", "weight", self.nIn, E),
-                ParamSpec("Wpos", [self.maxPositions, E], "c", "weight", self.maxPositions, E),
+        pos = [ParamSpec("Wpos", [self.maxPositions, E], "c", "weight", self.maxPositions, E)] \
+            if self.positionEmbeddings else []
+        return [ParamSpec("Wword", [self.nIn, E], "c", "weight", self.nIn, E)] + pos + [
                 ParamSpec("Wtype", [self.typeVocabSize, E], "c", "weight", self.typeVocabSize, E),
                 ParamSpec("lng", [1, E], "c", "const", value=1.0), ParamSpec("lnb", [1, E], "c", "const", value=0.0)]
 

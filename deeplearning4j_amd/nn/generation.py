@@ -403,7 +403,8 @@ def _sample(stepper, p, cfg):
 
 def _pin_capacity(stepper, Tp, N):
     """Tp + N positions; one less (the last token is sampled, never fed) where a position table ends there."""
-    limit = min([l.rnnPinLimit() for _, l in stepper.token_layers() if hasattr(l, "rnnPinLimit")], default=None)
+    limits = [l.rnnPinLimit() for _, l in stepper.token_layers() if hasattr(l, "rnnPinLimit")]
+    limit = min([n for n in limits if n is not None], default=None)         # None: a layer without a position table
     return Tp + N - 1 if limit is not None and limit == Tp + N - 1 else Tp + N
 
 

@@ -778,7 +778,9 @@ class ComputationGraph(BaseNetwork):
     def rnnSetCacheDataType(self, value):
         """The format of the rnnTimeStep key/value caches from the next sequence on, as
         MultiLayerNetwork.rnnSetCacheDataType: None (the compute dtype) or "fp8" on every layer that has
-        ``cacheDataType``. Refused, naming the vertex and changing nothing, while a layer holds state."""
+        ``cacheDataType``. Refused, naming the vertex and changing nothing, while a layer holds state. A rotary layer
+        (``positionEncoding="rotary"``) stores rotated keys in either format: its state is valid only for a layer with
+        the same ``ropeTheta``."""
         from ..generation import set_cache_data_type
         set_cache_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value)
 

@@ -19,6 +19,9 @@ the layer's PhiloxStream and regenerated in the backward; the explicit path take
 nHeads / nKVHeads query heads of its group and dK / dV come back summed over the group.
 ``rnnTimeStep`` on a causal layer appends the chunk's K / V to a per-layer cache and attends over it
 (``KVCacheState`` in transformer.py, csrc/attention_decode.hip).
+``positionEncoding="rotary"``: the Q and K columns of the buffer are rotated by their positions after the projection
+(csrc/attention_rope.hip, in place), the rotated buffer is what the attention reads and the backward keeps, and the
+transposed rotation is applied to dQ | dK before the weight, bias and input gradients.
 
 ``CrossAttentionLayerImpl`` is the two-sequence counterpart (a two-input graph layer): Q = X Wq + bq from its own
 stream [mb, nIn, Tq], KV = M Wkv + bkv from the memory [mb, nInMemory, Tk] in one GEMM straight into the
@@ -28,7 +31,7 @@ backward kernels, dWq / dWkv and their biases, dX = dQ Wq^T, dM = dKV Wkv^T, ret
 import torch
 
 from .base import LayerImpl, bias_grad_, matmul, weight_grad_
-from .transformer import DropoutSites, KVCacheState, MemoryKVState, _cross_bwd, _cross_fwd, _memory_mask
+from .transformer import DropoutSites, KVCacheState, MemoryKVState, _cross_bwd, _cross_fwd, _memory_mask, _rope
 from ...ops.gemm import mmul
 
 
@@ -91,6 +94,8 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         dt = self.W("Wq").dtype
         X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
         qkv = self._project(X, mb * T, x.device)
+        if self.conf.rotary():
+            qkv = _rope(qkv, mb, T, H, self.conf.kvHeads(), self.conf.ropeTheta, "SelfAttentionLayer")
         m = mask.reshape(mb, T) if mask is not None else None
         drop = float(self.conf.attentionDropout) if training else 0.0
         if drop > 0.0:
@@ -123,7 +128,8 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         dt = self.W("Wq").dtype
         X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
         qkv = self._project(X, mb * T, x.device)
-        o = self.cachedAttention(qkv.reshape(mb, T, -1), H, "SelfAttentionLayer rnnTimeStep", self.conf.kvHeads())
+        o = self.cachedAttention(qkv.reshape(mb, T, -1), H, "SelfAttentionLayer rnnTimeStep", self.conf.kvHeads(),
+                                 self.conf.ropeTheta if self.conf.rotary() else None)
         Y = matmul(o.reshape(mb * T, d), self.W("Wo"), bias=self.Wbias("bo"))
         z = Y.reshape(mb, T, -1).permute(0, 2, 1)
         y = self.conf.activation.getActivation(z, False) if self.conf.activation is not None else z
@@ -146,6 +152,8 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         dqkv = self._attn_bwd(qkv, dO, mb, T, H, m, actx).reshape(mb * T, blocks[2][1])
         if not dqkv.is_contiguous():
             dqkv = dqkv.contiguous()
+        if self.conf.rotary():
+            dqkv = _rope(dqkv, mb, T, H, self.conf.kvHeads(), self.conf.ropeTheta, "SelfAttentionLayer", inverse=True)
         Xt = X.t()
         dX = None
         for (lo, hi), (wk, bk) in zip(blocks, (("Wq", "bq"), ("Wk", "bk"), ("Wv", "bv"))):

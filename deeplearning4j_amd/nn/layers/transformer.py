@@ -32,6 +32,13 @@ Grouped-query attention (``nKVHeads`` on the encoder block): Wqkv projects to [B
 nKVHeads key/value heads only), the flash kernels share each of them between the query heads of its group, the
 backward returns dK / dV summed over the group, and the cache holds 2*Ekv columns (or the fp8 rows of nKVHeads heads).
 
+Rotary position embeddings (``positionEncoding="rotary"`` on the encoder block): the Q and K columns of qkv are
+rotated by their positions right after the projection (csrc/attention_rope.hip, in place), the rotated qkv is what the
+attention reads and the backward keeps, and the transposed rotation runs on dQ | dK before the weight, bias and input
+gradients. In ``rnnTimeStep`` a token's position is the index of its cache row and the append launch rotates as it
+stores, so the cache holds rotated keys and a step gains no launch. ``BertEmbeddingLayer.positionEmbeddings(False)``
+drops the learned position table (and with it the limit on a generated sequence's length).
+
 Decoder block (``TransformerDecoderLayerImpl``, a two-input graph layer: decoder stream + encoder memory): causal
 self-attention as above, then cross-attention of q2 = h1·Wq2 over kv2 = memory·Wkv2 (one GEMM straight into the
 kv [mb, Tk, 2E] layout of csrc/attention_cross.hip), then the FFN, each followed by LayerNorm(+residual). Its
@@ -242,6 +249,22 @@ def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx, Hkv=None):
     return TN.attention_bwd_explicit(ctx[1], dctx.reshape(B, T, -1), qkv.dtype).reshape(B * T, -1)
 
 
+def _rope(qkv, B, T, H, Hkv, theta, what, inverse=False):
+    """Rotary position embeddings on the Q | K columns of qkv [B*T, W] at positions 0 .. T-1 (``inverse``: the
+    transposed rotation, for dQ | dK): csrc/attention_rope.hip in place on a GPU in bf16 / fp16 with head size
+    64 / 128, else ``rope_reference``, counted as a fallback on a GPU. -> the rotated [B*T, W]."""
+    from ...ops import transformer_native as TN
+    q3 = qkv.reshape(B, T, -1)
+    if _native(q3, "attention") and TN.attn_rope(q3, H, 0, theta, Hkv=Hkv, inverse=inverse) is not None:
+        return qkv
+    if qkv.is_cuda:
+        from ...ops import fallback
+        fallback.record("attention", f"{what} rotary embedding, head size {q3.shape[-1] // (H + 2 * Hkv)} / dtype "
+                                     f"{qkv.dtype}: torch reference path")
+    pos = torch.arange(T, device=qkv.device)
+    return TN.rope_reference(q3, H, pos, theta, Hkv, inverse).reshape(qkv.shape)
+
+
 # ------------------------------------------------------------------------------------------------ cached decoding
 class KVCacheState:
     """rnnTimeStep state of a causal attention layer: one key/value cache ``kv [mb, Tcap, 2E]`` in the compute dtype
@@ -261,7 +284,12 @@ class KVCacheState:
     One tensor of 16-byte-multiple rows, so growth, trimming, reordering and pinning treat it as they treat the
     16-bit cache. A chunk of >= 64 tokens into an empty cache attends over its own unquantised K / V (the flash
     prompt path; only what it stores is quantised); every other chunk attends over what the cache holds, its own
-    new rows included. The state handed out is ``{"kv": uint8 [mb, L, R], "kvFormat": "fp8"}``."""
+    new rows included. The state handed out is ``{"kv": uint8 [mb, L, R], "kvFormat": "fp8"}``.
+
+    A rotary layer (``positionEncoding="rotary"``) stores ROTATED keys: a token is rotated by the index of its cache
+    row as it is appended. Everything that moves whole rows (growth, trimming, reordering, pinning, the cache format,
+    the state handed out and taken in) needs nothing for that, but such a state is valid only for a layer with the
+    same ``ropeTheta``."""
     _kv = None
     _kv_len = 0
     _kv_alt = None      # rnnReorderState's second buffer (same shape as _kv, or None): the two are swapped per call
@@ -282,7 +310,8 @@ class KVCacheState:
         """Pin the positions (the network's rnnPinState): the cache is reserved for ``capacity`` rows, the host bound
         becomes ``capacity - 1`` for good and ``short`` (int32 [mb] on the device, shared by every pinned layer of the
         network, which lowers it once per step) carries the rows' real positions: row b stands at
-        ``capacity - 1 - short[b]``. ``dryRun`` only validates."""
+        ``capacity - 1 - short[b]``. ``dryRun`` only validates. A rotary layer's new token is rotated by that row
+        index, read from ``short`` on the device."""
         if self._kv is None:
             return
         _pin_check(self, capacity, self._kv_len, self._kv_pinned)
@@ -295,7 +324,8 @@ class KVCacheState:
     def rnnTrimState(self, lengths, dryRun=False):
         """The rows of the stored chunk(s) were right-padded: row b holds ``lengths[b]`` real tokens (1 <= lengths[b]
         <= tokens seen). ``lengths``: integers [mb] (read on the host once, here). Once per sequence; ``dryRun``
-        only validates. A layer without a cache (a bidirectional block) has nothing to trim."""
+        only validates. A layer without a cache (a bidirectional block) has nothing to trim. A rotary layer's rows
+        hold keys rotated by their own row index, which trimming does not change."""
         if self._kv is None:
             return
         _refuse_pinned(self, "rnnTrimState", self._kv_pinned)
@@ -306,7 +336,8 @@ class KVCacheState:
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of the cache becomes the old row ``parents[i]`` (int32 device tensor [mbNew]; mbNew may differ from
         the stored minibatch size). The valid rows are gathered into a second buffer of the same capacity
-        (csrc/generation.hip; never in place) and the two swap, so a steady-state call allocates nothing."""
+        (csrc/generation.hip; never in place) and the two swap, so a steady-state call allocates nothing. Whole rows
+        move and keep their row index, so a rotary layer's rotated keys stay valid."""
         kv = self._kv
         if kv is None:
             return
@@ -329,6 +360,7 @@ class KVCacheState:
         return getattr(self.conf, "nKVHeads", None) or self.conf.nHeads
 
     def rnnGetPreviousState(self):
+        """The state of a rotary layer holds rotated keys: it is valid only for a layer with the same ``ropeTheta``."""
         if self._kv is None:
             return {}
         st = {"kv": self._kv[:, :self._kv_len].clone()}
@@ -340,7 +372,8 @@ class KVCacheState:
 
     def rnnSetPreviousState(self, state):
         """Takes the state in either format (16-bit / float ``kv [mb, L, 2E]``, or uint8 rows with
-        ``"kvFormat": "fp8"``) and converts it to the layer's own (plain torch: not a hot path)."""
+        ``"kvFormat": "fp8"``) and converts it to the layer's own (plain torch: not a hot path). A rotary layer takes
+        the keys as rotated by a layer with its own ``ropeTheta``; nothing here can check that."""
         kv = state.get("kv") if state else None
         self.rnnClearPreviousState()
         if kv is None:
@@ -383,13 +416,15 @@ class KVCacheState:
         self._kv = new
         self._kv_alt = None         # the second buffer follows the new capacity at the next rnnReorderState
 
-    def cachedAttention(self, qkv, H, what="rnnTimeStep", Hkv=None):
+    def cachedAttention(self, qkv, H, what="rnnTimeStep", Hkv=None, ropeTheta=None):
         """Causal attention of the chunk qkv [mb, Tn, 3E] ([mb, Tn, E + 2*Ekv] with ``Hkv`` key/value heads, which
         are what the cache then holds) over everything seen since rnnClearPreviousState(): its K / V
         are appended to the cache, its queries attend over the cache. -> [mb, Tn, E]. The decode kernels on a GPU in
         bf16 / fp16 with head size 64 / 128 (the causal flash forward for a prompt of >= 64 tokens into an empty
         cache), else the torch reference, counted as a fallback on a GPU. With the fp8 cache both paths store the
-        quantised rows and attend over the dequantised cache, except for that prompt chunk."""
+        quantised rows and attend over the dequantised cache, except for that prompt chunk.
+        ``ropeTheta`` (a rotary layer): Q and K are rotated by their cache row index pos - short[b] + t, on the
+        kernels by the append launch itself (``attn_rope_append``), so the cache holds rotated keys."""
         from ...ops import transformer_native as TN
         mb, Tn, E3 = qkv.shape
         Hkv = H if Hkv is None else Hkv
@@ -404,9 +439,11 @@ class KVCacheState:
         else:
             self._kv_reserve(mb, 2 * Ekv, pos + Tn, qkv.dtype, qkv.device)
         kv = self._kv
-        out = None
+        out = done = None
         if _native(qkv, "attention") and qkv.is_contiguous() and TN.attn_decode_supported(qkv, kv, H, Hkv):
-            if TN.attn_kv_append(qkv, kv, H, pos, short, Hkv=Hkv) is not None:
+            done = TN.attn_kv_append(qkv, kv, H, pos, short, Hkv=Hkv) if ropeTheta is None else \
+                TN.attn_rope_append(qkv, kv, H, pos, ropeTheta, short, Hkv=Hkv)
+            if done is not None:
                 if pos == 0 and Tn >= 64:
                     out = TN.attn_fwd(qkv, H, None, True, Hkv=Hkv)[0]
                 else:
@@ -415,6 +452,8 @@ class KVCacheState:
             if qkv.is_cuda:
                 from ...ops import fallback
                 fallback.record("attention", f"{what} head size {E // H} / dtype {qkv.dtype}: torch reference path")
+            if ropeTheta is not None and done is None:       # not rotated (and appended) by the kernel already
+                qkv = TN.rope_reference(qkv, H, TN.rope_positions(mb, Tn, pos, short, qkv.device), ropeTheta, Hkv)
             new = TN.kv_fp8_quantize_reference(qkv[:, :, E:], Hkv) if fp8 else qkv[:, :, E:]
             if short is None:
                 kv[:, pos:pos + Tn] = new
@@ -517,6 +556,8 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         if pa > 0.0 or ph > 0.0:
             self.dropoutBegin(x.device)
         qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        if c.rotary():                          # the rotated qkv is what the attention reads and backward keeps
+            qkv = _rope(qkv, B, T, H, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer")
         ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads())
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, ln1, a, d1 = _ln_fwd_drop(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps, ph, self,
@@ -548,7 +589,8 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         B, E, T = x.shape
         xt = _token_major(x).to(self.W("Wqkv").dtype)
         qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
-        ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads, Hkv=c.kvHeads()).reshape(B * T, -1)
+        ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads, Hkv=c.kvHeads(),
+                                   ropeTheta=c.ropeTheta if c.rotary() else None).reshape(B * T, -1)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
         f = matmul(h1, self.W("W1"), bias=self.Wbias("b1"), act="gelu")
@@ -591,6 +633,8 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         _wgrad(g["Wo"], ctx, da)
         dctx = matmul(da, self.W("Wo").t())
         dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads())
+        if c.rotary():                          # the transposed rotation takes dQ | dK back to the projection's output
+            dqkv = _rope(dqkv, B, T, c.nHeads, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer", inverse=True)
         _wgrad(g["Wqkv"], xt, dqkv)
         _bsum(g["bqkv"], dqkv)
         dx = mmul(dqkv, self.W("Wqkv").t(), out=ds1, beta=1.0)
@@ -864,6 +908,7 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         return y.reshape(B, T, -1).permute(0, 2, 1)
 
     def backpropGradient(self, eps, **kw):
+        c = self.conf
         idx, e, ln, B, T, dctx = self._c
         self._c = None
         dy = _token_major(eps).to(e.dtype)
@@ -882,7 +927,10 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
                 gw = NK.zero_(torch.empty_like(g["Wword"]))
                 nn_misc.embedding_backward_(gw, idx, de)
                 copy_grad_(g["Wword"], gw)
-            if nn_misc.bert_embed_backward_pt(de.contiguous(), g["Wpos"], g["Wtype"], B, T):
+            # without a position table the position sums go to a scratch: the kernel pair still gives Wtype's row
+            gpos = g["Wpos"] if c.positionEmbeddings else torch.empty(T, de.shape[1], dtype=torch.float32,
+                                                                      device=de.device)
+            if nn_misc.bert_embed_backward_pt(de.contiguous(), gpos, g["Wtype"], B, T):
                 return self.make_gradient(), None
         de = de.to(g["Wword"].dtype)
         if getattr(self.net, "_grads_zeroed", False) and g["Wword"].is_contiguous():
@@ -891,9 +939,10 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
             gw = torch.zeros_like(g["Wword"])
             gw.index_add_(0, idx.reshape(-1), de)
             copy_grad_(g["Wword"], gw)
-        copy_grad_(g["Wpos"][:T], de.reshape(B, T, -1).sum(0).to(g["Wpos"].dtype))
-        if g["Wpos"].shape[0] > T:
-            g["Wpos"][T:].zero_()
+        if c.positionEmbeddings:
+            copy_grad_(g["Wpos"][:T], de.reshape(B, T, -1).sum(0).to(g["Wpos"].dtype))
+            if g["Wpos"].shape[0] > T:
+                g["Wpos"][T:].zero_()
         gt = torch.zeros_like(g["Wtype"])
         gt[0] = de.sum(0)
         copy_grad_(g["Wtype"], gt)
@@ -901,13 +950,17 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
 
     def _embed(self, idx, pos, short=None):
         """[B*T, E] = Wword[idx] + Wpos[pos .. pos+T-1] + Wtype[0] in the compute dtype (in-tree kernel on a GPU);
-        with ``short`` (int32 [B]) row b takes the positions from pos - short[b]."""
+        with ``short`` (int32 [B]) row b takes the positions from pos - short[b]. Without position embeddings
+        (``positionEmbeddings(False)``) the Wpos addend is left out."""
         from ...ops import nn_misc
         B, T = idx.shape
-        e = nn_misc.bert_embed_forward(self.W("Wword"), self.W("Wpos"), self.W("Wtype"), idx, pos, short) \
+        Wp = self.W("Wpos") if self.conf.positionEmbeddings else None
+        e = nn_misc.bert_embed_forward(self.W("Wword"), Wp, self.W("Wtype"), idx, pos, short) \
             if idx.is_cuda else None
         if e is None:
-            if short is None:
+            if Wp is None:
+                wp = 0
+            elif short is None:
                 wp = self.W("Wpos")[pos:pos + T].repeat(B, 1)
             else:
                 rows = (pos - short.to(torch.int64)).reshape(B, 1) + torch.arange(T, device=short.device).reshape(1, T)
@@ -931,8 +984,8 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         return None if self._seen is None else (self._seen[0], self._seen[1], self._short)
 
     def rnnPinLimit(self):
-        """The largest capacity rnnPinState takes: the position table's rows."""
-        return int(self.W("Wpos").shape[0])
+        """The largest capacity rnnPinState takes: the position table's rows (None without one: no limit)."""
+        return int(self.W("Wpos").shape[0]) if self.conf.positionEmbeddings else None
 
     def rnnPinState(self, capacity, short, dryRun=False):
         """Pin the positions as KVCacheState.rnnPinState does: the count of tokens seen becomes ``capacity - 1`` for
@@ -940,7 +993,8 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         refused here, once, instead of at the step that would reach it."""
         if self._seen is None:
             return
-        _pin_check(self, capacity, self._seen[0], self._pinned, self.W("Wpos").shape[0])
+        _pin_check(self, capacity, self._seen[0], self._pinned,
+                   self.W("Wpos").shape[0] if self.conf.positionEmbeddings else None)
         if not dryRun:
             self._seen, self._short, self._pinned = (int(capacity) - 1, self._seen[1]), short, True
 
@@ -991,8 +1045,8 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
                 f"from the stored state's {mb}; call rnnClearPreviousState() before changing it")
         if self._pinned:
             _pinned_one_step(self, T)
-        maxp = self.W("Wpos").shape[0]
-        if pos + T > maxp:
+        maxp = self.W("Wpos").shape[0] if self.conf.positionEmbeddings else None
+        if maxp is not None and pos + T > maxp:
             raise DL4JInvalidInputException(
                 f"rnnTimeStep on layer {self.index} ({type(self.conf).__name__}): {pos} tokens seen + {T} new exceed "
                 f"maxPositions {maxp}; call rnnClearPreviousState() to start a new sequence")

@@ -478,7 +478,8 @@ class MultiLayerNetwork(BaseNetwork):
         """The format of the rnnTimeStep key/value caches from the next sequence on: None (the compute dtype) or
         "fp8", set on every layer that has ``cacheDataType`` — a trained or loaded model decodes with an fp8 cache
         without rebuilding its configuration. Refused, naming the layer and changing nothing, while a layer holds
-        state."""
+        state. A rotary layer (``positionEncoding="rotary"``) stores rotated keys in either format: its state is valid
+        only for a layer with the same ``ropeTheta``."""
         from .generation import set_cache_data_type
         set_cache_data_type([(f"layer {i}", l) for i, l in enumerate(self.layers)], value)
 

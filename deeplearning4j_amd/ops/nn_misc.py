@@ -178,10 +178,20 @@ def embedding_backward_(dW, idx, g):
 def bert_embed_forward(Ww, Wp, Wt, idx, pos=0, short=None):
     """[B*T, E] = Wword[idx] + Wpos[pos + t] + Wtype[0] for token ids ``idx`` [B, T] in one HIP pass (fp32 sum, one
     rounding); ``pos``: position of the first token (rnnTimeStep continues a sequence). ``short``: None, or int32 [B]
-    on the device (ragged batches): row b takes positions pos - short[b] + t, clamped into the table. None when the
-    kernel does not take these operands (the caller sums with torch)."""
+    on the device (ragged batches): row b takes positions pos - short[b] + t, clamped into the table. ``Wp`` None: no
+    position table, that addend is left out (``pos`` / ``short`` then do not matter). None when the kernel does not
+    take these operands (the caller sums with torch)."""
     B, T = idx.shape
     E = Ww.shape[1]
+    if Wp is None:
+        if not (use_native(Ww, "embedding") and _dt(Ww) is not None and Ww.dtype == Wt.dtype and
+                Ww.dim() == Wt.dim() == 2 and Ww.stride(1) == Wt.stride(1) == 1 and Wt.shape[1] == E):
+            return None
+        fi = idx.reshape(-1).to(torch.int64).contiguous()
+        out = torch.empty((B * T, E), dtype=Ww.dtype, device=Ww.device)
+        rc = _lib().dl4j_bert_embed_fwd_pos(_dt(Ww), _p(Ww), None, _p(Wt), _p(fi), _p(out), B * T, T, E, Ww.stride(0),
+                                            0, Ww.shape[0], 0, _s())
+        return out if rc == 0 else None
     if not (use_native(Ww, "embedding") and _dt(Ww) is not None and Ww.dtype == Wp.dtype == Wt.dtype and
             Ww.dim() == Wp.dim() == Wt.dim() == 2 and Ww.stride(1) == Wp.stride(1) == Wt.stride(1) == 1 and
             pos >= 0 and Wp.shape[0] >= pos + T and Wp.shape[1] == Wt.shape[1] == E):

@@ -23,9 +23,16 @@
             which bounds the gain. With --parent-lib also the parent commit's multi-head decode, forward and
             backward kernels against this tree's (twice per pass: the spread of the parent alone is the yardstick).
 
+  --rotary  rotary position embeddings (csrc/attention_rope.hip), 12 query heads of 64, bf16. (a) the fused
+            ``attn_rope_append`` of one new token against the plain ``attn_kv_append`` at the same shape (with
+            --parent-lib the parent commit's append: parent, ours, parent again in every pass, so the parent's own
+            spread stands next to the ratio), Hkv in {12, 4}, batch 1 and 32, both cache formats. (b) ``attn_rope``
+            alone at B = 32, T in {128, 512}: time and bytes per second (it reads and writes the Q and K columns once).
+
 Usage: python tools/bench_decode.py --kernel --model [--out profiles/decode_attention.txt]
        python tools/bench_decode.py --cache fp8 [--parent-lib PATH] [--out FILE]
-       python tools/bench_decode.py --kv-heads 4,1 [--parent-lib PATH] [--out FILE]"""
+       python tools/bench_decode.py --kv-heads 4,1 [--parent-lib PATH] [--out FILE]
+       python tools/bench_decode.py --rotary [--parent-lib PATH] [--out FILE]"""
 import argparse
 import sys
 import time
@@ -277,6 +284,60 @@ def gqa_mode(kv_heads, passes, reps, parent_lib):
     say()
 
 
+def rotary_mode(passes, reps, parent_lib):
+    import ctypes
+    from deeplearning4j_amd.ops import native
+    dev, dt = torch.device("cuda", 0), torch.bfloat16
+    H, D, theta = 12, 64, 10000.0
+    E = H * D
+    lib = ctypes.CDLL(parent_lib if parent_lib else native.KERNEL_LIB)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    who = "the parent commit's library" if parent_lib else "this tree (its append kernels are the parent's, unchanged)"
+    say(f"== attn_rope_append against attn_kv_append of {who}: H = {H} query heads of {D}, Tn = 1, bf16, pos = 1023 of "
+        f"1024 rows, GPU time per call in us (mean of {reps} back-to-back launches; median of {passes} passes, min .. "
+        "max); every pass runs plain, fused, plain: 'spread' = (max - min) / median over ALL plain timings, fused / "
+        "plain = ratio of the medians (above 1 = slower)")
+    for fp8 in (False, True):
+        for Hkv in (12, 4):
+            for B in (1, 32):
+                Ekv, pos, tcap = Hkv * D, 1023, 1024
+                g = torch.Generator().manual_seed(B + Hkv)
+                qkv = (torch.randn(B, 1, E + 2 * Ekv, generator=g) * 0.8).to(dt).to(dev)
+                width = TN.kv_fp8_row_bytes(Hkv, D) if fp8 else 2 * Ekv
+                kv = torch.zeros(B, tcap, width, dtype=torch.uint8 if fp8 else dt, device=dev)
+                f = lib.dl4j_attn_kv_append_fp8_gqa_dt if fp8 else lib.dl4j_attn_kv_append_gqa_dt
+                f.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+                st = lambda: vp(torch.cuda.current_stream().cuda_stream)                 # noqa: E731
+                plain = lambda: f(1, qkv.data_ptr(), kv.data_ptr(), B, 1, H, Hkv, D, pos, tcap, st())   # noqa: E731
+                fused = lambda: TN.attn_rope_append(qkv, kv, H, pos, theta, Hkv=Hkv)     # noqa: E731
+                assert plain() == 0 and fused() is kv
+                tp, tf = [], []
+                for _ in range(passes):
+                    tp.append(gpu_time(plain, reps=reps, warmup=3) * 1e3)
+                    tf.append(gpu_time(fused, reps=reps, warmup=3) * 1e3)
+                    tp.append(gpu_time(plain, reps=reps, warmup=3) * 1e3)
+                mp, lp, hp = _stats(tp)
+                mf, lf, hf = _stats(tf)
+                say(f"{'fp8   ' if fp8 else '16-bit'} Hkv={Hkv:2d} B={B:2d}: plain {mp:6.2f} ({lp:.2f} .. {hp:.2f}) us, "
+                    f"spread {(hp - lp) / mp * 100:4.1f} %  fused {mf:6.2f} ({lf:.2f} .. {hf:.2f}) us  fused / plain "
+                    f"{mf / mp:5.3f}x")
+    say()
+    say(f"== attn_rope alone (training and prompts): B = 32, H = {H}, D = {D}, bf16, in place; bytes = the Q and K "
+        "columns read once and written once")
+    for Hkv in (12, 4):
+        for T in (128, 512):
+            g = torch.Generator().manual_seed(T + Hkv)
+            qkv = (torch.randn(32, T, E + 2 * Hkv * D, generator=g) * 0.8).to(dt).to(dev)
+            assert TN.attn_rope(qkv, H, 0, theta, Hkv=Hkv) is qkv
+            t = [gpu_time(lambda: TN.attn_rope(qkv, H, 0, theta, Hkv=Hkv), reps=reps, warmup=3) * 1e3
+                 for _ in range(passes)]
+            m, lo, hi = _stats(t)
+            nbytes = 2.0 * 32 * T * (H + Hkv) * D * 2
+            say(f"Hkv={Hkv:2d} T={T:3d}: {m:7.2f} ({lo:.2f} .. {hi:.2f}) us  {nbytes / 1e6:6.1f} MB  "
+                f"{nbytes / m / 1e3:7.1f} GB/s")
+    say()
+
+
 def _sync_time(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -350,12 +411,14 @@ def main():
     ap.add_argument("--kv-heads", default=None,
                     help="grouped-query attention: key/value head counts (divisors of 12, comma separated) to compare "
                          "with the 12-head row")
+    ap.add_argument("--rotary", action="store_true",
+                    help="rotary embeddings: the fused rotate-and-append against the plain append, and attn_rope alone")
     ap.add_argument("--parent-lib", default=None,
-                    help="--cache / --kv-heads: kernel library built from the parent commit")
+                    help="--cache / --kv-heads / --rotary: kernel library built from the parent commit")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args()
-    if not (a.kernel or a.model or a.cache or a.kv_heads):
-        ap.error("give --kernel, --model, --cache fp8 and / or --kv-heads N")
+    if not (a.kernel or a.model or a.cache or a.kv_heads or a.rotary):
+        ap.error("give --kernel, --model, --cache fp8, --kv-heads N and / or --rotary")
     kv_heads = [int(h) for h in a.kv_heads.split(",")] if a.kv_heads else []
     if any(h < 1 or 12 % h for h in kv_heads):
         ap.error("--kv-heads: every count must divide the 12 query heads")
@@ -373,6 +436,8 @@ def main():
         cache_fp8_mode(max(a.passes, 5), a.reps, a.parent_lib)
     if kv_heads:
         gqa_mode(kv_heads, max(a.passes, 5), a.reps, a.parent_lib)
+    if a.rotary:
+        rotary_mode(max(a.passes, 5), a.reps, a.parent_lib)
     if _out is not None:
         _out.close()
 

@@ -34,18 +34,28 @@
              model built with nKVHeads = N against the 12-head model (one network per count), prefix 1024, the
              variants alternating within every pass; also the cache bytes per cached token and layer.
 
+  --rotary   rotary position embeddings: generate() and generate(useGraph=True) of the 12-layer, hidden-768 model
+             built with positionEncoding="rotary" against the same model with learned positions (one network each),
+             prefix 128 and 1024, the variants alternating within every pass; then one causal-LM training step
+             (batch 32, 128 tokens) of both. ``--positions learned`` measures the learned-position model alone and
+             ``--tree PATH`` imports the package from another checkout (the parent commit's, with its own kernel
+             library), so the same rows can be taken from both trees in alternating processes.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
        python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]
        python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]
-       python tools/bench_generate.py --kv-heads 4 [--batch 32] [--out FILE]"""
+       python tools/bench_generate.py --kv-heads 4 [--batch 32] [--out FILE]
+       python tools/bench_generate.py --rotary [--positions learned] [--tree PATH] [--out FILE]"""
 import argparse
 import sys
 import time
 
 import torch
 
-sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+# --tree PATH: the checkout the package is imported from (default: this one)
+sys.path.insert(0, sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv[:-1]
+                else __file__.rsplit("/tools/", 1)[0])
 from deeplearning4j_amd.ops import generation_native as GN  # noqa: E402
 from deeplearning4j_amd.ops.nn_misc import PhiloxStream  # noqa: E402
 from deeplearning4j_amd.ops.timing import gpu_time  # noqa: E402
@@ -511,6 +521,78 @@ def kv_heads_mode(kv_heads, batches, n, passes):
     say()
 
 
+def rotary_mode(batches, n, passes, positions):
+    """generate() / generate(useGraph=True) and a training step of the 12-layer, hidden-768 model with rotary
+    embeddings against learned positions: one network each, the variants alternating."""
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, MAXP, H, E = 77, 2048, 12, 768
+    kinds = ["learned", "rotary"] if positions == "both" else [positions]
+    nets = {k: TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=E, layers=12, heads=H, maxPositions=MAXP,
+                                         dataType=DataType.BFLOAT16,
+                                         **(dict(positionEncoding="rotary") if k == "rotary" else {})).init(device=DEV)
+            for k in kinds}
+    say(f"== generate() with rotary embeddings against learned positions on TextGenerationTransformer(768, 12 layers, "
+        f"12 heads, maxPositions {MAXP}), bf16, V = {V}, greedy, {n} new tokens; whole calls (prompt included) on the "
+        f"host clock, ended by a device synchronise; median of {passes} passes (min .. max), the variants alternating "
+        "within a pass; x = tokens/s against the learned-position model's same mode")
+    say("   parameters: " + ", ".join(f"{k} {nets[k].numParams()}" for k in kinds))
+    for mb in batches:
+        for P in (128, 1024):
+            prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb + P)).to(DEV)
+            variants = [(f"{k:7s} {mode}", nets[k], kw)
+                        for mode, kw in (("eager", {}), ("graph", dict(useGraph=True))) for k in kinds]
+
+            def call(net, kw, tokens=n):
+                net.rnnClearPreviousState()
+                return net.generate(prompt, maxNewTokens=tokens, **kw)
+
+            for _, net, kw in variants:
+                call(net, kw)
+            times = [[] for _ in variants]
+            for _ in range(passes):
+                for i, (_, net, kw) in enumerate(variants):
+                    times[i].append(_sync_time(lambda: call(net, kw)))
+            med = [sorted(t)[len(t) // 2] for t in times]
+            few = max(2, n // 4)
+            short = []
+            for _, net, kw in variants:
+                call(net, kw, few)
+                short.append(sorted(_sync_time(lambda: call(net, kw, few)) for _ in range(passes))[passes // 2])
+            per = [(m - ts) / (n - few) * 1e3 for ts, m in zip(short, med)]
+            for i, ((vn, _, _), t, m) in enumerate(zip(variants, times, med)):
+                b = (i // len(kinds)) * len(kinds)               # the learned-position row of the same mode
+                say(f"batch {mb:2d} prefix {P:4d} {vn}: {mb * n / m:9.1f} tok/s  {m * 1e3:8.1f} ms per call "
+                    f"({min(t) * 1e3:.1f} .. {max(t) * 1e3:.1f})  x {med[b] / m:5.3f} | step alone {per[i]:6.2f} ms  x "
+                    f"{per[b] / per[i]:5.3f}")
+    for net in nets.values():
+        net.rnnClearPreviousState()
+    say()
+    B, T, steps = 32, 128, 10
+    say(f"== one causal-LM training step (fit) of the same models, batch {B}, {T} tokens, bf16: ms per step on the host "
+        f"clock over {steps} steps ended by a device synchronise; median of {passes} passes (min .. max), alternating")
+    g = torch.Generator().manual_seed(1)
+    x = torch.randint(0, V, (B, T), generator=g).to(DEV)
+    y = torch.zeros(B, V, T, device=DEV)
+    y.scatter_(1, torch.randint(0, V, (B, 1, T), generator=g).to(DEV), 1.0)
+
+    def train(net):
+        for _ in range(steps):
+            net.fit([x], [y])
+
+    for k in kinds:
+        train(nets[k])
+    tt = {k: [] for k in kinds}
+    for _ in range(passes):
+        for k in kinds:
+            tt[k].append(_sync_time(lambda: train(nets[k])) / steps * 1e3)
+    base = sorted(tt[kinds[0]])[passes // 2]
+    for k in kinds:
+        t = sorted(tt[k])
+        say(f"{k:7s}: {t[len(t) // 2]:7.2f} ms per step ({t[0]:.2f} .. {t[-1]:.2f})  x {base / t[len(t) // 2]:5.3f}")
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -523,6 +605,11 @@ def main():
                     help="compare generate() with the fp8 key/value cache and with the 16-bit one")
     ap.add_argument("--kv-heads", default=None,
                     help="grouped-query attention: nKVHeads values (divisors of 12, comma separated) against 12")
+    ap.add_argument("--rotary", action="store_true",
+                    help="rotary embeddings against learned positions: generate(), generate(useGraph=True), training")
+    ap.add_argument("--positions", choices=["both", "learned", "rotary"], default="both",
+                    help="--rotary: the models to measure")
+    ap.add_argument("--tree", default=None, help="import the package from this checkout instead of the tool's own")
     ap.add_argument("--parent-lib", default=None,
                     help="kernel library built from the parent commit (--ragged, --graph)")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 32])
@@ -549,6 +636,8 @@ def main():
         cache_fp8_mode(a.batch, a.tokens, a.passes)
     if a.kv_heads:
         kv_heads_mode([int(h) for h in a.kv_heads.split(",")], a.batch, a.tokens, a.passes)
+    if a.rotary:
+        rotary_mode(a.batch, a.tokens, a.passes, a.positions)
 
 
 if __name__ == "__main__":
