@@ -952,6 +952,8 @@ class TextGenerationTransformer(ZooModel):
     """Causal transformer language model, the counterpart of ``TextGenerationLSTM`` (new relative to the reference
     zoo): BertEmbeddingLayer -> N causal TransformerEncoderLayer -> RnnOutputLayer (softmax, MCXENT). Input = token
     ids [mb, T]; output = next-token distribution [mb, numLabels, T]. ``numLabels`` is the vocabulary size.
+    ``normalization="rms", normPlacement="pre", ffnActivation="swiglu"`` make every block Llama-style (pre-norm
+    RMSNorm, gated feed-forward) and add an ``RMSNormalization`` layer ``final_norm`` before the output layer.
 
     Generation: ``TextGenerationTransformer.generate(net, prompt, maxNewTokens=..., ...)`` (``net.generate``): greedy,
     temperature / top-k / top-p sampling or beam search, with the token choice, the beam selection and the cache
@@ -970,7 +972,7 @@ class TextGenerationTransformer(ZooModel):
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
                  maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, positionEncoding=None,
-                 ropeTheta=10000.0, **kw):
+                 ropeTheta=10000.0, normalization="layer", normPlacement="post", ffnActivation="gelu", **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
@@ -980,9 +982,12 @@ class TextGenerationTransformer(ZooModel):
         # None: learned positions in the embedding (at most maxPositions tokens); "rotary": every block rotates its
         # Q / K heads with base ropeTheta, the embedding has no position table and maxPositions is unused
         self.positionEncoding, self.ropeTheta = positionEncoding, ropeTheta
+        # the block style of every block: ("layer", "post", "gelu") is BERT's, ("rms", "pre", "swiglu") the Llama
+        # family's; with "pre" an RMSNormalization layer ``final_norm`` stands before the output layer
+        self.normalization, self.normPlacement, self.ffnActivation = normalization, normPlacement, ffnActivation
 
     def graphBuilder(self):
-        from ..nn.conf import BertEmbeddingLayer, TransformerEncoderLayer
+        from ..nn.conf import BertEmbeddingLayer, RMSNormalization, TransformerEncoderLayer
         g = (self._builder().updater(Adam(self.learningRate)).weightInit(NormalDistribution(0.0, 0.02))
              .graphBuilder())
         g.addInputs("tokens")
@@ -994,8 +999,12 @@ class TextGenerationTransformer(ZooModel):
             g.addLayer(f"decoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
                        .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
                        .nKVHeads(self.nKVHeads).positionEncoding(self.positionEncoding)
-                       .ropeTheta(self.ropeTheta).build(), prev)
+                       .ropeTheta(self.ropeTheta).normalization(self.normalization)
+                       .normPlacement(self.normPlacement).ffnActivation(self.ffnActivation).build(), prev)
             prev = f"decoder_{i}"
+        if self.normPlacement == "pre":
+            g.addLayer("final_norm", RMSNormalization.Builder().nIn(self.hidden).nOut(self.hidden).build(), prev)
+            prev = "final_norm"
         g.addLayer("output", RnnOutputLayer.Builder(LossFunction.MCXENT).activation(Activation.SOFTMAX)
                    .nIn(self.hidden).nOut(self.numLabels).build(), prev)
         g.setOutputs("output")

@@ -837,6 +837,32 @@ class LayerNormalization(FeedForwardLayer):
         return key == "beta"
 
 
+class RMSNormalization(FeedForwardLayer):
+    """RMSNorm over the feature dim: y = x * rsqrt(mean(x^2) + eps) * gamma, no mean and no beta (csrc/rmsnorm.hip).
+    Takes feed-forward [mb, n] and recurrent [mb, n, T] input; the final norm of a stack of pre-norm transformer
+    blocks (``TransformerEncoderLayer.normPlacement("pre")``). Stateless: rnnTimeStep passes through it."""
+    FIELDS = {"eps": 1e-6}
+    RUNTIME = "deeplearning4j_amd.nn.layers.normalization:RMSNormalizationImpl"
+
+    def getOutputType(self, layerIndex, inputType):
+        return inputType
+
+    def setNIn(self, inputType, override=False):
+        if self.nIn and not override:
+            return
+        self.nIn = inputType.size
+        self.nOut = self.nIn
+
+    def getPreProcessorForInputType(self, inputType):
+        return None
+
+    def param_specs(self):
+        return [ParamSpec("gamma", [1, self.nIn], "c", "const", value=1.0)]
+
+    def is_bias(self, key):
+        return False
+
+
 class ActivationLayer(NoParamLayer):
     FIELDS = {"activation": None}
     _CONVERTERS = dict(NoParamLayer._CONVERTERS, activation=to_activation)
@@ -1435,6 +1461,27 @@ def _check_position_encoding(layer, headSize=None):
             f"{headSize}")
 
 
+NORMALIZATIONS = ("layer", "rms")
+NORM_PLACEMENTS = ("post", "pre")
+FFN_ACTIVATIONS = ("gelu", "swiglu")
+
+
+def _check_block_style(layer):
+    """``normalization`` "layer" | "rms", ``normPlacement`` "post" | "pre", ``ffnActivation`` "gelu" | "swiglu". The
+    normalisation comes in two styles: ("layer", "post"), BERT's block, and ("rms", "pre"), the Llama family's; the
+    feed-forward activation is independent of them."""
+    for name, allowed in (("normalization", NORMALIZATIONS), ("normPlacement", NORM_PLACEMENTS),
+                          ("ffnActivation", FFN_ACTIVATIONS)):
+        v = getattr(layer, name)
+        if v not in allowed:
+            raise DL4JInvalidConfigException(
+                f"{_who(layer)}: {name} is " + " or ".join(f'"{a}"' for a in allowed) + f", got {v!r}")
+    if (layer.normalization, layer.normPlacement) not in (("layer", "post"), ("rms", "pre")):
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: normalization \"{layer.normalization}\" with normPlacement \"{layer.normPlacement}\" is "
+            "not supported; the block is (\"layer\", \"post\") or (\"rms\", \"pre\")")
+
+
 def _check_drop_prob(layer, name):
     """``name`` is a DROP probability in [0, 1) (HuggingFace's convention; 0.0 = off) — the opposite of the
     retain-probability ``dropOut`` of the reference's layers."""
@@ -1535,11 +1582,21 @@ class TransformerEncoderLayer(FeedForwardLayer):
 
     ``positionEncoding``: None (the default) or "rotary": rotary position embeddings (RoPE) on the Q and K columns of
     the fused projection, with base ``ropeTheta`` (default 10000). A token's position is its index in the sequence,
-    in ``rnnTimeStep`` the index of its cache row; the cache then holds rotated keys. The head size must be even."""
+    in ``rnnTimeStep`` the index of its cache row; the cache then holds rotated keys. The head size must be even.
+
+    ``normalization`` / ``normPlacement``: ("layer", "post"), the default, is the block above; ("rms", "pre") is the
+    Llama family's: ``h = x + Attn(RMSNorm(x))``, ``y = h + FFN(RMSNorm(h))`` (csrc/rmsnorm.hip; the add of the first
+    residual runs inside the second norm's launch). ``layerNormEps`` is then the RMS epsilon, there are no ``ln1b`` /
+    ``ln2b`` parameters, hidden dropout acts on the two branch outputs, and a stack ends in an ``RMSNormalization``
+    layer. The other two combinations are refused.
+
+    ``ffnActivation``: "gelu" (the default) or "swiglu": the gated feed-forward ``W2(silu(x Wg) * (x Wu))``
+    (csrc/swiglu.hip) with ``W1 = [Wg | Wu]`` of shape [nIn, 2*ffnSize]; it works in either block."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
               "attentionDropout": 0.0, "cacheDataType": None, "nKVHeads": None, "positionEncoding": None,
-              "ropeTheta": 10000.0}
-    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta")
+              "ropeTheta": 10000.0, "normalization": "layer", "normPlacement": "post", "ffnActivation": "gelu"}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta", "normalization",
+                        "normPlacement", "ffnActivation")
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
 
     def _post_init(self):
@@ -1549,6 +1606,13 @@ class TransformerEncoderLayer(FeedForwardLayer):
         _check_cache_dtype(self)
         _check_kv_heads(self)
         self._check_rope()
+        _check_block_style(self)
+
+    def preNorm(self):
+        return self.normPlacement == "pre"
+
+    def swiglu(self):
+        return self.ffnActivation == "swiglu"
 
     def _check_rope(self):
         _check_position_encoding(self, self.nIn // self.nHeads if self.nIn else 0)
@@ -1576,12 +1640,16 @@ class TransformerEncoderLayer(FeedForwardLayer):
     def param_specs(self):
         E, F = self.nIn, self.ffnSize
         Q = E + 2 * (E // self.nHeads) * self.kvHeads()          # E + 2*Ekv columns of the fused projection
-        return [ParamSpec("Wqkv", [E, Q], "c", "weight", E, E), ParamSpec("bqkv", [1, Q], "c", "bias"),
-                ParamSpec("Wo", [E, E], "c", "weight", E, E), ParamSpec("bo", [1, E], "c", "bias"),
-                ParamSpec("ln1g", [1, E], "c", "const", value=1.0), ParamSpec("ln1b", [1, E], "c", "const", value=0.0),
-                ParamSpec("W1", [E, F], "c", "weight", E, F), ParamSpec("b1", [1, F], "c", "bias"),
-                ParamSpec("W2", [F, E], "c", "weight", F, E), ParamSpec("b2", [1, E], "c", "bias"),
-                ParamSpec("ln2g", [1, E], "c", "const", value=1.0), ParamSpec("ln2b", [1, E], "c", "const", value=0.0)]
+        F1 = 2 * F if self.swiglu() else F                       # swiglu: W1 = [gate | up]
+        specs = [ParamSpec("Wqkv", [E, Q], "c", "weight", E, E), ParamSpec("bqkv", [1, Q], "c", "bias"),
+                 ParamSpec("Wo", [E, E], "c", "weight", E, E), ParamSpec("bo", [1, E], "c", "bias"),
+                 ParamSpec("ln1g", [1, E], "c", "const", value=1.0), ParamSpec("ln1b", [1, E], "c", "const", value=0.0),
+                 ParamSpec("W1", [E, F1], "c", "weight", E, F), ParamSpec("b1", [1, F1], "c", "bias"),
+                 ParamSpec("W2", [F, E], "c", "weight", F, E), ParamSpec("b2", [1, E], "c", "bias"),
+                 ParamSpec("ln2g", [1, E], "c", "const", value=1.0), ParamSpec("ln2b", [1, E], "c", "const", value=0.0)]
+        if self.normalization == "rms":                          # no mean, no beta
+            specs = [p for p in specs if p.key not in ("ln1b", "ln2b")]
+        return specs
 
     def is_bias(self, key):
         return key.startswith("b") or key in ("ln1b", "ln2b")

@@ -156,3 +156,56 @@ class LayerNormalizationImpl(LayerImpl):
         copy_grad_(self.grads["gamma"], dg)
         copy_grad_(self.grads["beta"], db)
         return self.make_gradient(), dx
+
+
+def _dense_copy(v):
+    """Contiguous copy of the strided view ``v``: the in-tree strided-copy kernel on a GPU, torch elsewhere."""
+    if v.is_cuda:
+        from ...ops import nd4j_kernels
+        r = nd4j_kernels.materialize(v)
+        if r is not None:
+            return r
+    return v.contiguous()
+
+
+class RMSNormalizationImpl(LayerImpl):
+    """y = x * rsqrt(mean(x^2) + eps) * gamma over the feature dim of [mb, n] or [mb, n, T] input (conf:
+    RMSNormalization): csrc/rmsnorm.hip in bf16 / fp16 on a GPU, the torch reference elsewhere. Like the transformer
+    blocks it applies no activation function and, being stateless, it takes rnnTimeStep chunks through ``activate``.
+
+    A recurrent input is normalised as time-major rows (row t*mb + b), the memory order of the recurrent and output
+    layers, so the output layer that follows the final norm of a transformer stack reads it in place. The transformer
+    blocks hand over token-major memory: that input is reordered once, by the in-tree strided-copy kernel, and the
+    gradient goes back token-major the same way; a time-major input (or one time step) is used as it is."""
+
+    def _rows(self, x):
+        """[mb, n] or [mb, n, T] -> contiguous [rows, n] in the compute dtype, a recurrent input time-major."""
+        if x.dim() == 3:
+            x = x.permute(2, 0, 1)
+        x = x.to(self.compute_dtype)
+        return (x if x.is_contiguous() else _dense_copy(x)).reshape(-1, x.shape[-1])
+
+    def activate(self, x, training=False, mask=None):
+        from .transformer import _rms_fwd
+        self.input = x
+        xr = self._rows(x)
+        y, _, rstd = _rms_fwd(xr, None, self.params["gamma"], self.conf.eps)
+        # whether the gradient goes back token-major: the input was [mb, T, n] memory and had to be reordered
+        back = x.dim() == 3 and not x.permute(2, 0, 1).is_contiguous() and x.permute(0, 2, 1).is_contiguous()
+        self._ctx = (xr, rstd, back) if training else None
+        if x.dim() == 3:
+            return y.reshape(x.shape[2], x.shape[0], x.shape[1]).permute(1, 2, 0)
+        return y.reshape(x.shape)
+
+    def backpropGradient(self, eps):
+        from .transformer import _rms_bwd
+        xr, rstd, back = self._ctx
+        self._ctx = None
+        dx = _rms_bwd(self._rows(eps), xr, self.params["gamma"], rstd, self.grads["gamma"])
+        if eps.dim() == 3:
+            mb, n, T = eps.shape
+            dx = dx.reshape(T, mb, n)
+            dx = _dense_copy(dx.permute(1, 0, 2)).permute(0, 2, 1) if back else dx.permute(1, 2, 0)
+        else:
+            dx = dx.reshape(eps.shape)
+        return self.make_gradient(), dx

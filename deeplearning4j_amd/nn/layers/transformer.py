@@ -39,6 +39,13 @@ gradients. In ``rnnTimeStep`` a token's position is the index of its cache row a
 stores, so the cache holds rotated keys and a step gains no launch. ``BertEmbeddingLayer.positionEmbeddings(False)``
 drops the learned position table (and with it the limit on a generated sequence's length).
 
+Llama-style block (``normalization="rms"``, ``normPlacement="pre"`` on the encoder block; ``ffnActivation="swiglu"`` in
+either block): n1 = rms(x), a = Attn(n1)·Wo + bo, (h, n2) = rms(a, r = x) in ONE launch that overwrites a with
+h = x + a (csrc/rmsnorm.hip), f = swiglu(n2·W1 + b1) (csrc/swiglu.hip; or the GELU epilogue), y = h + f·W2 + b2 (the
+add rides on the GEMM in ``rnnTimeStep`` and is one pairwise launch in ``activate``). Backward mirrors it: the norm's
+backward kernel takes the gradient arriving over the residual path as ``dres`` and adds it before the one rounding.
+Hidden dropout uses the stand-alone Philox launches on the two branch outputs.
+
 Decoder block (``TransformerDecoderLayerImpl``, a two-input graph layer: decoder stream + encoder memory): causal
 self-attention as above, then cross-attention of q2 = h1·Wq2 over kv2 = memory·Wkv2 (one GEMM straight into the
 kv [mb, Tk, 2E] layout of csrc/attention_cross.hip), then the FFN, each followed by LayerNorm(+residual). Its
@@ -51,7 +58,7 @@ import torch.nn.functional as F
 
 from ... import ops
 from .base import LayerImpl, copy_grad_, matmul, weight_grad_
-from ...ops.gemm import mmul
+from ...ops.gemm import bias_vec, mmul
 
 
 def _native(x, op):
@@ -141,6 +148,79 @@ def _ln_bwd(dy, x, res, g, ctx, gview=None, bview=None, dsum_view=None):
     if dsum_view is not None:
         _bsum(dsum_view, ds)
     return ds
+
+
+# ------------------------------------------------------------------------------------------------ RMSNorm / SwiGLU
+def _rms_fwd(x, res, g, eps, s_out=None):
+    """RMSNorm of s = x (+ res) -> (y, s, rstd): csrc/rmsnorm.hip on a GPU in bf16 / fp16 (with ``res`` the add runs in
+    the same launch and s is written to ``s_out``, which may be x itself), else ``rms_norm_reference``, counted as a
+    fallback on a GPU."""
+    from ...ops import transformer_native as TN
+    if _native(x, "rmsnorm"):
+        r = TN.rms_fwd(x, g, eps, res, s_out)
+        if r is not None:
+            return r
+    if x.is_cuda:
+        from ...ops import fallback
+        fallback.record("rmsnorm", f"width {x.shape[-1]} / dtype {x.dtype}: torch reference path")
+    return TN.rms_norm_reference(x, g, eps, res)
+
+
+def _rms_bwd(dy, s, g, rstd, gview, dres=None, dsum_view=None, dx_out=None):
+    """-> ds = the gradient of s (+ ``dres``, the gradient arriving over the residual path, added before the one
+    rounding; ``dx_out`` may be ``dres``); dgamma lands in ``gview``. ``dsum_view``: the producing dense layer's
+    bias-gradient view, filled with the column sums of ds by the backward kernel itself when it can, else by _bsum."""
+    from ...ops import transformer_native as TN
+    if _native(s, "rmsnorm") and rstd.dim() == 1:
+        f32v = lambda v: v is not None and v.is_contiguous() and v.dtype == torch.float32  # noqa: E731
+        dsv = dsum_view.view(-1) if f32v(dsum_view) else None
+        r = TN.rms_bwd(dy.to(s.dtype).contiguous(), s, g, rstd, dres, gview.view(-1) if f32v(gview) else None, dsv,
+                       dx_out)
+        if r is not None:
+            ds, dg = r
+            if dg.data_ptr() != gview.data_ptr():
+                copy_grad_(gview, dg)
+            if dsum_view is not None and dsv is None:
+                _bsum(dsum_view, ds)
+            return ds
+    ds, dg = TN.rms_norm_backward_reference(dy, s, g, rstd.reshape(-1, 1) if rstd.dim() == 1 else rstd, dres)
+    copy_grad_(gview, dg)
+    if dsum_view is not None:
+        _bsum(dsum_view, ds)
+    return ds
+
+
+def _swiglu_fwd(z):
+    """silu(gate) * up of the fused projection z [M, 2F] (csrc/swiglu.hip; ``swiglu_reference`` off the kernels,
+    counted as a fallback on a GPU)."""
+    from ...ops import transformer_native as TN
+    if _native(z, "swiglu"):
+        r = TN.swiglu(z)
+        if r is not None:
+            return r
+    if z.is_cuda:
+        from ...ops import fallback
+        fallback.record("swiglu", f"width {z.shape[-1]} / dtype {z.dtype}: torch reference path")
+    return TN.swiglu_reference(z)
+
+
+def _swiglu_bwd(z, df):
+    from ...ops import transformer_native as TN
+    if _native(z, "swiglu"):
+        r = TN.swiglu_bwd(z, df.to(z.dtype).contiguous())
+        if r is not None:
+            return r
+    return TN.swiglu_backward_reference(z, df)
+
+
+def _add_into(a, b):
+    """a + b written over b (the last residual add of a pre-norm block): the in-tree pairwise kernel on a GPU."""
+    if a.is_cuda and ops.use_native(a, "rmsnorm"):
+        from ...ops import nd4j_kernels
+        if a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous() and \
+                nd4j_kernels.binary(a, b, "add", out=b) is not None:
+            return b
+    return b.add_(a)
 
 
 # ------------------------------------------------------------------------------------------------ dropout
@@ -546,6 +626,8 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
 
     def activate(self, x, training=False, mask=None, **kw):
         c = self.conf
+        if c.preNorm():
+            return self._activate_pre(x, training, mask)
         self.training = training
         B, E, T = x.shape
         H = c.nHeads
@@ -562,15 +644,69 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, ln1, a, d1 = _ln_fwd_drop(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps, ph, self,
                                       "hidden1")
-        # FFN-1 with bias + exact GELU fused into the GEMM epilogue; the pre-activation z1 is kept for backward
-        z1 = torch.empty(h1.shape[0], self.W("W1").shape[1], dtype=h1.dtype, device=h1.device)
-        f = matmul(h1, self.W("W1"), bias=self.Wbias("b1"), act="gelu", z=z1)
+        f, z1 = self._ffn1(h1, True)
         f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
         y, ln2, f2, d2 = _ln_fwd_drop(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps, ph, self,
                                       "hidden2")
         self.maskArray = mask
         if training:
             self._c = (xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m, d1, d2)
+        self.input = x
+        return y.reshape(B, T, E).permute(0, 2, 1)
+
+    def _ffn1(self, h, keep):
+        """The first feed-forward projection and its activation -> (f, z1): GELU in the GEMM epilogue (z1, the
+        pre-activation, kept for backward when ``keep``), or the fused gate | up projection z1 and ``swiglu``."""
+        if self.conf.swiglu():
+            z1 = matmul(h, self.W("W1"), bias=self.Wbias("b1"))
+            return _swiglu_fwd(z1), z1
+        if not keep:
+            return matmul(h, self.W("W1"), bias=self.Wbias("b1"), act="gelu"), None
+        # FFN-1 with bias + exact GELU fused into the GEMM epilogue; the pre-activation z1 is kept for backward
+        z1 = torch.empty(h.shape[0], self.W("W1").shape[1], dtype=h.dtype, device=h.device)
+        return matmul(h, self.W("W1"), bias=self.Wbias("b1"), act="gelu", z=z1), z1
+
+    def _ffn1_bwd(self, df2, z1):
+        """dz1, the gradient of the first projection's output, from df2, the gradient of the second's."""
+        if self.conf.swiglu():
+            return _swiglu_bwd(z1, matmul(df2, self.W("W2").t()))
+        if _native(df2, "gemm") and z1.dtype == df2.dtype:
+            # GELU backward in the GEMM epilogue: dz1 = (df2 · W2ᵀ) * gelu'(z1)
+            return mmul(df2, self.W("W2").t(), act="dgelu", z=z1)
+        return _gelu_bwd(z1, matmul(df2, self.W("W2").t()))
+
+    def _activate_pre(self, x, training, mask):
+        """The pre-norm block: h = x + drop(Attn(RMSNorm(x))), y = h + drop(FFN(RMSNorm(h))). The first residual add
+        runs inside the second norm's launch (h overwrites the attention branch's output); the second is one launch
+        of the pairwise kernel over the feed-forward branch's output."""
+        c = self.conf
+        self.training = training
+        B, E, T = x.shape
+        H = c.nHeads
+        P = self.params
+        xt = _token_major(x).to(self.W("Wqkv").dtype).contiguous()
+        m = mask.reshape(B, T) if mask is not None else None
+        pa, ph = (float(c.attentionDropout), float(c.hiddenDropout)) if training else (0.0, 0.0)
+        if pa > 0.0 or ph > 0.0:
+            self.dropoutBegin(x.device)
+        n1, _, r1 = _rms_fwd(xt, None, P["ln1g"], c.layerNormEps)
+        qkv = matmul(n1, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        if c.rotary():
+            qkv = _rope(qkv, B, T, H, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer")
+        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads())
+        a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
+        d1 = d2 = None
+        if ph > 0.0:
+            a, d1 = _drop_fwd(a, ph, self, "hidden1")
+        n2, h, r2 = _rms_fwd(a, xt, P["ln2g"], c.layerNormEps, s_out=a)
+        f, z1 = self._ffn1(n2, True)
+        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        if ph > 0.0:
+            f2, d2 = _drop_fwd(f2, ph, self, "hidden2")
+        y = _add_into(h, f2)
+        self.maskArray = mask
+        if training:
+            self._c = (xt, n1, r1, qkv, actx, ctx, h, n2, r2, z1, f, B, T, m, d1, d2)
         self.input = x
         return y.reshape(B, T, E).permute(0, 2, 1)
 
@@ -588,19 +724,34 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         self._check_state_mb(x)
         B, E, T = x.shape
         xt = _token_major(x).to(self.W("Wqkv").dtype)
-        qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        if c.preNorm():
+            xt = xt.contiguous()
+            n1, _, _ = _rms_fwd(xt, None, self.params["ln1g"], c.layerNormEps)
+            qkv = matmul(n1, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+        else:
+            qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
         ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads, Hkv=c.kvHeads(),
                                    ropeTheta=c.ropeTheta if c.rotary() else None).reshape(B * T, -1)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
-        h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
-        f = matmul(h1, self.W("W1"), bias=self.Wbias("b1"), act="gelu")
-        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
-        y, _ = _ln_fwd(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps)
+        if c.preNorm():
+            n2, h, _ = _rms_fwd(a, xt, self.params["ln2g"], c.layerNormEps, s_out=a)
+            f, _ = self._ffn1(n2, False)
+            if _native(f, "gemm"):
+                y = mmul(f, self.W("W2"), out=h, bias=bias_vec(self.Wbias("b2")), beta=1.0)   # y = h + f·W2 + b2
+            else:
+                y = _add_into(h, matmul(f, self.W("W2"), bias=self.Wbias("b2")))
+        else:
+            h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
+            f, _ = self._ffn1(h1, False)
+            f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+            y, _ = _ln_fwd(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps)
         y = y.reshape(B, T, E).permute(0, 2, 1)
         return y[:, :, 0] if one else y
 
     def backpropGradient(self, eps, **kw):
         c = self.conf
+        if c.preNorm():
+            return self._backprop_pre(eps)
         xt, qkv, actx, ctx, a, ln1, h1, z1, f, f2, ln2, B, T, m, d1, d2 = self._c
         self._c = None
         g = self.grads
@@ -616,11 +767,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
             df2 = _drop_bwd(ds2, d2)
             _bsum(g["b2"], df2)
         _wgrad(g["W2"], f, df2)
-        if _native(df2, "gemm") and z1.dtype == df2.dtype:
-            # GELU backward in the GEMM epilogue: dz1 = (df2 · W2ᵀ) * gelu'(z1)
-            dz1 = mmul(df2, self.W("W2").t(), act="dgelu", z=z1)
-        else:
-            dz1 = _gelu_bwd(z1, matmul(df2, self.W("W2").t()))
+        dz1 = self._ffn1_bwd(df2, z1)
         _wgrad(g["W1"], h1, dz1)
         _bsum(g["b1"], dz1)
         dh1 = mmul(dz1, self.W("W1").t(), out=ds2, beta=1.0)          # residual gradient summed in place
@@ -638,6 +785,43 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         _wgrad(g["Wqkv"], xt, dqkv)
         _bsum(g["bqkv"], dqkv)
         dx = mmul(dqkv, self.W("Wqkv").t(), out=ds1, beta=1.0)
+        E = dx.shape[1]
+        return self.make_gradient(), dx.reshape(B, T, E).permute(0, 2, 1)
+
+    def _backprop_pre(self, eps):
+        """The backward of ``_activate_pre``: dy flows to the feed-forward branch and, as ``dres`` of the second
+        norm's backward, over the residual; dh likewise to the attention branch and into the first norm's backward,
+        which adds it in place."""
+        c = self.conf
+        xt, n1, r1, qkv, actx, ctx, h, n2, r2, z1, f, B, T, m, d1, d2 = self._c
+        self._c = None
+        g = self.grads
+        P = self.params
+        dy = _token_major(eps).to(xt.dtype).contiguous()
+        df2 = dy if d2 is None else _drop_bwd(dy, d2)
+        _bsum(g["b2"], df2)
+        _wgrad(g["W2"], f, df2)
+        dz1 = self._ffn1_bwd(df2, z1)
+        _wgrad(g["W1"], n2, dz1)
+        _bsum(g["b1"], dz1)
+        dn2 = matmul(dz1, self.W("W1").t())
+        # dh: the gradient of h = x + a. Without hidden dropout it is also the attention branch's (da) and its column
+        # sums (bo's gradient) come out of the norm's backward launch
+        if d1 is None:
+            dh = da = _rms_bwd(dn2, h, P["ln2g"], r2, g["ln2g"], dres=dy, dsum_view=g["bo"])
+        else:
+            dh = _rms_bwd(dn2, h, P["ln2g"], r2, g["ln2g"], dres=dy)
+            da = _drop_bwd(dh, d1)
+            _bsum(g["bo"], da)
+        _wgrad(g["Wo"], ctx, da)
+        dctx = matmul(da, self.W("Wo").t())
+        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads())
+        if c.rotary():
+            dqkv = _rope(dqkv, B, T, c.nHeads, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer", inverse=True)
+        _wgrad(g["Wqkv"], n1, dqkv)
+        _bsum(g["bqkv"], dqkv)
+        dn1 = matmul(dqkv, self.W("Wqkv").t())
+        dx = _rms_bwd(dn1, xt, P["ln1g"], r1, g["ln1g"], dres=dh, dx_out=dh)
         E = dx.shape[1]
         return self.make_gradient(), dx.reshape(B, T, E).permute(0, 2, 1)
 

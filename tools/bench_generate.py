@@ -41,12 +41,16 @@
              ``--tree PATH`` imports the package from another checkout (the parent commit's, with its own kernel
              library), so the same rows can be taken from both trees in alternating processes.
 
+  --block llama  Llama-style blocks (RMSNorm, pre-norm, SwiGLU with ffnSize 2048) against post-LayerNorm GELU blocks
+             (ffnSize 3072, the same parameter count) on the rotary 12-layer, hidden-768 model: the rows of --rotary.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
        python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]
        python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]
        python tools/bench_generate.py --kv-heads 4 [--batch 32] [--out FILE]
-       python tools/bench_generate.py --rotary [--positions learned] [--tree PATH] [--out FILE]"""
+       python tools/bench_generate.py --rotary [--positions learned] [--tree PATH] [--out FILE]
+       python tools/bench_generate.py --block llama [--out FILE]"""
 import argparse
 import sys
 import time
@@ -536,6 +540,32 @@ def rotary_mode(batches, n, passes, positions):
         f"12 heads, maxPositions {MAXP}), bf16, V = {V}, greedy, {n} new tokens; whole calls (prompt included) on the "
         f"host clock, ended by a device synchronise; median of {passes} passes (min .. max), the variants alternating "
         "within a pass; x = tokens/s against the learned-position model's same mode")
+    _compare_models(nets, kinds, V, batches, n, passes)
+
+
+def block_mode(batches, n, passes):
+    """--block llama: the Llama-style block (RMSNorm, pre-norm, SwiGLU with ffnSize 2048) against today's (LayerNorm,
+    post-norm, GELU with ffnSize 3072) at equal parameter count on the 12-layer, hidden-768 rotary model."""
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, H, E = 77, 12, 768
+    kinds = ["bert", "llama"]
+    style = {"bert": dict(ffn=3072),
+             "llama": dict(ffn=2048, normalization="rms", normPlacement="pre", ffnActivation="swiglu")}
+    nets = {k: TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=E, layers=12, heads=H,
+                                         dataType=DataType.BFLOAT16, positionEncoding="rotary",
+                                         **style[k]).init(device=DEV) for k in kinds}
+    say(f"== generate() with Llama-style blocks (rms / pre / swiglu, ffnSize 2048) against post-LayerNorm GELU blocks "
+        f"(ffnSize 3072) on TextGenerationTransformer(768, 12 layers, 12 heads, rotary), bf16, V = {V}, greedy, {n} new "
+        f"tokens; whole calls (prompt included) on the host clock, ended by a device synchronise; median of {passes} "
+        "passes (min .. max), the variants alternating within a pass; x = tokens/s against the post-LayerNorm model's "
+        "same mode")
+    _compare_models(nets, kinds, V, batches, n, passes)
+
+
+def _compare_models(nets, kinds, V, batches, n, passes):
+    """generate() eager and graph-replayed at prefix 128 and 1024, then a training step, of the models ``nets`` (by
+    kind, the first the base line), the variants alternating within a pass."""
     say("   parameters: " + ", ".join(f"{k} {nets[k].numParams()}" for k in kinds))
     for mb in batches:
         for P in (128, 1024):
@@ -561,7 +591,7 @@ def rotary_mode(batches, n, passes, positions):
                 short.append(sorted(_sync_time(lambda: call(net, kw, few)) for _ in range(passes))[passes // 2])
             per = [(m - ts) / (n - few) * 1e3 for ts, m in zip(short, med)]
             for i, ((vn, _, _), t, m) in enumerate(zip(variants, times, med)):
-                b = (i // len(kinds)) * len(kinds)               # the learned-position row of the same mode
+                b = (i // len(kinds)) * len(kinds)               # the base model's row of the same mode
                 say(f"batch {mb:2d} prefix {P:4d} {vn}: {mb * n / m:9.1f} tok/s  {m * 1e3:8.1f} ms per call "
                     f"({min(t) * 1e3:.1f} .. {max(t) * 1e3:.1f})  x {med[b] / m:5.3f} | step alone {per[i]:6.2f} ms  x "
                     f"{per[b] / per[i]:5.3f}")
@@ -609,6 +639,8 @@ def main():
                     help="rotary embeddings against learned positions: generate(), generate(useGraph=True), training")
     ap.add_argument("--positions", choices=["both", "learned", "rotary"], default="both",
                     help="--rotary: the models to measure")
+    ap.add_argument("--block", choices=["llama"], default=None,
+                    help="Llama-style blocks against post-LayerNorm GELU blocks: generate(), useGraph=True, training")
     ap.add_argument("--tree", default=None, help="import the package from this checkout instead of the tool's own")
     ap.add_argument("--parent-lib", default=None,
                     help="kernel library built from the parent commit (--ragged, --graph)")
@@ -638,6 +670,8 @@ def main():
         kv_heads_mode([int(h) for h in a.kv_heads.split(",")], a.batch, a.tokens, a.passes)
     if a.rotary:
         rotary_mode(a.batch, a.tokens, a.passes, a.positions)
+    if a.block:
+        block_mode(a.batch, a.tokens, a.passes)
 
 
 if __name__ == "__main__":
