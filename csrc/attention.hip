@@ -107,8 +107,108 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_gqa_kernel(const hb* __rest
                                         Hkv * D);
 }
 
+// The sliding-window forms (the WIN = true instances of the bodies, always causal): one kernel per body for both head
+// layouts, GQA = false being Hkv == H with its compile-time group size and V offset.
+template <int D, typename hb, int NB, bool DROP, bool GQA>
+__global__ void __launch_bounds__(256) attn_fwd_win_kernel(const hb* __restrict__ qkv, const float* __restrict__ mask,
+                                                           hb* __restrict__ out, float* __restrict__ lse, int T, int H,
+                                                           int Hkv, float scale2, int window, DropArgs da) {
+  const long long ld = (long long)(H + 2 * Hkv) * D;
+  attn_fwd_body<D, hb, NB, DROP, GQA, true>(qkv, T * ld, ld, qkv + H * D, T * ld, ld, mask, out, lse, T, T, H, scale2,
+                                            1, da, H / Hkv, Hkv * D, window);
+}
+
+template <int D, typename hb, bool DROP, bool GQA>
+__global__ void __launch_bounds__(256) attn_bwd_dq_win_kernel(const hb* __restrict__ qkv, const hb* __restrict__ dout,
+                                                              const float* __restrict__ mask,
+                                                              const float* __restrict__ lse,
+                                                              float* __restrict__ dq_dot, hb* __restrict__ dqkv,
+                                                              int T, int H, int Hkv, float scale2, float scale,
+                                                              int window, DropArgs da) {
+  const long long ld = (long long)(H + 2 * Hkv) * D;
+  attn_bwd_dq_body<D, hb, DROP, GQA, true>(qkv, T * ld, ld, qkv + H * D, T * ld, ld, dout, mask, lse, dq_dot, dqkv,
+                                           T * ld, ld, T, T, H, scale2, scale, 1, da, H / Hkv, Hkv * D, window,
+                                           dq_dot);
+}
+
+template <int D, typename hb, bool DROP, bool GQA>
+__global__ void __launch_bounds__(256) attn_bwd_dkdv_win_kernel(const hb* __restrict__ qkv,
+                                                                const hb* __restrict__ dout,
+                                                                const float* __restrict__ mask,
+                                                                const float* __restrict__ lse,
+                                                                const float* __restrict__ dq_dot,
+                                                                hb* __restrict__ dqkv, int T, int H, int Hkv,
+                                                                float scale2, float scale, int window, DropArgs da) {
+  const long long ld = (long long)(H + 2 * Hkv) * D;
+  attn_bwd_dkdv_body<D, hb, DROP, GQA, true>(qkv, T * ld, ld, qkv + H * D, T * ld, ld, dout, mask, lse, dq_dot,
+                                             dqkv + H * D, T * ld, ld, T, T, H, scale2, scale, 1, da, H / Hkv,
+                                             Hkv * D, window);
+}
+
 // ------------------------------------------------------------------------------------------------ launch
 static bool gqa_heads_ok(int H, int Hkv) { return H >= 1 && Hkv >= 1 && H % Hkv == 0; }
+
+template <bool DROP>
+static int fwd_win_dispatch(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H,
+                            int Hkv, int D, float scale, int window, DropArgs da, hipStream_t s) {
+  if (B < 1 || T < 1 || window < 1 || window >= T || !gqa_heads_ok(H, Hkv)) return -1;
+  const int W = window;
+  return attn_dispatch(dt, D, [&](auto d, auto e) {
+    constexpr int DD = decltype(d)::value, NB = DD == 64 ? 2 : 1;
+    using hb = typename decltype(e)::type;
+    const dim3 grid((T + BLK - 1) / BLK, B * H);
+    if (Hkv == H)
+      hipLaunchKernelGGL((attn_fwd_win_kernel<DD, hb, NB, DROP, false>), grid, dim3(256), 0, s, (const hb*)qkv, mask,
+                         (hb*)out, lse, T, H, Hkv, scale * kLog2e, W, da);
+    else
+      hipLaunchKernelGGL((attn_fwd_win_kernel<DD, hb, NB, DROP, true>), grid, dim3(256), 0, s, (const hb*)qkv, mask,
+                         (hb*)out, lse, T, H, Hkv, scale * kLog2e, W, da);
+    return (int)hipGetLastError();
+  });
+}
+
+// With dropout the dQ kernel computes Delta itself (csrc/attention_body.h) and leaves it in dq_dot for the dK/dV
+// kernel, which therefore runs second and no pre kernel is launched; without dropout the order is the unwindowed one.
+template <bool DROP, bool GQA>
+static int bwd_win_launch(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                          const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int Hkv, int D,
+                          float scale, int W, DropArgs da, hipStream_t s) {
+  return attn_dispatch(dt, D, [&](auto d, auto e) {
+    constexpr int DD = decltype(d)::value;
+    using hb = typename decltype(e)::type;
+    const dim3 grid((T + BLK - 1) / BLK, B * H), gridkv((T + BLK - 1) / BLK, B * Hkv);
+    auto dkdv = [&] {
+      hipLaunchKernelGGL((attn_bwd_dkdv_win_kernel<DD, hb, DROP, GQA>), gridkv, dim3(256), 0, s, (const hb*)qkv,
+                         (const hb*)dout, mask, lse, dq_dot, (hb*)dqkv, T, H, Hkv, scale * kLog2e, scale, W, da);
+    };
+    auto dq = [&] {
+      hipLaunchKernelGGL((attn_bwd_dq_win_kernel<DD, hb, DROP, GQA>), grid, dim3(256), 0, s, (const hb*)qkv,
+                         (const hb*)dout, mask, lse, dq_dot, (hb*)dqkv, T, H, Hkv, scale * kLog2e, scale, W, da);
+    };
+    if constexpr (DROP) {
+      dq();
+      dkdv();
+    } else {
+      const long long n = (long long)B * H * T;
+      hipLaunchKernelGGL((attn_bwd_pre_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                         (const hb*)out, (const hb*)dout, dq_dot, B, T, H);
+      dkdv();
+      dq();
+    }
+    return (int)hipGetLastError();
+  });
+}
+
+template <bool DROP>
+static int bwd_win_dispatch(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                            const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int Hkv, int D,
+                            float scale, int window, DropArgs da, hipStream_t s) {
+  if (B < 1 || T < 1 || window < 1 || window >= T || !gqa_heads_ok(H, Hkv)) return -1;
+  return Hkv == H ? bwd_win_launch<DROP, false>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale,
+                                                window, da, s)
+                  : bwd_win_launch<DROP, true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale,
+                                               window, da, s);
+}
 
 template <bool DROP>
 static int fwd_dispatch(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T, int H,
@@ -234,6 +334,46 @@ DL4J_API int dl4j_attn_bwd_drop_gqa_dt(int dt, const void* qkv, const void* out,
   DropArgs da;
   if (!drop_args(drop, seed, offset, &da) || !attn_aligned16({qkv, out, dout, dqkv})) return -1;
   return bwd_dispatch<true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale, causal, da, s);
+}
+
+// Causal attention with a sliding window: query q sees keys q - window < k <= q (window >= 1 keys, itself included;
+// Mistral's sliding_window). Operands, layouts and status codes of dl4j_attn_fwd_gqa_dt / dl4j_attn_bwd_gqa_dt with
+// causal = 1 (Hkv = H is plain multi-head); key blocks no query of a tile can see are skipped. drop = 0 runs the
+// kernels without dropout (seed / offset unused, offset may be null); drop in (0, 1) is that of the *_drop_* entry
+// points and draws the same keep mask. A window >= T sees what the causal cut sees and runs the causal kernels
+// without a window (their bits). With dropout the windowed backward takes Delta from its own probabilities instead of
+// the stored output (csrc/attention_body.h) and uses dq_dot as the hand-over between its two kernels. -1 also for
+// window < 1.
+DL4J_API int dl4j_attn_fwd_win_dt(int dt, const void* qkv, const float* mask, void* out, float* lse, int B, int T,
+                                  int H, int Hkv, int D, float scale, int window, float drop, unsigned long long seed,
+                                  const long long* offset, hipStream_t s) {
+  if (!attn_aligned16({qkv, out}) || window < 1) return -1;
+  if (window >= T)
+    return drop == 0.f ? dl4j_attn_fwd_gqa_dt(dt, qkv, mask, out, lse, B, T, H, Hkv, D, scale, 1, s)
+                       : dl4j_attn_fwd_drop_gqa_dt(dt, qkv, mask, out, lse, B, T, H, Hkv, D, scale, 1, drop, seed,
+                                                   offset, s);
+  if (drop == 0.f)
+    return fwd_win_dispatch<false>(dt, qkv, mask, out, lse, B, T, H, Hkv, D, scale, window, DropArgs{}, s);
+  DropArgs da;
+  if (!drop_args(drop, seed, offset, &da)) return -1;
+  return fwd_win_dispatch<true>(dt, qkv, mask, out, lse, B, T, H, Hkv, D, scale, window, da, s);
+}
+
+DL4J_API int dl4j_attn_bwd_win_dt(int dt, const void* qkv, const void* out, const void* dout, const float* mask,
+                                  const float* lse, float* dq_dot, void* dqkv, int B, int T, int H, int Hkv, int D,
+                                  float scale, int window, float drop, unsigned long long seed,
+                                  const long long* offset, hipStream_t s) {
+  if (!attn_aligned16({qkv, out, dout, dqkv}) || window < 1) return -1;
+  if (window >= T)
+    return drop == 0.f ? dl4j_attn_bwd_gqa_dt(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale, 1, s)
+                       : dl4j_attn_bwd_drop_gqa_dt(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale,
+                                                   1, drop, seed, offset, s);
+  if (drop == 0.f)
+    return bwd_win_dispatch<false>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale, window,
+                                   DropArgs{}, s);
+  DropArgs da;
+  if (!drop_args(drop, seed, offset, &da)) return -1;
+  return bwd_win_dispatch<true>(dt, qkv, out, dout, mask, lse, dq_dot, dqkv, B, T, H, Hkv, D, scale, window, da, s);
 }
 
 // Test / debug only: keep [B*H, T, T] uint8 (1 = kept) of the mask the DROP kernels apply. Never part of a step.

@@ -16,6 +16,14 @@
 // dK + v_off. lse, dq_dot and the dropout mask stay indexed by the QUERY head. With GQA = false G is the constant 1
 // and v_off the constant E: those instances are the kernels as they were, not a run-time special case.
 //
+// Sliding window (the WIN = true instances of the three bodies, causal only): query q sees keys q - window < k <= q.
+// The forward and dQ bodies start at the first key block the tile's first query sees, max(0, q0 - window + 1) / BLK
+// (for NB = 2 a round may therefore start at an odd block: rounds carry no alignment), the dK/dV body stops at the last
+// query block that sees its key block, and the score mask gains key > q - window. Blocks outside are skipped, not
+// masked; the dropout tile stays keyed by the absolute (q, k), so a pair keeps its draw with and without a window.
+// With WIN and DROP the dQ body computes Delta itself in a first pass over its blocks (see there) and the dK/dV
+// kernel, launched after it, reads that. With WIN = false the bodies are the kernels as they were.
+//
 // CDNA4 mapping (per 64-wide wave, v_mfma_f32_16x16x32_{bf16,f16}):
 //  * forward / dQ: grid (ceil(Tq/64), B*H); a wave owns 16 queries. Scores are computed TRANSPOSED, Sᵀ = K·Qᵀ, so the
 //    query is the lane's accumulator column: the online-softmax state (running max m, sum l) is one scalar per lane and
@@ -146,11 +154,11 @@ __device__ __forceinline__ void attn_kv_stash(hb* Kj, hb* Vtj, int ldv, const V8
 // The masking and online-softmax update is written out here: as a helper function it is optimised on its own before
 // it is inlined, its exp2 / add order changes, and the D = 64 instances go from 116-124 to 132-136 VGPRs, one wave per
 // SIMD less.
-template <int D, typename hb, int NB, bool DROP, bool GQA = false>
+template <int D, typename hb, int NB, bool DROP, bool GQA = false, bool WIN = false>
 __device__ __forceinline__ void attn_fwd_body(const hb* qp, long long q_bs, long long q_ld, const hb* kp,
                                               long long k_bs, long long k_ld, const float* mask, hb* out, float* lse,
                                               int Tq, int Tk, int H, float scale2, int causal, DropArgs da,
-                                              int Garg = 1, int v_off_arg = 0) {
+                                              int Garg = 1, int v_off_arg = 0, int window = 0) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = NB * BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Ks[NB * BLK * LDK];
@@ -173,7 +181,9 @@ __device__ __forceinline__ void attn_fwd_body(const hb* qp, long long q_bs, long
   const float* mrow = mask ? mask + (long long)b * Tk : nullptr;
   const int nkb = causal ? min((blockIdx.x * BLK + BLK + BLK - 1) / BLK, (Tk + BLK - 1) / BLK) : (Tk + BLK - 1) / BLK;
   const int rows = min(Tk, nkb * BLK);                           // blocks at or beyond nkb are not loaded
-  for (int kb0 = 0; kb0 < nkb; kb0 += NB) {
+  int kb_first = 0;                                              // WIN: the first block the tile's first query sees
+  if constexpr (WIN) kb_first = max(0, (int)blockIdx.x * BLK - window + 1) / BLK;
+  for (int kb0 = kb_first; kb0 < nkb; kb0 += NB) {
     __syncthreads();
     V8<hb> kr[NB][KS], vr[NB][KS];
 #pragma unroll
@@ -194,6 +204,7 @@ __device__ __forceinline__ void attn_fwd_body(const hb* qp, long long q_bs, long
         for (int r = 0; r < 4; ++r) {
           const int key = kb * BLK + mt * 16 + hgrp * 4 + r;
           bool ok = key < Tk && (!causal || key <= q);
+          if constexpr (WIN) ok = ok && key > q - window;
           if (ok && mrow) ok = mrow[key] != 0.f;
           const float v = ok ? s[mt][r] * scale2 : kNegInf;
           s[mt][r] = v;
@@ -261,12 +272,13 @@ __global__ void __launch_bounds__(256) attn_bwd_pre_kernel(const hb* __restrict_
 }
 
 // dQ per query block (forward orientation: query on the lane). DROP: dS = P o (D o dP - Delta), D in {0, 1/keep_eff}.
-template <int D, typename hb, bool DROP, bool GQA = false>
+template <int D, typename hb, bool DROP, bool GQA = false, bool WIN = false>
 __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, long long q_ld, const hb* kp,
                                                  long long k_bs, long long k_ld, const hb* dout, const float* mask,
                                                  const float* lse, const float* dq_dot, hb* dq, long long dq_bs,
                                                  long long dq_ld, int Tq, int Tk, int H, float scale2, float scale,
-                                                 int causal, DropArgs da, int Garg = 1, int v_off_arg = 0) {
+                                                 int causal, DropArgs da, int Garg = 1, int v_off_arg = 0,
+                                                 int window = 0, float* delta_out = nullptr) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDT = BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Ks[BLK * LDK];
@@ -283,7 +295,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
   attn_ld_frag<D>(qf, qp + (long long)b * q_bs + (long long)qc * q_ld + h * D, hgrp);
   attn_ld_frag<D>(df, dout + ((long long)b * Tq + qc) * E + h * D, hgrp);
   const float l2 = lse[(long long)bh * Tq + qc];
-  const float dd = dq_dot[(long long)bh * Tq + qc];
+  float dd = 0.f;
+  if constexpr (!(WIN && DROP)) dd = dq_dot[(long long)bh * Tq + qc];
   unsigned drop_off = 0;
   if constexpr (DROP) drop_off = (unsigned)da.offset[0];
   f4_t acc[DT];
@@ -291,7 +304,39 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
   for (int dt = 0; dt < DT; ++dt) acc[dt] = f4_t{0.f, 0.f, 0.f, 0.f};
   const float* mrow = mask ? mask + (long long)b * Tk : nullptr;
   const int nkb = causal ? min((blockIdx.x * BLK + BLK + BLK - 1) / BLK, (Tk + BLK - 1) / BLK) : (Tk + BLK - 1) / BLK;
-  for (int kb = 0; kb < nkb; ++kb) {
+  int kb_first = 0;                                              // WIN: as in the forward
+  if constexpr (WIN) kb_first = max(0, (int)blockIdx.x * BLK - window + 1) / BLK;
+  if constexpr (WIN && DROP) {
+    // Delta = sum_k P (D o dP) over the window's few blocks, in fp32 from this pass's own probabilities, instead of
+    // dO . O from the stored output: O = (P o D) V / keep_eff is rounded to 16 bits, and where a query sees few keys
+    // dS = P (D o dP - Delta) cancels down to that rounding (with one visible key the exact dS is zero). A first
+    // pass over the same blocks in the same order; the result also goes to delta_out for the dK/dV kernel, which
+    // is launched after this one. No atomics: the sum runs in a fixed order.
+    float part = 0.f;
+    for (int kb = kb_first; kb < nkb; ++kb) {
+      __syncthreads();
+      stage_rows<D>(Ks, LDK, kbase, k_ld, kb * BLK, Tk);
+      stage_rows<D>(Vs, LDK, kbase + v_off, k_ld, kb * BLK, Tk);
+      __syncthreads();
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        const f4_t s = attn_score_tile<D>(Ks, qf, mt, col, hgrp), dp = attn_score_tile<D>(Vs, df, mt, col, hgrp);
+        const unsigned w = attn_drop_word(
+            attn_drop_tile(da.seed, drop_off, (unsigned)bh, (unsigned)q >> 2, (unsigned)(kb * 16 + mt * 4 + hgrp)),
+            q & 3);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = kb * BLK + mt * 16 + hgrp * 4 + r;
+          bool ok = key < Tk && q < Tq && key <= q && key > q - window && attn_drop_keep(w, r, da.thr);
+          if (ok && mrow) ok = mrow[key] != 0.f;
+          if (ok) part += exp2f(s[r] * scale2 - l2) * (dp[r] * da.inv_keep);
+        }
+      }
+    }
+    dd = wsum16(part);
+    if (hgrp == 0 && q < Tq) delta_out[(long long)bh * Tq + q] = dd;
+  }
+  for (int kb = kb_first; kb < nkb; ++kb) {
     __syncthreads();
     stage_rows<D>(Ks, LDK, kbase, k_ld, kb * BLK, Tk);
     stage_rows<D>(Vs, LDK, kbase + v_off, k_ld, kb * BLK, Tk);
@@ -314,6 +359,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
       for (int r = 0; r < 4; ++r) {
         const int key = kb * BLK + mt * 16 + hgrp * 4 + r;
         bool ok = key < Tk && q < Tq && (!causal || key <= q);
+        if constexpr (WIN) ok = ok && key > q - window;
         if (ok && mrow) ok = mrow[key] != 0.f;
         const float p = ok ? exp2f(s[mt][r] * scale2 - l2) : 0.f;
         float dpv = dp[mt][r];
@@ -333,12 +379,13 @@ __device__ __forceinline__ void attn_bwd_dq_body(const hb* qp, long long q_bs, l
 // GQA: grid.y is B*Hkv; the block loads its K / V fragments once and runs the query-block loop for each query head
 // g = 0 .. G-1 of its group in that fixed order (that head's Q, dO, lse, dq_dot and dropout tile), dK and dV
 // accumulating in the same fp32 registers and stored once: no atomics, no workspace, bitwise reproducible.
-template <int D, typename hb, bool DROP, bool GQA = false>
+template <int D, typename hb, bool DROP, bool GQA = false, bool WIN = false>
 __device__ __forceinline__ void attn_bwd_dkdv_body(const hb* qp, long long q_bs, long long q_ld, const hb* kp,
                                                    long long k_bs, long long k_ld, const hb* dout, const float* mask,
                                                    const float* lse, const float* dq_dot, hb* dk_out, long long dk_bs,
                                                    long long dk_ld, int Tq, int Tk, int H, float scale2, float scale,
-                                                   int causal, DropArgs da, int Garg = 1, int v_off_arg = 0) {
+                                                   int causal, DropArgs da, int Garg = 1, int v_off_arg = 0,
+                                                   int window = 0) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDQ = D + 8, LDT = BLK + 8;
   __shared__ __attribute__((aligned(16))) hb Qs[BLK * LDQ];
@@ -364,7 +411,9 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const hb* qp, long long q_bs,
   f4_t dk[DT], dv[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dk[dt] = dv[dt] = f4_t{0.f, 0.f, 0.f, 0.f};
-  const int nqb = (Tq + BLK - 1) / BLK;
+  int nqb = (Tq + BLK - 1) / BLK;
+  // WIN: the last query that sees a key of this block is its last key + window - 1 (the host keeps window <= Tq)
+  if constexpr (WIN) nqb = min(nqb, ((int)blockIdx.x * BLK + BLK - 1 + window - 1) / BLK + 1);
   const int qb0 = causal ? blockIdx.x : 0;                     // queries before the key block see none of it
   for (int g = 0; g < G; ++g) {
     const int h = GQA ? j * G + g : j;
@@ -398,7 +447,8 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const hb* qp, long long q_bs,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qi = mt * 16 + hgrp * 4 + r, q = qb * BLK + qi;
-          const bool ok = kvalid && q < Tq && (!causal || key <= q);
+          bool ok = kvalid && q < Tq && (!causal || key <= q);
+          if constexpr (WIN) ok = ok && key > q - window;
           const float p = ok ? exp2f(s[mt][r] * scale2 - Ls[qi]) : 0.f;
           float dpv = dp[mt][r];
           bool keep = true;

@@ -109,10 +109,12 @@ template <int D, typename hb> struct KvCacheFp8 {
 // The body takes the position of its own batch row: the uniform kernel passes the host's pos, the ragged one
 // pos - shortfall[b] (everything below — key-block count, split ranges, causal cut, zero staging — follows from it).
 // GQA: the cache side (row stride, V offset, scale bytes) is that of Hkv heads, the lane-columns are slots.
-template <int D, typename hb, typename CP = KvCache16<D, hb>, bool GQA = false>
+// WIN: query i sees keys pos + i - window < k <= pos + i; the key blocks are [kb_first, nkb) with kb_first the first
+// block the tile's smallest query sees, the S splits divide that range and the blocks before it are never read.
+template <int D, typename hb, typename CP = KvCache16<D, hb>, bool GQA = false, bool WIN = false>
 __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, const typename CP::elem* __restrict__ kv,
                                                  hb* __restrict__ out, float* __restrict__ ws, int Tn, int H, int pos,
-                                                 int Tcap, int S, float scale2, int Garg = 1) {
+                                                 int Tcap, int S, float scale2, int Garg = 1, int window = 0) {
   constexpr int KS = D / 32, DT = D / 16;
   constexpr int LDK = D + 8, LDV = BLK + 8;
   constexpr int CPR = CP::CPR, PER = BLK * CPR / 256;            // 16-byte chunks per row / per thread per block
@@ -143,9 +145,12 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
   float m = kNegInf, l = 0.f;
   // this split's key blocks, cut at the last block any query of the tile can see
   const int nkb = (L + BLK - 1) / BLK;
-  const int kb_lo = (int)((long long)split * nkb / S);
+  int kb_first = 0;                                              // WIN: the first block the tile's smallest query sees
+  if constexpr (WIN) kb_first = max(0, pos + (GQA ? q0 / G : q0) - window + 1) / BLK;
+  const int nwb = nkb - kb_first;
+  const int kb_lo = kb_first + (int)((long long)split * nwb / S);
   const int i_hi = GQA ? (min(q0 + BLK, nslots) - 1) / G : min(q0 + BLK, Tn) - 1;   // the tile's largest query
-  const int kb_hi = min((int)((long long)(split + 1) * nkb / S), (pos + i_hi) / BLK + 1);
+  const int kb_hi = min(kb_first + (int)((long long)(split + 1) * nwb / S), (pos + i_hi) / BLK + 1);
   typename CP::chunk kr[PER], vr[PER];
   typename CP::scale_t ksc[PER], vsc[PER];
   auto fetch = [&](int kb) {
@@ -200,7 +205,11 @@ __device__ __forceinline__ void attn_decode_body(const hb* __restrict__ qkv, con
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kb * BLK + mt * 16 + hgrp * 4 + r;
-        const float v = (key < L && key <= pos + qi) ? s[mt][r] * scale2 : kNegInf;
+        float v;
+        if constexpr (WIN)
+          v = (key < L && key <= pos + qi && key > pos + qi - window) ? s[mt][r] * scale2 : kNegInf;
+        else
+          v = (key < L && key <= pos + qi) ? s[mt][r] * scale2 : kNegInf;
         s[mt][r] = v;
         bm = fmaxf(bm, v);
       }
@@ -298,6 +307,19 @@ __global__ void __launch_bounds__(256) attn_decode_gqa_kernel(const hb* __restri
   const int b = blockIdx.y / Hkv;
   const int pb = shortfall ? pos - min(max(shortfall[b], 0), pos) : pos;
   attn_decode_body<D, hb, CP, true>(qkv, kv, out, ws, Tn, H, pb, Tcap, S, scale2, H / Hkv);
+}
+
+// The sliding-window variants, all eight from one kernel (CP: 16-bit or fp8 cache; GQA = false is Hkv == H with the
+// compile-time group size; shortfall null = every row at pos): the body with WIN = true at the row's own position.
+template <int D, typename hb, typename CP, bool GQA>
+__global__ void __launch_bounds__(256) attn_decode_win_kernel(const hb* __restrict__ qkv,
+                                                              const typename CP::elem* __restrict__ kv,
+                                                              hb* __restrict__ out, float* __restrict__ ws, int Tn,
+                                                              int H, int Hkv, int pos, int Tcap, int S, float scale2,
+                                                              int window, const int* __restrict__ shortfall) {
+  const int b = blockIdx.y / Hkv;
+  const int pb = shortfall ? pos - min(max(shortfall[b], 0), pos) : pos;
+  attn_decode_body<D, hb, CP, GQA, true>(qkv, kv, out, ws, Tn, H, pb, Tcap, S, scale2, H / Hkv, window);
 }
 
 // out[b, q, h*D + d] = sum_s acc_s[d] 2^(m_s - M) / sum_s l_s 2^(m_s - M), M = max_s m_s, in the order s = 0 .. S-1;
@@ -600,6 +622,40 @@ static int decode_launch(int dt, const void* qkv, const void* kv, void* out, flo
   });
 }
 
+// The windowed launch: the S splits divide the key blocks from the first one the window reaches (at the upper bound
+// pos) to the last, so splits is clamped to that count.
+template <bool FP8>
+static int decode_win_launch(int dt, const void* qkv, const void* kv, void* out, float* ws, const int* shortfall,
+                             int B, int Tn, int H, int Hkv, int D, int pos, int Tcap, int window, int splits,
+                             float scale, hipStream_t s) {
+  if (!decode_shape_ok(dt, B, Tn, H, Hkv, D, pos, Tcap) || !qkv || !kv || !out || splits < 1 || window < 1) return -1;
+  if (!attn_aligned16({qkv, kv, out, ws})) return -1;
+  const int W = window < pos + Tn ? window : pos + Tn;           // a wider window sees what pos + Tn sees
+  const int first = (pos - W + 1 > 0 ? pos - W + 1 : 0) / BLK * BLK;
+  const int S = decode_clamp_splits(splits, pos + Tn - first);
+  if (S > 1 && !ws) return -1;
+  return attn_dispatch(dt, D, [&](auto d, auto e) {
+    constexpr int DD = decltype(d)::value;
+    using hb = typename decltype(e)::type;
+    using CP = std::conditional_t<FP8, KvCacheFp8<DD, hb>, KvCache16<DD, hb>>;
+    using ce = typename CP::elem;
+    const float scale2 = scale * kLog2e;
+    const dim3 grid(S, B * Hkv, (Tn * (H / Hkv) + BLK - 1) / BLK);
+    if (Hkv != H)
+      hipLaunchKernelGGL((attn_decode_win_kernel<DD, hb, CP, true>), grid, dim3(256), 0, s, (const hb*)qkv,
+                         (const ce*)kv, (hb*)out, ws, Tn, H, Hkv, pos, Tcap, S, scale2, W, shortfall);
+    else
+      hipLaunchKernelGGL((attn_decode_win_kernel<DD, hb, CP, false>), grid, dim3(256), 0, s, (const hb*)qkv,
+                         (const ce*)kv, (hb*)out, ws, Tn, H, Hkv, pos, Tcap, S, scale2, W, shortfall);
+    if (S > 1) {
+      const long long n = (long long)B * H * Tn * (DD / 4);
+      hipLaunchKernelGGL((attn_decode_combine_kernel<DD, hb>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws,
+                         (hb*)out, (long long)B * H, Tn, H, S);
+    }
+    return (int)hipGetLastError();
+  });
+}
+
 // out [B,Tn,H*D]; rows [0, pos+Tn) of kv [B,Tcap,2*Hkv*D] are the keys / values (the new rows already appended), query
 // i sees keys <= pos + i. splits >= 1 is clamped to the number of 64-key blocks; ws: fp32 workspace of
 // dl4j_attn_decode_ws_bytes_gqa(..., splits) bytes (may be null for one split). -1 = unsupported shape / dtype,
@@ -650,4 +706,25 @@ DL4J_API int dl4j_attn_decode_fp8_gqa_dt(int dt, const void* qkv, const void* kv
 DL4J_API int dl4j_attn_decode_fp8_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws, int B, int Tn,
                                      int H, int D, int pos, int Tcap, int splits, float scale, hipStream_t s) {
   return decode_launch<true>(dt, qkv, kv8, out, ws, nullptr, B, Tn, H, H, D, pos, Tcap, splits, scale, s);
+}
+
+// Cached decoding with a sliding window: query i sees keys pos + i - window < k <= pos + i (at pos - shortfall[b] in a
+// ragged batch). Arguments, workspace and status codes of dl4j_attn_decode_ragged_gqa_dt (shortfall may be null,
+// Hkv = H is plain multi-head); -1 also for window < 1. The key blocks wholly before the window are not read, and
+// splits divides (and is clamped to) the blocks from the first one the window reaches at pos to the last: size it
+// with dl4j_attn_decode_splits_gqa on that many keys, not on pos + Tn. window >= pos + Tn gives the bits of the
+// unwindowed entry at the same split count.
+DL4J_API int dl4j_attn_decode_win_dt(int dt, const void* qkv, const void* kv, void* out, float* ws,
+                                     const int* shortfall, int B, int Tn, int H, int Hkv, int D, int pos, int Tcap,
+                                     int window, int splits, float scale, hipStream_t s) {
+  return decode_win_launch<false>(dt, qkv, kv, out, ws, shortfall, B, Tn, H, Hkv, D, pos, Tcap, window, splits, scale,
+                                  s);
+}
+
+// The same over the fp8 cache kv8 [B,Tcap,R] bytes.
+DL4J_API int dl4j_attn_decode_win_fp8_dt(int dt, const void* qkv, const void* kv8, void* out, float* ws,
+                                         const int* shortfall, int B, int Tn, int H, int Hkv, int D, int pos,
+                                         int Tcap, int window, int splits, float scale, hipStream_t s) {
+  return decode_win_launch<true>(dt, qkv, kv8, out, ws, shortfall, B, Tn, H, Hkv, D, pos, Tcap, window, splits, scale,
+                                 s);
 }

@@ -972,7 +972,8 @@ class TextGenerationTransformer(ZooModel):
 
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
                  maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, positionEncoding=None,
-                 ropeTheta=10000.0, normalization="layer", normPlacement="post", ffnActivation="gelu", **kw):
+                 ropeTheta=10000.0, normalization="layer", normPlacement="post", ffnActivation="gelu",
+                 attentionWindow=None, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
@@ -985,9 +986,26 @@ class TextGenerationTransformer(ZooModel):
         # the block style of every block: ("layer", "post", "gelu") is BERT's, ("rms", "pre", "swiglu") the Llama
         # family's; with "pre" an RMSNormalization layer ``final_norm`` stands before the output layer
         self.normalization, self.normPlacement, self.ffnActivation = normalization, normPlacement, ffnActivation
+        # sliding-window attention: None, a positive integer for every block, or a sequence with one entry per block
+        # (None = full attention in that block; Gemma alternates the two)
+        self.attentionWindow = attentionWindow
+
+    def blockWindows(self):
+        """``attentionWindow`` as a list with one entry (None or the window) per block."""
+        w = self.attentionWindow
+        if w is None or isinstance(w, (int, float)):
+            return [w] * self.layers
+        w = list(w)
+        if len(w) != self.layers:
+            from ..exceptions import DL4JInvalidConfigException
+            raise DL4JInvalidConfigException(
+                f"TextGenerationTransformer: attentionWindow has {len(w)} entries for {self.layers} blocks; give one "
+                "window (or None) per block, or a single value for all of them")
+        return w
 
     def graphBuilder(self):
         from ..nn.conf import BertEmbeddingLayer, RMSNormalization, TransformerEncoderLayer
+        windows = self.blockWindows()
         g = (self._builder().updater(Adam(self.learningRate)).weightInit(NormalDistribution(0.0, 0.02))
              .graphBuilder())
         g.addInputs("tokens")
@@ -1000,7 +1018,8 @@ class TextGenerationTransformer(ZooModel):
                        .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
                        .nKVHeads(self.nKVHeads).positionEncoding(self.positionEncoding)
                        .ropeTheta(self.ropeTheta).normalization(self.normalization)
-                       .normPlacement(self.normPlacement).ffnActivation(self.ffnActivation).build(), prev)
+                       .normPlacement(self.normPlacement).ffnActivation(self.ffnActivation)
+                       .attentionWindow(windows[i]).build(), prev)
             prev = f"decoder_{i}"
         if self.normPlacement == "pre":
             g.addLayer("final_norm", RMSNormalization.Builder().nIn(self.hidden).nOut(self.hidden).build(), prev)

@@ -1440,6 +1440,22 @@ def _check_kv_heads(layer, grouped=True):
             f"nHeads = {layer.nHeads}, got {v!r}")
 
 
+def _check_attention_window(layer):
+    """``attentionWindow``: None (the default: a causal layer attends over its whole prefix) or a positive integer W,
+    the sliding window of Mistral / Gemma / Phi-3: the query at position p sees keys p - W < k <= p, W keys with
+    itself. Causal layers only."""
+    v = layer.attentionWindow
+    if v is None:
+        return
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: attentionWindow is None (no window) or a positive integer, got {v!r}")
+    if not layer.causal:
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: attentionWindow = {v} needs causal = True; a window on a bidirectional layer is not "
+            "supported")
+
+
 ROTARY = "rotary"
 
 
@@ -1508,10 +1524,15 @@ class SelfAttentionLayer(FeedForwardLayer):
 
     ``positionEncoding``: None (the default) or "rotary": rotary position embeddings (RoPE) on the Q and K heads, with
     base ``ropeTheta`` (default 10000). A token's position is its index in the sequence, in ``rnnTimeStep`` the index
-    of its cache row; the cache then holds rotated keys. The head size must be even."""
+    of its cache row; the cache then holds rotated keys. The head size must be even.
+
+    ``attentionWindow``: None (the default) or a positive integer W on a causal layer: sliding-window attention, the
+    query at position p sees keys p - W < k <= p. The rnnTimeStep cache still keeps every row; a step reads the
+    window only."""
     FIELDS = {"nHeads": 1, "headSize": 0, "projectInput": True, "causal": False, "attentionDropout": 0.0,
-              "cacheDataType": None, "nKVHeads": None, "positionEncoding": None, "ropeTheta": 10000.0}
-    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta")
+              "cacheDataType": None, "nKVHeads": None, "positionEncoding": None, "ropeTheta": 10000.0,
+              "attentionWindow": None}
+    _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta", "attentionWindow")
     RUNTIME = "deeplearning4j_amd.nn.layers.attention:SelfAttentionLayerImpl"
 
     def _post_init(self):
@@ -1520,6 +1541,7 @@ class SelfAttentionLayer(FeedForwardLayer):
         _check_cache_dtype(self)
         _check_kv_heads(self)
         self._check_rope()
+        _check_attention_window(self)
 
     def _check_rope(self):
         hs = self.headSize or (self.nOut // self.nHeads if self.nOut else 0)
@@ -1584,6 +1606,10 @@ class TransformerEncoderLayer(FeedForwardLayer):
     the fused projection, with base ``ropeTheta`` (default 10000). A token's position is its index in the sequence,
     in ``rnnTimeStep`` the index of its cache row; the cache then holds rotated keys. The head size must be even.
 
+    ``attentionWindow``: None (the default) or a positive integer W on a causal block: sliding-window attention
+    (Mistral's ``sliding_window``), the query at position p sees keys p - W < k <= p. The rnnTimeStep cache still
+    keeps every row (a position stays a cache row index); the decode kernel reads the window's key blocks only.
+
     ``normalization`` / ``normPlacement``: ("layer", "post"), the default, is the block above; ("rms", "pre") is the
     Llama family's: ``h = x + Attn(RMSNorm(x))``, ``y = h + FFN(RMSNorm(h))`` (csrc/rmsnorm.hip; the add of the first
     residual runs inside the second norm's launch). ``layerNormEps`` is then the RMS epsilon, there are no ``ln1b`` /
@@ -1594,9 +1620,10 @@ class TransformerEncoderLayer(FeedForwardLayer):
     (csrc/swiglu.hip) with ``W1 = [Wg | Wu]`` of shape [nIn, 2*ffnSize]; it works in either block."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
               "attentionDropout": 0.0, "cacheDataType": None, "nKVHeads": None, "positionEncoding": None,
-              "ropeTheta": 10000.0, "normalization": "layer", "normPlacement": "post", "ffnActivation": "gelu"}
+              "ropeTheta": 10000.0, "normalization": "layer", "normPlacement": "post", "ffnActivation": "gelu",
+              "attentionWindow": None}
     _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta", "normalization",
-                        "normPlacement", "ffnActivation")
+                        "normPlacement", "ffnActivation", "attentionWindow")
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
 
     def _post_init(self):
@@ -1607,6 +1634,7 @@ class TransformerEncoderLayer(FeedForwardLayer):
         _check_kv_heads(self)
         self._check_rope()
         _check_block_style(self)
+        _check_attention_window(self)
 
     def preNorm(self):
         return self.normPlacement == "pre"

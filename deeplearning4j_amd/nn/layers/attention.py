@@ -68,15 +68,17 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
                 and TN.attn_supported(q3, H, Hkv):
             if drop > 0.0:
                 st = self.dropoutStream("attention")
-                out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), dropout=drop, rng=st, Hkv=Hkv)
+                out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), dropout=drop, rng=st, Hkv=Hkv,
+                                       window=self.conf.attentionWindow)
                 return out, ("native", out, lse, drop, st)
-            out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), Hkv=Hkv)
+            out, lse = TN.attn_fwd(q3, H, mask, bool(self.conf.causal), Hkv=Hkv, window=self.conf.attentionWindow)
             return out, ("native", out, lse)
         if q3.is_cuda:
             from ...ops import fallback
             fallback.record("attention", f"SelfAttentionLayer head size {q3.shape[-1] // (H + 2 * Hkv)} / {q3.dtype}")
         keep = self.dropoutKeep("attention", (mb, H, T, T), drop, q3) if drop > 0.0 else None
-        out, ctx = TN.attention_fwd_explicit(q3, H, mask, bool(self.conf.causal), keep=keep, Hkv=Hkv)
+        out, ctx = TN.attention_fwd_explicit(q3, H, mask, bool(self.conf.causal), keep=keep, Hkv=Hkv,
+                                             window=self.conf.attentionWindow)
         return out, ("explicit", ctx)
 
     def _attn_bwd(self, qkv, do, mb, T, H, mask, ctx):
@@ -84,7 +86,8 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         if ctx[0] == "native":
             kw = dict(dropout=ctx[3], rng=ctx[4]) if len(ctx) > 3 else {}
             return TN.attn_bwd(qkv.reshape(mb, T, -1), ctx[1], ctx[2], do.reshape(mb, T, -1), H, mask,
-                               bool(self.conf.causal), Hkv=self.conf.kvHeads(), **kw)
+                               bool(self.conf.causal), Hkv=self.conf.kvHeads(), window=self.conf.attentionWindow,
+                               **kw)
         return TN.attention_bwd_explicit(ctx[1], do.reshape(mb, T, -1), qkv.dtype)
 
     def activate(self, x, training=False, mask=None, **kw):
@@ -129,7 +132,7 @@ class SelfAttentionLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         X = x.permute(0, 2, 1).reshape(mb * T, nIn).to(dt).contiguous()
         qkv = self._project(X, mb * T, x.device)
         o = self.cachedAttention(qkv.reshape(mb, T, -1), H, "SelfAttentionLayer rnnTimeStep", self.conf.kvHeads(),
-                                 self.conf.ropeTheta if self.conf.rotary() else None)
+                                 self.conf.ropeTheta if self.conf.rotary() else None, self.conf.attentionWindow)
         Y = matmul(o.reshape(mb * T, d), self.W("Wo"), bias=self.Wbias("bo"))
         z = Y.reshape(mb, T, -1).permute(0, 2, 1)
         y = self.conf.activation.getActivation(z, False) if self.conf.activation is not None else z

@@ -299,7 +299,7 @@ def _drop_bwd(d, dctx):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def _attn_fwd(qkv, B, T, H, mask, causal, drop=0.0, owner=None, Hkv=None):
+def _attn_fwd(qkv, B, T, H, mask, causal, drop=0.0, owner=None, Hkv=None, window=None):
     from ...ops import transformer_native as TN
     Hkv = H if Hkv is None else Hkv
     if _native(qkv, "attention"):
@@ -307,25 +307,25 @@ def _attn_fwd(qkv, B, T, H, mask, causal, drop=0.0, owner=None, Hkv=None):
         if TN.attn_supported(q3, H, Hkv):
             if drop > 0.0:
                 st = owner.dropoutStream("attention")
-                out, lse = TN.attn_fwd(q3, H, mask, causal, dropout=drop, rng=st, Hkv=Hkv)
+                out, lse = TN.attn_fwd(q3, H, mask, causal, dropout=drop, rng=st, Hkv=Hkv, window=window)
                 return out.reshape(B * T, -1), ("native", out, lse, drop, st)
-            out, lse = TN.attn_fwd(q3, H, mask, causal, Hkv=Hkv)
+            out, lse = TN.attn_fwd(q3, H, mask, causal, Hkv=Hkv, window=window)
             return out.reshape(B * T, -1), ("native", out, lse)
     if qkv.is_cuda:
         from ...ops import fallback
         fallback.record("attention",
                         f"head size {qkv.shape[-1] // (H + 2 * Hkv)} / dtype {qkv.dtype}: explicit torch path")
     keep = owner.dropoutKeep("attention", (B, H, T, T), drop, qkv) if drop > 0.0 else None
-    o, ctx = TN.attention_fwd_explicit(qkv.reshape(B, T, -1), H, mask, causal, keep=keep, Hkv=Hkv)
+    o, ctx = TN.attention_fwd_explicit(qkv.reshape(B, T, -1), H, mask, causal, keep=keep, Hkv=Hkv, window=window)
     return o.reshape(B * T, -1), ("explicit", ctx)
 
 
-def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx, Hkv=None):
+def _attn_bwd(dctx, qkv, B, T, H, mask, causal, ctx, Hkv=None, window=None):
     from ...ops import transformer_native as TN
     if ctx[0] == "native":
         kw = dict(dropout=ctx[3], rng=ctx[4]) if len(ctx) > 3 else {}
         return TN.attn_bwd(qkv.reshape(B, T, -1), ctx[1], ctx[2], dctx.reshape(B, T, -1), H, mask,
-                           causal, Hkv=Hkv, **kw).reshape(B * T, -1)
+                           causal, Hkv=Hkv, window=window, **kw).reshape(B * T, -1)
     return TN.attention_bwd_explicit(ctx[1], dctx.reshape(B, T, -1), qkv.dtype).reshape(B * T, -1)
 
 
@@ -496,7 +496,7 @@ class KVCacheState:
         self._kv = new
         self._kv_alt = None         # the second buffer follows the new capacity at the next rnnReorderState
 
-    def cachedAttention(self, qkv, H, what="rnnTimeStep", Hkv=None, ropeTheta=None):
+    def cachedAttention(self, qkv, H, what="rnnTimeStep", Hkv=None, ropeTheta=None, window=None):
         """Causal attention of the chunk qkv [mb, Tn, 3E] ([mb, Tn, E + 2*Ekv] with ``Hkv`` key/value heads, which
         are what the cache then holds) over everything seen since rnnClearPreviousState(): its K / V
         are appended to the cache, its queries attend over the cache. -> [mb, Tn, E]. The decode kernels on a GPU in
@@ -504,7 +504,10 @@ class KVCacheState:
         cache), else the torch reference, counted as a fallback on a GPU. With the fp8 cache both paths store the
         quantised rows and attend over the dequantised cache, except for that prompt chunk.
         ``ropeTheta`` (a rotary layer): Q and K are rotated by their cache row index pos - short[b] + t, on the
-        kernels by the append launch itself (``attn_rope_append``), so the cache holds rotated keys."""
+        kernels by the append launch itself (``attn_rope_append``), so the cache holds rotated keys.
+        ``window`` (the layer's ``attentionWindow``): a query at position p sees keys p - window < k <= p. The cache
+        still keeps every row; the decode kernel skips the key blocks before the window, so a step reads
+        O(window) rows whatever the cache holds."""
         from ...ops import transformer_native as TN
         mb, Tn, E3 = qkv.shape
         Hkv = H if Hkv is None else Hkv
@@ -525,9 +528,9 @@ class KVCacheState:
                 TN.attn_rope_append(qkv, kv, H, pos, ropeTheta, short, Hkv=Hkv)
             if done is not None:
                 if pos == 0 and Tn >= 64:
-                    out = TN.attn_fwd(qkv, H, None, True, Hkv=Hkv)[0]
+                    out = TN.attn_fwd(qkv, H, None, True, Hkv=Hkv, window=window)[0]
                 else:
-                    out = TN.attn_decode(qkv, kv, H, pos, short=short, Hkv=Hkv)
+                    out = TN.attn_decode(qkv, kv, H, pos, short=short, Hkv=Hkv, window=window)
         if out is None:
             if qkv.is_cuda:
                 from ...ops import fallback
@@ -547,7 +550,7 @@ class KVCacheState:
             else:
                 seen = TN.kv_fp8_dequantize_reference(kv[:, :pos + Tn], Hkv, D, qkv.dtype)
             out = TN.attention_decode_reference(qkv[:, :, :E], seen[:, :, :Ekv], seen[:, :, Ekv:], H, pos, short=short,
-                                                Hkv=Hkv)
+                                                Hkv=Hkv, window=window)
         if not self._kv_pinned:                  # pinned: the bound stays, the network lowers ``short`` on the device
             self._kv_len = pos + Tn
         return out
@@ -640,7 +643,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
         if c.rotary():                          # the rotated qkv is what the attention reads and backward keeps
             qkv = _rope(qkv, B, T, H, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer")
-        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads())
+        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads(), c.attentionWindow)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, ln1, a, d1 = _ln_fwd_drop(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps, ph, self,
                                       "hidden1")
@@ -693,7 +696,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         qkv = matmul(n1, self.W("Wqkv"), bias=self.Wbias("bqkv"))
         if c.rotary():
             qkv = _rope(qkv, B, T, H, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer")
-        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads())
+        ctx, actx = _attn_fwd(qkv, B, T, H, m, c.causal, pa, self, c.kvHeads(), c.attentionWindow)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         d1 = d2 = None
         if ph > 0.0:
@@ -731,7 +734,8 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         else:
             qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
         ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads, Hkv=c.kvHeads(),
-                                   ropeTheta=c.ropeTheta if c.rotary() else None).reshape(B * T, -1)
+                                   ropeTheta=c.ropeTheta if c.rotary() else None,
+                                   window=c.attentionWindow).reshape(B * T, -1)
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         if c.preNorm():
             n2, h, _ = _rms_fwd(a, xt, self.params["ln2g"], c.layerNormEps, s_out=a)
@@ -779,7 +783,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
             _bsum(g["bo"], da)
         _wgrad(g["Wo"], ctx, da)
         dctx = matmul(da, self.W("Wo").t())
-        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads())
+        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads(), c.attentionWindow)
         if c.rotary():                          # the transposed rotation takes dQ | dK back to the projection's output
             dqkv = _rope(dqkv, B, T, c.nHeads, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer", inverse=True)
         _wgrad(g["Wqkv"], xt, dqkv)
@@ -815,7 +819,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
             _bsum(g["bo"], da)
         _wgrad(g["Wo"], ctx, da)
         dctx = matmul(da, self.W("Wo").t())
-        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads())
+        dqkv = _attn_bwd(dctx, qkv, B, T, c.nHeads, m, c.causal, actx, c.kvHeads(), c.attentionWindow)
         if c.rotary():
             dqkv = _rope(dqkv, B, T, c.nHeads, c.kvHeads(), c.ropeTheta, "TransformerEncoderLayer", inverse=True)
         _wgrad(g["Wqkv"], n1, dqkv)

@@ -29,7 +29,14 @@
             spread stands next to the ratio), Hkv in {12, 4}, batch 1 and 32, both cache formats. (b) ``attn_rope``
             alone at B = 32, T in {128, 512}: time and bytes per second (it reads and writes the Q and K columns once).
 
+  --window W[,W..]  sliding-window decode (``attn_decode(..., window=W)``), 12 query heads of 64, Tn = 1, bf16, batch
+            1 and 32, 12 and 4 key/value heads, 16-bit and fp8 cache, default splits: 4096 cached keys with each
+            window against the kernel without a window at 4096 keys, and against the kernel without a window over a
+            cache of W keys, which reads the same bytes and is the yardstick (ratio 1 = the window costs nothing
+            beyond the keys it reads). All variants alternate within every pass.
+
 Usage: python tools/bench_decode.py --kernel --model [--out profiles/decode_attention.txt]
+       python tools/bench_decode.py --window 1024,256 [--out FILE]
        python tools/bench_decode.py --cache fp8 [--parent-lib PATH] [--out FILE]
        python tools/bench_decode.py --kv-heads 4,1 [--parent-lib PATH] [--out FILE]
        python tools/bench_decode.py --rotary [--parent-lib PATH] [--out FILE]"""
@@ -284,6 +291,58 @@ def gqa_mode(kv_heads, passes, reps, parent_lib):
     say()
 
 
+def window_mode(windows, passes, reps):
+    """Tn = 1 over 4096 cached keys with a window against no window, and against no window over W keys."""
+    dev, dt = torch.device("cuda", 0), torch.bfloat16
+    H, D, L = 12, 64, 4096
+    E = H * D
+    say(f"== sliding-window decode, H = {H} query heads of {D}, Tn = 1, bf16, default splits S, GPU time per call in us "
+        f"(mean of {reps} back-to-back launches; median of {passes} passes, min .. max; all variants alternate within "
+        "a pass)")
+    say(f"   full = no window over {L} keys; W = window W over {L} keys; short = no window over a cache of W keys (the "
+        "same bytes read: the yardstick); W / short = ratio of the medians, full / W = the gain")
+    for B in (1, 32):
+        for Hkv in (12, 4):
+            for fp8 in (False, True):
+                Ekv = Hkv * D
+                R = TN.kv_fp8_row_bytes(Hkv, D) if fp8 else 2 * Ekv
+
+                def cache(n):
+                    g = torch.Generator().manual_seed(n + B + Hkv)
+                    qkv = (torch.randn(B, 1, E + 2 * Ekv, generator=g) * 0.8).to(dt).to(dev)
+                    hist = (torch.randn(B, n, E + 2 * Ekv, generator=g) * 0.8).to(dt).to(dev)
+                    kv = torch.zeros(B, (n + 63) // 64 * 64, R, dtype=torch.uint8 if fp8 else dt, device=dev)
+                    assert TN.attn_kv_append(hist, kv, H, 0, Hkv=Hkv) is kv
+                    return qkv, kv
+
+                qkv, kv = cache(L)
+                variants = [("full", TN.attn_decode_splits(B, 1, H, D, L, Hkv=Hkv),
+                             lambda q=qkv, c=kv: TN.attn_decode(q, c, H, L - 1, Hkv=Hkv))]
+                for W in windows:
+                    qs, ks = cache(W)
+                    variants.append((f"W={W}", TN.attn_decode_splits(B, 1, H, D, L, Hkv=Hkv, window=W),
+                                     lambda q=qkv, c=kv, w=W: TN.attn_decode(q, c, H, L - 1, Hkv=Hkv, window=w)))
+                    variants.append((f"short={W}", TN.attn_decode_splits(B, 1, H, D, W, Hkv=Hkv),
+                                     lambda q=qs, c=ks, w=W: TN.attn_decode(q, c, H, w - 1, Hkv=Hkv)))
+                for v in variants:
+                    assert v[2]() is not None
+                t = [[] for _ in variants]
+                for _ in range(passes):
+                    for i, v in enumerate(variants):
+                        t[i].append(gpu_time(v[2], reps=reps, warmup=3) * 1e3)
+                med = {}
+                head = f"B={B:2d} Hkv={Hkv:2d} {'fp8   ' if fp8 else '16-bit'}"
+                for (name, S, _), ti in zip(variants, t):
+                    m, lo, hi = _stats(ti)
+                    med[name] = m
+                    line = f"{head} {name:10s} S={S:2d}: {m:7.2f} ({lo:.2f} .. {hi:.2f}) us, spread {(hi - lo) / m * 100:4.1f} %"
+                    if name.startswith("short="):
+                        w = name[6:]
+                        line += f"  W / short {med['W=' + w] / m:5.3f}  full / W {med['full'] / med['W=' + w]:5.2f}x"
+                    say(line)
+    say()
+
+
 def rotary_mode(passes, reps, parent_lib):
     import ctypes
     from deeplearning4j_amd.ops import native
@@ -413,12 +472,18 @@ def main():
                          "with the 12-head row")
     ap.add_argument("--rotary", action="store_true",
                     help="rotary embeddings: the fused rotate-and-append against the plain append, and attn_rope alone")
+    ap.add_argument("--window", default=None,
+                    help="comma-separated windows: the windowed decode at 4096 keys against no window and against "
+                         "no window over W keys")
     ap.add_argument("--parent-lib", default=None,
                     help="--cache / --kv-heads / --rotary: kernel library built from the parent commit")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args()
-    if not (a.kernel or a.model or a.cache or a.kv_heads or a.rotary):
-        ap.error("give --kernel, --model, --cache fp8, --kv-heads N and / or --rotary")
+    if not (a.kernel or a.model or a.cache or a.kv_heads or a.rotary or a.window):
+        ap.error("give --kernel, --model, --cache fp8, --kv-heads N, --rotary and / or --window W")
+    windows = [int(w) for w in a.window.split(",")] if a.window else []
+    if any(w < 1 for w in windows):
+        ap.error("--window: every window must be a positive integer")
     kv_heads = [int(h) for h in a.kv_heads.split(",")] if a.kv_heads else []
     if any(h < 1 or 12 % h for h in kv_heads):
         ap.error("--kv-heads: every count must divide the 12 query heads")
@@ -438,6 +503,8 @@ def main():
         gqa_mode(kv_heads, max(a.passes, 5), a.reps, a.parent_lib)
     if a.rotary:
         rotary_mode(max(a.passes, 5), a.reps, a.parent_lib)
+    if windows:
+        window_mode(windows, max(a.passes, 5), a.reps)
     if _out is not None:
         _out.close()
 

@@ -44,13 +44,18 @@
   --block llama  Llama-style blocks (RMSNorm, pre-norm, SwiGLU with ffnSize 2048) against post-LayerNorm GELU blocks
              (ffnSize 3072, the same parameter count) on the rotary 12-layer, hidden-768 model: the rows of --rotary.
 
+  --window W  sliding-window attention (attentionWindow = W in every block) against none on the rotary 12-layer,
+             hidden-768 model: generate() and generate(useGraph=True) at prefix 1024 and 4032, and a causal-LM
+             training step of batch 32 at 2048 tokens.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
        python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]
        python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]
        python tools/bench_generate.py --kv-heads 4 [--batch 32] [--out FILE]
        python tools/bench_generate.py --rotary [--positions learned] [--tree PATH] [--out FILE]
-       python tools/bench_generate.py --block llama [--out FILE]"""
+       python tools/bench_generate.py --block llama [--out FILE]
+       python tools/bench_generate.py --window 256 --batch 32 [--out FILE]"""
 import argparse
 import sys
 import time
@@ -563,12 +568,32 @@ def block_mode(batches, n, passes):
     _compare_models(nets, kinds, V, batches, n, passes)
 
 
-def _compare_models(nets, kinds, V, batches, n, passes):
-    """generate() eager and graph-replayed at prefix 128 and 1024, then a training step, of the models ``nets`` (by
-    kind, the first the base line), the variants alternating within a pass."""
+def window_mode(window, batches, n, passes):
+    """--window W: sliding-window attention in every block against none on the 12-layer, hidden-768 rotary model:
+    generate() eager and graph-replayed at prefix 1024 and 4032, and a causal-LM training step at 2048 tokens."""
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, H, E = 77, 12, 768
+    kinds = ["full", "window"]
+    nets = {k: TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=E, layers=12, heads=H,
+                                         dataType=DataType.BFLOAT16, positionEncoding="rotary",
+                                         attentionWindow=window if k == "window" else None).init(device=DEV)
+            for k in kinds}
+    say(f"== generate() with attentionWindow = {window} in every block against no window on "
+        f"TextGenerationTransformer(768, 12 layers, 12 heads, rotary), bf16, V = {V}, greedy, {n} new tokens; whole "
+        f"calls (prompt included) on the host clock, ended by a device synchronise; median of {passes} passes "
+        "(min .. max), the variants alternating within a pass; x = tokens/s against the model without a window, same "
+        "mode")
+    _compare_models(nets, kinds, V, batches, n, passes, prefixes=(1024, 4032), train=(32, 2048, 3))
+
+
+def _compare_models(nets, kinds, V, batches, n, passes, prefixes=(128, 1024), train=(32, 128, 10)):
+    """generate() eager and graph-replayed at the ``prefixes``, then a training step of ``train`` = (batch, tokens,
+    steps per timing), of the models ``nets`` (by kind, the first the base line), the variants alternating within a
+    pass."""
     say("   parameters: " + ", ".join(f"{k} {nets[k].numParams()}" for k in kinds))
     for mb in batches:
-        for P in (128, 1024):
+        for P in prefixes:
             prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb + P)).to(DEV)
             variants = [(f"{k:7s} {mode}", nets[k], kw)
                         for mode, kw in (("eager", {}), ("graph", dict(useGraph=True))) for k in kinds]
@@ -598,7 +623,7 @@ def _compare_models(nets, kinds, V, batches, n, passes):
     for net in nets.values():
         net.rnnClearPreviousState()
     say()
-    B, T, steps = 32, 128, 10
+    B, T, steps = train
     say(f"== one causal-LM training step (fit) of the same models, batch {B}, {T} tokens, bf16: ms per step on the host "
         f"clock over {steps} steps ended by a device synchronise; median of {passes} passes (min .. max), alternating")
     g = torch.Generator().manual_seed(1)
@@ -606,16 +631,16 @@ def _compare_models(nets, kinds, V, batches, n, passes):
     y = torch.zeros(B, V, T, device=DEV)
     y.scatter_(1, torch.randint(0, V, (B, 1, T), generator=g).to(DEV), 1.0)
 
-    def train(net):
+    def fit(net):
         for _ in range(steps):
             net.fit([x], [y])
 
     for k in kinds:
-        train(nets[k])
+        fit(nets[k])
     tt = {k: [] for k in kinds}
     for _ in range(passes):
         for k in kinds:
-            tt[k].append(_sync_time(lambda: train(nets[k])) / steps * 1e3)
+            tt[k].append(_sync_time(lambda: fit(nets[k])) / steps * 1e3)
     base = sorted(tt[kinds[0]])[passes // 2]
     for k in kinds:
         t = sorted(tt[k])
@@ -641,6 +666,9 @@ def main():
                     help="--rotary: the models to measure")
     ap.add_argument("--block", choices=["llama"], default=None,
                     help="Llama-style blocks against post-LayerNorm GELU blocks: generate(), useGraph=True, training")
+    ap.add_argument("--window", type=int, default=None,
+                    help="sliding-window attention (attentionWindow in every block) against none: generate(), "
+                         "useGraph=True at prefix 1024 and 4032, a training step at 2048 tokens")
     ap.add_argument("--tree", default=None, help="import the package from this checkout instead of the tool's own")
     ap.add_argument("--parent-lib", default=None,
                     help="kernel library built from the parent commit (--ragged, --graph)")
@@ -672,6 +700,8 @@ def main():
         rotary_mode(a.batch, a.tokens, a.passes, a.positions)
     if a.block:
         block_mode(a.batch, a.tokens, a.passes)
+    if a.window:
+        window_mode(a.window, a.batch, a.tokens, a.passes)
 
 
 if __name__ == "__main__":
