@@ -24,6 +24,12 @@
 //     glds writes lane-linearly, so the swizzle is applied on the per-lane SOURCE address and undone on the read.
 //   * XCD-aware, grouped block raster (consecutive block ids of one XCD share A row panels in its L2).
 //   * split-K over grid.y: fp32 partial slabs + a deterministic fixed-order reduce kernel that applies the epilogue.
+//   * grouped modes (mixture-of-experts feed-forward, csrc/moe.hip), template parameter GRP, no split-K:
+//       GRP 1  every 128-row tile of A / C belongs to one expert read from a device-side tile map: the block takes
+//              that expert's B matrix (batch stride sB) and bias row; a tile mapped to -1 returns at once
+//       GRP 2  one batch per expert over a shared [rows, M] x [rows, N] operand pair: the K range of batch e is
+//              [off[e], off[e] + cnt[e]), read on the device (the per-expert weight gradient)
+//     GemmArgs has no field of its own for them: ws carries the int32 tile map (GRP 1) or off (GRP 2), Z carries cnt.
 // gemm_simple (any dtype incl. fp32, any strides / shapes / alignment)
 //   * 64 x 64 x 16 tile, operands converted to fp32 in LDS, exact-fp32 v_mfma_f32_32x32x2_f32; used for fp32
 //     networks and for shapes the fast kernel's 16-byte DMA cannot address.
@@ -62,7 +68,7 @@ constexpr int glds_smem(int BM, int BN, int STAGES) {
   return cmax(STAGES * (BM + BN) * 128, cmax(BM * BN * 2, 64 * (BN * 4 + 16)));
 }
 
-template <int DT, int BM, int BN, int WGM, int WGN, bool AKC, bool BKC, int STAGES, bool LEAN = false>
+template <int DT, int BM, int BN, int WGM, int WGN, bool AKC, bool BKC, int STAGES, bool LEAN = false, int GRP = 0>
 __global__ __launch_bounds__(WGM* WGN * 64, (STAGES == 1 && WGM * WGN == 4 ? 4 : 2)) void gemm_glds(GemmArgs g) {
   constexpr int NW = WGM * WGN;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
@@ -82,11 +88,24 @@ __global__ __launch_bounds__(WGM* WGN * 64, (STAGES == 1 && WGM * WGN == 4 ? 4 :
   const int tm = first_m + in_g % gsz, tn = in_g / gsz;
   const int m0 = tm * BM, n0 = tn * BN;
   const int z = blockIdx.y, bz = blockIdx.z;
-  const int kbeg = z * g.kps;
-  const int kend = min(g.K, kbeg + g.kps);
+  typedef unsigned short E;
+  if constexpr (GRP == 1) {
+    // the row tile's expert (block-uniform, read before any barrier): its B matrix and bias row, or nothing to do
+    static_assert(BM == 128, "the grouped row tile is dl4j_moe_row_tile() = 128");
+    const int ex = reinterpret_cast<const int*>(g.ws)[tm];
+    if (ex < 0) return;
+    g.B = reinterpret_cast<const E*>(g.B) + (long long)ex * g.sB;
+    if (g.bias_mode == 1) g.bias += (long long)ex * g.N;
+  }
+  int kb_ = z * g.kps, ke_ = min(g.K, kb_ + g.kps);
+  if constexpr (GRP == 2) {            // batch bz = expert: its live rows are the K range, pad rows never enter
+    kb_ = reinterpret_cast<const int*>(g.ws)[bz];
+    ke_ = kb_ + reinterpret_cast<const int*>(g.Z)[bz];
+  }
+  const int kbeg = kb_;
+  const int kend = ke_;
   const int nk = (kend - kbeg + 63) / 64;
 
-  typedef unsigned short E;
   const E* A = reinterpret_cast<const E*>(g.A) + (long long)bz * g.sA;
   const E* B = reinterpret_cast<const E*>(g.B) + (long long)bz * g.sB;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -247,7 +266,8 @@ __global__ __launch_bounds__(WGM* WGN * 64, (STAGES == 1 && WGM * WGN == 4 ? 4 :
                 : reinterpret_cast<char*>(g.C) + (long long)bz * g.sC * (g.out_dt == 0 ? 4 : 2);
   o.ld = split ? g.N : g.ldc;
   o.vec = split ? ((g.N & 3) == 0) : (g.coalesce != 0);
-  void* Zp = (!split && g.Z) ? reinterpret_cast<char*>(g.Z) + (long long)bz * g.sC * (g.out_dt == 0 ? 4 : 2) : nullptr;
+  void* Zp = (GRP == 0 && !split && g.Z) ? reinterpret_cast<char*>(g.Z) + (long long)bz * g.sC * (g.out_dt == 0 ? 4 : 2)
+                                        : nullptr;
   wait_vm<0>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   raw_barrier();
@@ -1175,5 +1195,93 @@ DL4J_API int dl4j_gemm_simple(int in_dt, int out_dt, int M, int N, int K, int ba
   sa.bA = sA; sa.bB = sB; sa.bC = sC; sa.in_dt = in_dt;
   const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
   hipLaunchKernelGGL(gemm_simple, dim3(tiles, 1, batch), dim3(256), 0, s, g, sa);
+  return (int)hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------------------- grouped GEMM
+// The mixture-of-experts feed-forward (csrc/moe.hip): rows sorted by expert in segments padded to the 128-row tile,
+// described by a device-side plan, so the launch geometry depends on shapes only and nothing is read back.
+namespace {
+
+constexpr int kGrpTile = 128;        // = dl4j_moe_row_tile(): the BM of the one tile configuration used below
+
+inline bool grp_al(const void* p, uintptr_t a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+template <int DT, bool BKC, bool LEAN>
+int launch_grouped(const GemmArgs& g, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_glds<DT, 128, 128, 2, 2, true, BKC, 2, LEAN, 1>), dim3(g.tiles_m * g.tiles_n, 1, 1),
+                     dim3(256), 0, s, g);
+  return (int)hipGetLastError();
+}
+
+template <int DT>
+int launch_grouped_dt(const GemmArgs& g, bool bkc, bool lean, hipStream_t s) {
+  if (bkc) return lean ? launch_grouped<DT, true, true>(g, s) : launch_grouped<DT, true, false>(g, s);
+  return lean ? launch_grouped<DT, false, true>(g, s) : launch_grouped<DT, false, false>(g, s);
+}
+
+}  // namespace
+
+// C[r, :] = A[r, :] . B_e + bias_e with e = tile_expert[r / 128], for the R rows (a multiple of 128) of A [R, K]
+// (row stride lda) and C [R, N] (row stride ldc), both in `dtype` (1 bf16, 2 fp16; fp32 accumulation). B_e starts
+// sB elements after B_{e-1} and is K-contiguous (bkc = 1: B_e(k, n) = B[n*ldb + k]) or N-contiguous (bkc = 0:
+// B[k*ldb + n]); bias is fp32 [X, N] or null. A tile with tile_expert = -1 is neither read nor written; every other
+// tile is written whole (its pad rows included). One tile configuration (128 x 128 x 64, two stages), no split-K: a
+// row's bits depend on its own A row and its expert's B only. Returns -1 (nothing launched) for a dtype other than
+// bf16 / fp16, a null or misaligned operand (16 bytes for A / B / C, 4 for bias and the map), R < 128 or R % 128,
+// N, K, lda, ldb, ldc or sB not multiples of 8 (or too small for the shape), X outside 1..64.
+DL4J_API int dl4j_gemm_grouped(int dtype, const void* A, long long lda, const void* B, long long ldb, int bkc,
+                               long long sB, void* C, long long ldc, const float* bias, const int* tile_expert,
+                               long long R, int N, int K, int X, hipStream_t s) {
+  if (dtype != 1 && dtype != 2) return -1;
+  if (!grp_al(A, 16) || !grp_al(B, 16) || !grp_al(C, 16) || !grp_al(tile_expert, 4) || (bias && !grp_al(bias, 4)))
+    return -1;
+  if (R < kGrpTile || R % kGrpTile || R > 0x7fffffffLL - kGrpTile || X < 1 || X > 64) return -1;
+  if (N < 8 || (N & 7) || K < 8 || (K & 7) || (lda & 7) || (ldb & 7) || (ldc & 7) || (sB & 7) || sB < 0) return -1;
+  if (lda < K || ldc < N || ldb < (bkc ? K : N)) return -1;
+  GemmArgs g = {};
+  g.A = A; g.B = B; g.C = C; g.bias = bias;
+  g.ws = reinterpret_cast<float*>(const_cast<int*>(tile_expert));       // GRP 1: the tile map travels in ws
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sB = sB;
+  g.M = (int)R; g.N = N; g.K = K;
+  g.kps = (K + 63) / 64 * 64;
+  g.splits = 1;
+  g.alpha = 1.f; g.bias_mode = bias ? 1 : 0; g.out_dt = dtype;
+  g.store_nt = store_nt_for(R * N * 2);
+  g.coalesce = 1;
+  g.tiles_m = (int)(R / kGrpTile);
+  g.tiles_n = (N + 127) / 128;
+  if ((long long)g.tiles_m * g.tiles_n > 0x7fffffffLL) return -1;
+  const bool lean = lean_ok(g, 1);
+  return dtype == 1 ? launch_grouped_dt<1>(g, bkc != 0, lean, s) : launch_grouped_dt<2>(g, bkc != 0, lean, s);
+}
+
+// dW[e] = Ap[seg_e]^T . Bp[seg_e] for e < X, with seg_e the rows [off[e], off[e] + cnt[e]) of Ap [R, M] (row stride
+// lda) and Bp [R, N] (row stride ldb), off / cnt int32 on the device (off[e] a multiple of 128). dW is fp32
+// [X, M, N] contiguous (4-byte aligned: usually a view into the flat gradient); an empty expert's slab is written
+// with zeros; rows outside the segments are never read. The sum over a segment runs in row order in one block per
+// output tile, so two calls give the same bits. Returns -1 as dl4j_gemm_grouped does (M, N, lda, ldb multiples of 8).
+DL4J_API int dl4j_gemm_grouped_wgrad(int dtype, const void* Ap, long long lda, const void* Bp, long long ldb,
+                                     float* dW, const int* off, const int* cnt, long long R, int M, int N, int X,
+                                     hipStream_t s) {
+  if (dtype != 1 && dtype != 2) return -1;
+  if (!grp_al(Ap, 16) || !grp_al(Bp, 16) || !grp_al(dW, 4) || !grp_al(off, 4) || !grp_al(cnt, 4)) return -1;
+  if (R < kGrpTile || R % kGrpTile || R > 0x7fffffffLL - kGrpTile || X < 1 || X > 64) return -1;
+  if (M < 8 || (M & 7) || N < 8 || (N & 7) || (lda & 7) || (ldb & 7) || lda < M || ldb < N) return -1;
+  GemmArgs g = {};
+  g.A = Ap; g.B = Bp; g.C = dW;
+  g.ws = reinterpret_cast<float*>(const_cast<int*>(off));               // GRP 2: off travels in ws, cnt in Z
+  g.Z = const_cast<int*>(cnt);
+  g.lda = lda; g.ldb = ldb; g.ldc = N; g.sC = (long long)M * N;
+  g.M = M; g.N = N; g.K = (int)R;
+  g.kps = (int)((R + 63) / 64 * 64);
+  g.splits = 1;
+  g.alpha = 1.f; g.out_dt = 0;
+  g.coalesce = ((reinterpret_cast<uintptr_t>(dW) & 15) == 0 && (N & 3) == 0) ? 1 : 0;
+  g.tiles_m = (M + 127) / 128;
+  g.tiles_n = (N + 127) / 128;
+  const dim3 grid(g.tiles_m * g.tiles_n, 1, X);
+  if (dtype == 1) hipLaunchKernelGGL((gemm_glds<1, 128, 128, 2, 2, false, false, 2, false, 2>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_glds<2, 128, 128, 2, 2, false, false, 2, false, 2>), grid, dim3(256), 0, s, g);
   return (int)hipGetLastError();
 }

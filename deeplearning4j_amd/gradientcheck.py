@@ -38,9 +38,10 @@ def _clip_off(net):
 
 def checkGradients(net, epsilon=1e-6, maxRelError=1e-3, minAbsoluteError=1e-8, print_results=False,
                    exitOnFirstError=False, input=None, labels=None, inputMask=None, labelMask=None,
-                   subset=None, seed=12345):
+                   subset=None, seed=12345, indices=None):
     """MultiLayerNetwork or ComputationGraph. ``input``/``labels`` may be lists for graphs.
-    ``subset``: if set, check at most that many randomly chosen parameters (large nets)."""
+    ``subset``: if set, check at most that many randomly chosen parameters (large nets). ``indices``: if set, check
+    exactly these positions of the flat parameter vector (``paramIndices`` gives those of a layer's tensor)."""
     _check_net(net)
     _clip_off(net)
     is_graph = hasattr(net, "topo")
@@ -65,7 +66,9 @@ def checkGradients(net, epsilon=1e-6, maxRelError=1e-3, minAbsoluteError=1e-8, p
     params = net.flattenedParams
     n = params.numel()
     idx = range(n)
-    if subset is not None and subset < n:
+    if indices is not None:
+        idx = sorted(int(i) for i in indices)
+    elif subset is not None and subset < n:
         g = torch.Generator().manual_seed(seed)
         idx = sorted(torch.randperm(n, generator=g)[:subset].tolist())
     total_fail = 0
@@ -95,6 +98,18 @@ def checkGradients(net, epsilon=1e-6, maxRelError=1e-3, minAbsoluteError=1e-8, p
         print(f"GradientCheck: {len(list(idx)) if not isinstance(idx, range) else n} params, {total_fail} failed, "
               f"max rel error {worst:.3e}")
     return total_fail == 0
+
+
+def paramIndices(net, layer, key):
+    """The positions in the flat parameter vector of parameter ``key`` of the layer named (or indexed) ``layer``."""
+    for idx, name, impl, off in net._layer_offsets:
+        if layer in (idx, name):
+            o = off
+            for spec in impl.conf.param_specs():
+                if spec.key == key:
+                    return list(range(o, o + spec.numel))
+                o += spec.numel
+    raise KeyError(f"no parameter {key!r} in layer {layer!r}")
 
 
 def _param_names(net):

@@ -973,7 +973,7 @@ class TextGenerationTransformer(ZooModel):
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
                  maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, positionEncoding=None,
                  ropeTheta=10000.0, normalization="layer", normPlacement="post", ffnActivation="gelu",
-                 attentionWindow=None, **kw):
+                 attentionWindow=None, nExperts=None, nExpertsPerToken=2, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         self.ffn = int(ffn) if ffn else 4 * hidden
@@ -989,6 +989,22 @@ class TextGenerationTransformer(ZooModel):
         # sliding-window attention: None, a positive integer for every block, or a sequence with one entry per block
         # (None = full attention in that block; Gemma alternates the two)
         self.attentionWindow = attentionWindow
+        # mixture-of-experts feed-forward: None (dense blocks), the number of experts of every block, or a sequence
+        # with one entry per block (None = a dense block); nExpertsPerToken of them run on a token
+        self.nExperts, self.nExpertsPerToken = nExperts, nExpertsPerToken
+
+    def blockExperts(self):
+        """``nExperts`` as a list with one entry (None or the number of experts) per block."""
+        x = self.nExperts
+        if x is None or isinstance(x, (int, float)):
+            return [x] * self.layers
+        x = list(x)
+        if len(x) != self.layers:
+            from ..exceptions import DL4JInvalidConfigException
+            raise DL4JInvalidConfigException(
+                f"TextGenerationTransformer: nExperts has {len(x)} entries for {self.layers} blocks; give one "
+                "count (or None) per block, or a single value for all of them")
+        return x
 
     def blockWindows(self):
         """``attentionWindow`` as a list with one entry (None or the window) per block."""
@@ -1005,7 +1021,7 @@ class TextGenerationTransformer(ZooModel):
 
     def graphBuilder(self):
         from ..nn.conf import BertEmbeddingLayer, RMSNormalization, TransformerEncoderLayer
-        windows = self.blockWindows()
+        windows, experts = self.blockWindows(), self.blockExperts()
         g = (self._builder().updater(Adam(self.learningRate)).weightInit(NormalDistribution(0.0, 0.02))
              .graphBuilder())
         g.addInputs("tokens")
@@ -1014,12 +1030,15 @@ class TextGenerationTransformer(ZooModel):
                    .positionEmbeddings(self.positionEncoding is None).build(), "tokens")
         prev = "embeddings"
         for i in range(self.layers):
-            g.addLayer(f"decoder_{i}", TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
-                       .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
-                       .nKVHeads(self.nKVHeads).positionEncoding(self.positionEncoding)
-                       .ropeTheta(self.ropeTheta).normalization(self.normalization)
-                       .normPlacement(self.normPlacement).ffnActivation(self.ffnActivation)
-                       .attentionWindow(windows[i]).build(), prev)
+            b = (TransformerEncoderLayer.Builder().nIn(self.hidden).nOut(self.hidden)
+                 .nHeads(self.heads).ffnSize(self.ffn).causal(True).cacheDataType(self.cacheDataType)
+                 .nKVHeads(self.nKVHeads).positionEncoding(self.positionEncoding)
+                 .ropeTheta(self.ropeTheta).normalization(self.normalization)
+                 .normPlacement(self.normPlacement).ffnActivation(self.ffnActivation)
+                 .attentionWindow(windows[i]))
+            if experts[i] is not None:                  # a dense block keeps nExpertsPerToken at its default
+                b = b.nExperts(experts[i]).nExpertsPerToken(self.nExpertsPerToken)
+            g.addLayer(f"decoder_{i}", b.build(), prev)
             prev = f"decoder_{i}"
         if self.normPlacement == "pre":
             g.addLayer("final_norm", RMSNormalization.Builder().nIn(self.hidden).nOut(self.hidden).build(), prev)

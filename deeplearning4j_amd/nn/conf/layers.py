@@ -1477,6 +1477,28 @@ def _check_position_encoding(layer, headSize=None):
             f"{headSize}")
 
 
+def _check_experts(layer):
+    """``nExperts``: None (the default: the dense feed-forward) or an integer 1..64, the feed-forward networks of a
+    sparse mixture-of-experts block; ``nExpertsPerToken``: the k of them a token's router picks (default 2,
+    1 <= k <= min(nExperts, 8)). k away from its default without ``nExperts`` is refused."""
+    x, k = layer.nExperts, layer.nExpertsPerToken
+    integer = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    if x is not None and not (integer(x) and 1 <= x <= MAX_EXPERTS):
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: nExperts is None (a dense feed-forward) or an integer in 1..{MAX_EXPERTS}, got {x!r}")
+    if x is None:
+        if k != 2:
+            raise DL4JInvalidConfigException(
+                f"{_who(layer)}: nExpertsPerToken = {k!r} needs nExperts; a dense feed-forward has no router")
+        return
+    if not (integer(k) and 1 <= k <= min(x, MAX_EXPERTS_PER_TOKEN)):
+        raise DL4JInvalidConfigException(
+            f"{_who(layer)}: nExpertsPerToken must be an integer in 1..min(nExperts, {MAX_EXPERTS_PER_TOKEN}) = "
+            f"{min(x, MAX_EXPERTS_PER_TOKEN)}, got {k!r}")
+
+
+MAX_EXPERTS = 64
+MAX_EXPERTS_PER_TOKEN = 8
 NORMALIZATIONS = ("layer", "rms")
 NORM_PLACEMENTS = ("post", "pre")
 FFN_ACTIVATIONS = ("gelu", "swiglu")
@@ -1617,13 +1639,20 @@ class TransformerEncoderLayer(FeedForwardLayer):
     layer. The other two combinations are refused.
 
     ``ffnActivation``: "gelu" (the default) or "swiglu": the gated feed-forward ``W2(silu(x Wg) * (x Wu))``
-    (csrc/swiglu.hip) with ``W1 = [Wg | Wu]`` of shape [nIn, 2*ffnSize]; it works in either block."""
+    (csrc/swiglu.hip) with ``W1 = [Wg | Wu]`` of shape [nIn, 2*ffnSize]; it works in either block.
+
+    ``nExperts`` / ``nExpertsPerToken``: None (the default: the dense feed-forward above) or X in 1..64: a sparse
+    mixture-of-experts feed-forward (Mixtral's contract). A router ``Wr [nIn, X]`` (no bias) scores every token, the
+    k = ``nExpertsPerToken`` (default 2, at most min(X, 8)) experts with the largest logits (ties: the lower index)
+    run on it and their outputs are summed with the softmax of the k chosen logits as weights; no token is dropped.
+    ``W1 [X*nIn, F1]``, ``b1 [X, F1]``, ``W2 [X*ffnSize, nIn]``, ``b2 [X, nIn]`` hold the experts one after another
+    (csrc/moe.hip and the grouped mode of csrc/gemm.hip). Works with either ``ffnActivation`` and either block."""
     FIELDS = {"nHeads": 12, "ffnSize": 3072, "layerNormEps": 1e-12, "causal": False, "hiddenDropout": 0.0,
               "attentionDropout": 0.0, "cacheDataType": None, "nKVHeads": None, "positionEncoding": None,
               "ropeTheta": 10000.0, "normalization": "layer", "normPlacement": "post", "ffnActivation": "gelu",
-              "attentionWindow": None}
+              "attentionWindow": None, "nExperts": None, "nExpertsPerToken": 2}
     _OMIT_AT_DEFAULT = ("cacheDataType", "nKVHeads", "positionEncoding", "ropeTheta", "normalization",
-                        "normPlacement", "ffnActivation", "attentionWindow")
+                        "normPlacement", "ffnActivation", "attentionWindow", "nExperts", "nExpertsPerToken")
     RUNTIME = "deeplearning4j_amd.nn.layers.transformer:TransformerEncoderLayerImpl"
 
     def _post_init(self):
@@ -1635,6 +1664,7 @@ class TransformerEncoderLayer(FeedForwardLayer):
         self._check_rope()
         _check_block_style(self)
         _check_attention_window(self)
+        _check_experts(self)
 
     def preNorm(self):
         return self.normPlacement == "pre"
@@ -1675,6 +1705,13 @@ class TransformerEncoderLayer(FeedForwardLayer):
                  ParamSpec("W1", [E, F1], "c", "weight", E, F), ParamSpec("b1", [1, F1], "c", "bias"),
                  ParamSpec("W2", [F, E], "c", "weight", F, E), ParamSpec("b2", [1, E], "c", "bias"),
                  ParamSpec("ln2g", [1, E], "c", "const", value=1.0), ParamSpec("ln2b", [1, E], "c", "const", value=0.0)]
+        if self.nExperts is not None:                            # the experts one after another, fans per expert
+            X = self.nExperts
+            moe = {"W1": ParamSpec("W1", [X * E, F1], "c", "weight", E, F), "b1": ParamSpec("b1", [X, F1], "c", "bias"),
+                   "W2": ParamSpec("W2", [X * F, E], "c", "weight", F, E), "b2": ParamSpec("b2", [X, E], "c", "bias")}
+            specs = [moe.get(p.key, p) for p in specs]
+            at = [p.key for p in specs].index("W1")
+            specs.insert(at, ParamSpec("Wr", [E, X], "c", "weight", E, X))
         if self.normalization == "rms":                          # no mean, no beta
             specs = [p for p in specs if p.key not in ("ln1b", "ln2b")]
         return specs

@@ -46,6 +46,14 @@ add rides on the GEMM in ``rnnTimeStep`` and is one pairwise launch in ``activat
 backward kernel takes the gradient arriving over the residual path as ``dres`` and adds it before the one rounding.
 Hidden dropout uses the stand-alone Philox launches on the two branch outputs.
 
+Mixture-of-experts feed-forward (``nExperts`` on the encoder block): logits = n·Wr in fp32 (n: the feed-forward's input),
+the router picks k experts per token and sorts the (token, choice) assignments by expert on the device (csrc/moe.hip),
+Xp = gather(n), Z1p = Xp·W1[e] + b1[e] and Yp = act(Z1p)·W2[e] + b2[e] on the grouped mode of the GEMM (every 128-row
+tile reads its own expert's matrix), f2[n] = sum_j g_j·Yp[row(n, j)] in fp32 (the last add of a pre-norm ``rnnTimeStep``
+rides on this launch). Backward: the gate gradients by wave dot products, dYp = g·df2 gathered, the per-expert weight
+gradients over the segments' live rows straight into the gradient views, and the router's gradient through the plain
+GEMMs. Every launch is sized by shapes alone and nothing is read back, so a step captures into a graph as it is.
+
 Decoder block (``TransformerDecoderLayerImpl``, a two-input graph layer: decoder stream + encoder memory): causal
 self-attention as above, then cross-attention of q2 = h1·Wq2 over kv2 = memory·Wkv2 (one GEMM straight into the
 kv [mb, Tk, 2E] layout of csrc/attention_cross.hip), then the FFN, each followed by LayerNorm(+residual). Its
@@ -211,6 +219,38 @@ def _swiglu_bwd(z, df):
         if r is not None:
             return r
     return TN.swiglu_backward_reference(z, df)
+
+
+# ------------------------------------------------------------------------------------------------ mixture of experts
+def _moe_op(name, like, *args, **kw):
+    """``ops.transformer_native.<name>`` (csrc/moe.hip, the grouped GEMM) when ``like`` is on a GPU in bf16 / fp16,
+    else (CPU, fp32 / fp64, a refusal) its torch twin ``<name>_reference``, counted as a fallback on a GPU."""
+    from ...ops import transformer_native as TN
+    if _native(like, "moe"):
+        r = getattr(TN, name)(*args, **kw)
+        if r is not None:
+            return r
+    if like.is_cuda:
+        from ...ops import fallback
+        fallback.record("moe", f"{name} dtype {like.dtype}: torch reference path")
+    return getattr(TN, name + "_reference")(*args, **kw)
+
+
+def _moe_bias(b):
+    """An expert bias [X, N] as the grouped GEMM takes it: fp32 (fp64 stays fp64), contiguous."""
+    if b.dtype in (torch.float32, torch.float64):
+        return b.contiguous()
+    return b.to(torch.float32).contiguous()
+
+
+def _moe_grad(view, fn):
+    """``fn(out)`` writes a per-expert gradient into ``out``: the gradient view itself when it is contiguous."""
+    if view.is_contiguous():
+        fn(view)
+    else:
+        tmp = torch.empty(view.shape, dtype=view.dtype, device=view.device)
+        fn(tmp)
+        copy_grad_(view, tmp)
 
 
 def _add_into(a, b):
@@ -647,8 +687,11 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         h1, ln1, a, d1 = _ln_fwd_drop(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps, ph, self,
                                       "hidden1")
-        f, z1 = self._ffn1(h1, True)
-        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        if c.nExperts is None:
+            f, z1 = self._ffn1(h1, True)
+            f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        else:                                   # z1 carries the experts' context
+            f, (f2, z1) = None, self._moe_fwd(h1)
         y, ln2, f2, d2 = _ln_fwd_drop(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps, ph, self,
                                       "hidden2")
         self.maskArray = mask
@@ -668,6 +711,52 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         # FFN-1 with bias + exact GELU fused into the GEMM epilogue; the pre-activation z1 is kept for backward
         z1 = torch.empty(h.shape[0], self.W("W1").shape[1], dtype=h.dtype, device=h.device)
         return matmul(h, self.W("W1"), bias=self.Wbias("b1"), act="gelu", z=z1), z1
+
+    def _moe_fwd(self, n, acc=None):
+        """The sparse feed-forward of n [N, E] -> (f2 [N, E] (+ ``acc``, written over it on the kernels), ctx =
+        (plan, gate, Xp, Z1p, Fp, Yp) for ``_moe_bwd``)."""
+        c = self.conf
+        X, k, E = c.nExperts, c.nExpertsPerToken, n.shape[1]
+        sixteen = n.dtype in (torch.bfloat16, torch.float16)
+        logits = mmul(n, self.W("Wr"), out_dtype=torch.float32 if sixteen else None)
+        plan, gate = _moe_op("moe_route", n, logits, k)
+        W1, W2 = self.W("W1"), self.W("W2")
+        xp = _moe_op("moe_gather", n, n, plan)
+        z1p = _moe_op("gemm_grouped", n, xp, W1.view(X, E, -1), _moe_bias(self.Wbias("b1")), plan)
+        fp = _swiglu_fwd(z1p) if c.swiglu() else _gelu_fwd(z1p)
+        yp = _moe_op("gemm_grouped", n, fp, W2.view(X, -1, E), _moe_bias(self.Wbias("b2")), plan)
+        if acc is not None and _native(n, "moe"):
+            f2 = _moe_op("moe_combine", n, yp, plan, gate, acc, out=acc)
+        else:
+            f2 = _moe_op("moe_combine", n, yp, plan, gate, acc)
+        return f2, (plan, gate, xp, z1p, fp, yp)
+
+    def _moe_bwd(self, df2, n, ctx, acc=None):
+        """-> dn, the gradient of the sparse feed-forward's input (+ ``acc``, the gradient arriving over the residual
+        path, summed in place on the kernels); the gradients of Wr, W1, b1, W2, b2 land in their views."""
+        from ...ops import transformer_native as TN
+        c = self.conf
+        X, E = c.nExperts, n.shape[1]
+        plan, gate, xp, z1p, fp, yp = ctx
+        g = self.grads
+        df2 = df2.to(n.dtype).contiguous()
+        W1, W2 = self.W("W1"), self.W("W2")
+        dgate = _moe_op("moe_combine_bwd", n, df2, yp, plan)
+        dyp = _moe_op("moe_gather", n, df2, plan, gate)
+        _moe_grad(g["W2"], lambda out: _moe_op("gemm_grouped_wgrad", n, fp, dyp, plan, out))
+        _moe_grad(g["b2"], lambda out: _moe_op("moe_segment_colsum", n, dyp, plan, out))
+        dfp = _moe_op("gemm_grouped", n, dyp, W2.view(X, -1, E).transpose(1, 2), None, plan)
+        dz1p = _swiglu_bwd(z1p, dfp) if c.swiglu() else _gelu_bwd(z1p, dfp)
+        _moe_grad(g["W1"], lambda out: _moe_op("gemm_grouped_wgrad", n, xp, dz1p, plan, out))
+        _moe_grad(g["b1"], lambda out: _moe_op("moe_segment_colsum", n, dz1p, plan, out))
+        dxp = _moe_op("gemm_grouped", n, dz1p, W1.view(X, E, -1).transpose(1, 2), None, plan)
+        if acc is not None and _native(n, "moe"):
+            dn = _moe_op("moe_combine", n, dxp, plan, None, acc, out=acc)
+        else:
+            dn = _moe_op("moe_combine", n, dxp, plan, None, acc)
+        dl = _moe_op("moe_route_bwd", n, plan, gate, dgate, n.dtype)
+        _wgrad(g["Wr"], n, dl)
+        return mmul(dl, self.W("Wr").t(), out=dn, beta=1.0)
 
     def _ffn1_bwd(self, df2, z1):
         """dz1, the gradient of the first projection's output, from df2, the gradient of the second's."""
@@ -702,8 +791,11 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         if ph > 0.0:
             a, d1 = _drop_fwd(a, ph, self, "hidden1")
         n2, h, r2 = _rms_fwd(a, xt, P["ln2g"], c.layerNormEps, s_out=a)
-        f, z1 = self._ffn1(n2, True)
-        f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        if c.nExperts is None:
+            f, z1 = self._ffn1(n2, True)
+            f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+        else:
+            f, (f2, z1) = None, self._moe_fwd(n2)
         if ph > 0.0:
             f2, d2 = _drop_fwd(f2, ph, self, "hidden2")
         y = _add_into(h, f2)
@@ -739,6 +831,10 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         if c.preNorm():
             n2, h, _ = _rms_fwd(a, xt, self.params["ln2g"], c.layerNormEps, s_out=a)
+            if c.nExperts is not None:
+                y = self._moe_fwd(n2, acc=h)[0]                 # y = h + f2: the add rides on the combine
+                y = y.reshape(B, T, E).permute(0, 2, 1)
+                return y[:, :, 0] if one else y
             f, _ = self._ffn1(n2, False)
             if _native(f, "gemm"):
                 y = mmul(f, self.W("W2"), out=h, bias=bias_vec(self.Wbias("b2")), beta=1.0)   # y = h + f·W2 + b2
@@ -746,8 +842,11 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
                 y = _add_into(h, matmul(f, self.W("W2"), bias=self.Wbias("b2")))
         else:
             h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
-            f, _ = self._ffn1(h1, False)
-            f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+            if c.nExperts is None:
+                f, _ = self._ffn1(h1, False)
+                f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
+            else:
+                f2 = self._moe_fwd(h1)[0]
             y, _ = _ln_fwd(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps)
         y = y.reshape(B, T, E).permute(0, 2, 1)
         return y[:, :, 0] if one else y
@@ -765,16 +864,21 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         # column sums (b2 / bo gradient) come out of the LayerNorm backward launch; with it the producer's gradient is
         # ds∘D in a tensor of its own (ds stays the residual accumulator below) and the bias gradient ITS column sums.
         if d2 is None:
-            ds2 = df2 = _ln_bwd(dy, f2, h1, self.params["ln2g"], ln2, g["ln2g"], g["ln2b"], g["b2"])
+            ds2 = df2 = _ln_bwd(dy, f2, h1, self.params["ln2g"], ln2, g["ln2g"], g["ln2b"],
+                                g["b2"] if c.nExperts is None else None)      # the experts' b2 [X, E]: _moe_bwd
         else:
             ds2 = _ln_bwd(dy, f2, h1, self.params["ln2g"], ln2, g["ln2g"], g["ln2b"])
             df2 = _drop_bwd(ds2, d2)
-            _bsum(g["b2"], df2)
-        _wgrad(g["W2"], f, df2)
-        dz1 = self._ffn1_bwd(df2, z1)
-        _wgrad(g["W1"], h1, dz1)
-        _bsum(g["b1"], dz1)
-        dh1 = mmul(dz1, self.W("W1").t(), out=ds2, beta=1.0)          # residual gradient summed in place
+            if c.nExperts is None:
+                _bsum(g["b2"], df2)
+        if c.nExperts is None:
+            _wgrad(g["W2"], f, df2)
+            dz1 = self._ffn1_bwd(df2, z1)
+            _wgrad(g["W1"], h1, dz1)
+            _bsum(g["b1"], dz1)
+            dh1 = mmul(dz1, self.W("W1").t(), out=ds2, beta=1.0)      # residual gradient summed in place
+        else:
+            dh1 = self._moe_bwd(df2, h1, z1, acc=ds2)
         if d1 is None:
             ds1 = da = _ln_bwd(dh1, a, xt, self.params["ln1g"], ln1, g["ln1g"], g["ln1b"], g["bo"])
         else:
@@ -803,12 +907,15 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         P = self.params
         dy = _token_major(eps).to(xt.dtype).contiguous()
         df2 = dy if d2 is None else _drop_bwd(dy, d2)
-        _bsum(g["b2"], df2)
-        _wgrad(g["W2"], f, df2)
-        dz1 = self._ffn1_bwd(df2, z1)
-        _wgrad(g["W1"], n2, dz1)
-        _bsum(g["b1"], dz1)
-        dn2 = matmul(dz1, self.W("W1").t())
+        if c.nExperts is None:
+            _bsum(g["b2"], df2)
+            _wgrad(g["W2"], f, df2)
+            dz1 = self._ffn1_bwd(df2, z1)
+            _wgrad(g["W1"], n2, dz1)
+            _bsum(g["b1"], dz1)
+            dn2 = matmul(dz1, self.W("W1").t())
+        else:
+            dn2 = self._moe_bwd(df2, n2, z1)
         # dh: the gradient of h = x + a. Without hidden dropout it is also the attention branch's (da) and its column
         # sums (bo's gradient) come out of the norm's backward launch
         if d1 is None:
