@@ -966,7 +966,8 @@ class TextGenerationTransformer(ZooModel):
     def generate(net, prompt, promptLengths=None, **cfg):
         """``net.generate`` for this model: ``prompt`` [mb, Tp] token ids of one common length, or right-padded to Tp
         with ``promptLengths`` [mb] the length of every row; ``cfg``: GenerationConfig fields (maxNewTokens,
-        doSample, temperature, topK, topP, numBeams, eosToken, seed, ...).
+        doSample, temperature, topK, topP, numBeams, eosToken, seed, numDraftTokens, draftNgram, ...) and
+        ``assistant`` (the drafting network of speculative decoding).
         -> GenerationResult(tokens, lengths, scores)."""
         return net.generate(prompt, promptLengths=promptLengths, **cfg)
 
@@ -1080,7 +1081,8 @@ class TransformerSeq2Seq(ZooModel):
         """``net.generate`` for this model: ``source`` [mb, Ts] ids, ``start`` [mb, Tp] the first target tokens (e.g.
         one begin-of-sequence id per row), ``sourceMask`` [mb, Ts] the source padding, ``startLengths`` [mb] the
         length of every row of a right-padded ``start`` (forced prefixes of different lengths); ``cfg``:
-        GenerationConfig fields. -> GenerationResult(tokens, lengths, scores)."""
+        GenerationConfig fields, and ``assistant`` (a second TransformerSeq2Seq that drafts for speculative decoding;
+        it takes the same source and mask). -> GenerationResult(tokens, lengths, scores)."""
         masks = None if sourceMask is None else [sourceMask, None]
         return net.generate(start, others={"source": source}, masks=masks, tokenInput="target",
                             promptLengths=startLengths, **cfg)

@@ -41,7 +41,10 @@ class GenerationConfig:
     the generated stream (default: the last one). pinPositions: after the prompt the network's state is pinned
     (``rnnPinState``) so that every step has the same launch arguments: positions advance on the device, the sampler
     writes a staging row and one commit launch per step files it (not with numBeams > 1). useGraph: pinPositions, and
-    the step is captured once into a HIP graph and replayed (GPU only)."""
+    the step is captured once into a HIP graph and replayed (GPU only). numDraftTokens K (0 = off, else 1..16):
+    speculative decoding, K drafted tokens per round checked by the network in one chunked step (greedy or sampling
+    without topK / topP; not with numBeams > 1, pinPositions or useGraph); the drafts come from the ``assistant`` of
+    ``generate``, or without one from prompt lookup with n-grams of up to draftNgram (1..8) tokens."""
     maxNewTokens: int = 16
     doSample: bool = False
     temperature: float = 1.0
@@ -57,6 +60,8 @@ class GenerationConfig:
     tokenInput: Optional[str] = None
     pinPositions: bool = False
     useGraph: bool = False
+    numDraftTokens: int = 0
+    draftNgram: int = 3
 
     def validate(self):
         def bad(msg):
@@ -82,6 +87,21 @@ class GenerationConfig:
         for f in ("useGraph", "pinPositions"):
             if getattr(self, f) and int(self.numBeams) > 1:
                 bad(f"{f} cannot be combined with numBeams > 1 (beam search reorders the caches every step)")
+        if not 0 <= int(self.numDraftTokens) <= 16:
+            bad(f"numDraftTokens must be in 0..16 (0 = off), got {self.numDraftTokens}")
+        if not 1 <= int(self.draftNgram) <= 8:
+            bad(f"draftNgram must be in 1..8, got {self.draftNgram}")
+        if int(self.numDraftTokens) > 0:
+            if int(self.numBeams) > 1:
+                bad("numDraftTokens cannot be combined with numBeams > 1 (speculative decoding checks one draft "
+                    "sequence per row)")
+            for f in ("useGraph", "pinPositions"):
+                if getattr(self, f):
+                    bad(f"numDraftTokens cannot be combined with {f} (a round sets the positions back, a pinned "
+                        "state only advances)")
+            if int(self.topK) != 0 or float(self.topP) != 1.0:
+                bad(f"numDraftTokens cannot be combined with topK / topP (got topK={self.topK}, topP={self.topP}): "
+                    "the residual of filtered distributions is not supported")
         return self
 
 
@@ -126,6 +146,39 @@ def trim_layers(named, lengths):
                 l.rnnTrimState(n, dryRun=dry)
             except DL4JInvalidInputException as e:
                 raise DL4JInvalidInputException(f"{label}: {e}") from None
+
+
+def positionable_layers(named):
+    """The (label, layer) pairs that keep rnnTimeStep state; a layer among them whose state cannot be set back to an
+    earlier position (LSTM family, SimpleRnn, a wrapper) refuses, naming itself, before anything is changed."""
+    todo = [(label, l) for label, l in named if hasattr(l, "rnnClearPreviousState")]
+    for label, l in todo:
+        if not hasattr(l, "rnnSetPositions"):
+            from .layers.recurrent import cannot_reposition
+            _labelled(label, cannot_reposition, l)
+    return todo
+
+
+def set_positions(net, named, bound, short):
+    """rnnSetPositions of a network over its (label, layer) pairs: every layer is validated (the layers that hold
+    state must have seen one count of tokens in one number of rows, ``short`` must be int32 [mb] on the network's
+    device), then every layer takes ``bound`` and the tensor ``short`` itself. Nothing is launched or read."""
+    refuse_pinned(net, "rnnSetPositions")
+    todo = positionable_layers(named)
+    live = [(label, l, l.rnnPinInfo()) for label, l in todo if hasattr(l, "rnnPinInfo")]
+    live = [(label, l, i) for label, l, i in live if i is not None]
+    if torch.is_tensor(short) and live:
+        dev = torch.device(net.device)
+        if short.device.type != dev.type or (dev.index is not None and short.device.index != dev.index):
+            raise DL4JInvalidInputException(f"rnnSetPositions: short is on {short.device}, the network on {dev}")
+    for label, l, (s, m, _) in live:
+        if (s, m) != live[0][2][:2]:
+            raise DL4JInvalidInputException(
+                f"rnnSetPositions: {label} has seen {s} tokens in {m} rows, {live[0][0]} {live[0][2][0]} in "
+                f"{live[0][2][1]}; one bound and one position array cannot serve both")
+    for dry in (True, False):
+        for label, l in todo:
+            _labelled(label, l.rnnSetPositions, bound, short, dryRun=dry)
 
 
 def set_cache_data_type(named, value):
@@ -294,6 +347,28 @@ class _Stepper:
     def step(self, tok):
         return self._run(self._encode(tok.reshape(-1, 1)), False)
 
+    def chunk(self, ids):
+        """ids [rows, Tn] int64 -> every time step's distribution as [rows, Tn, V]: a view of the network's output
+        where it lies (the output layer's [rows, V, Tn] is time-major memory, so a row is contiguous in V)."""
+        last = _output_layer(self.net)
+        last.chunkRowsInTree = True                              # this call alone: no torch copy in a round
+        try:
+            if self.graph:
+                ins = [None] * len(self.names)
+                ins[self.tidx] = self._encode(ids)
+                out = self.net._rnn_time_step_raw(*ins)[0]
+            else:
+                out = self.net._rnn_time_step_raw(self._encode(ids))
+        finally:
+            last.chunkRowsInTree = False
+        return out.permute(0, 2, 1)
+
+    def set_positions(self, bound, short):
+        if self.graph:
+            self.net.rnnSetPositions(bound, short, self.names[self.tidx])
+        else:
+            self.net.rnnSetPositions(bound, short)
+
     def token_layers(self):
         """(label, layer) of the layers the generated stream runs through."""
         if self.graph:
@@ -307,9 +382,12 @@ class _Stepper:
             self.net.rnnPinState(capacity)
 
 
+def _output_layer(net):
+    return net.layers_by_name[net.outputs[0]] if hasattr(net, "layers_by_name") else net.layers[-1]
+
+
 def _vocab(net):
-    layer = net.layers_by_name[net.outputs[0]] if hasattr(net, "layers_by_name") else net.layers[-1]
-    return int(layer.conf.nOut)
+    return int(_output_layer(net).conf.nOut)
 
 
 def _stream(cfg, device):
@@ -323,7 +401,7 @@ def _stream(cfg, device):
 
 
 def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=False, promptLengths=None,
-             **configFields):
+             assistant=None, **configFields):
     """Generate ``maxNewTokens`` tokens per row of ``prompt`` [mb, Tp] (ids of one common length, or with
     ``promptLengths`` [mb] right-padded to Tp with row b that long, 1 <= promptLengths[b] <= Tp; the entries past a
     row's length must be valid ids and otherwise do not matter: the prompt runs as one padded rectangle, then
@@ -333,6 +411,11 @@ def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=Fals
     ComputationGraph.rnnTimeStep, for the first call. ``useBeamPath`` runs numBeams == 1 through the beam search.
     With ``pinPositions`` / ``useGraph`` the network stays pinned afterwards (``rnnClearPreviousState()`` unpins) and
     ``net.lastGenerationStats`` tells how the steps ran: {"captures", "graphReplays", "eagerSteps"}.
+    Speculative decoding (``numDraftTokens`` K >= 1, see ``_speculative``): per round K tokens are drafted — by
+    ``assistant``, a second MultiLayerNetwork / ComputationGraph over the same vocabulary that takes the same
+    ``others`` / ``masks``, or without one by prompt lookup — and checked by ``net`` in one chunked step; greedy output
+    is the plain call's, sampled output follows the network's distribution exactly.
+    ``net.lastGenerationStats`` = {"rounds", "draftTokens", "acceptedTokens"}.
     -> GenerationResult(tokens int64 [mb, maxNewTokens], lengths int64 [mb] (up to and including eos),
     scores fp32 [mb] (the sum of the chosen tokens' log-probabilities; for beam search divided by
     length**lengthPenalty))."""
@@ -362,9 +445,27 @@ def generate(net, prompt, config=None, others=None, masks=None, useBeamPath=Fals
             raise DL4JInvalidConfigException(f"GenerationConfig: useGraph needs a GPU, the network is on "
                                              f"{net.device}; pinPositions runs the same steps eagerly on any device")
         pinnable_layers(stepper.token_layers())                  # refused before the prompt runs
+    K = int(cfg.numDraftTokens)
+    drafter = None
+    if assistant is not None and K == 0:
+        raise DL4JInvalidConfigException("generate: an assistant drafts for speculative decoding, which "
+                                         "numDraftTokens >= 1 turns on; got numDraftTokens=0")
+    if K > 0:
+        if useBeamPath:
+            raise DL4JInvalidConfigException("GenerationConfig: numDraftTokens cannot run the beam path")
+        if assistant is net:
+            raise DL4JInvalidInputException("generate: the assistant must be a network of its own (a clone of the "
+                                            "network, not the network itself): both keep rnnTimeStep state")
+        if assistant is not None:
+            drafter = _Stepper(assistant, cfg, others, masks)
+        _speculative_check(stepper, drafter, prompt.shape[1], cfg)   # refused before the prompt runs
+        if assistant is not None:
+            assistant.rnnClearPreviousState()
     net.rnnClearPreviousState()
     with torch.no_grad():
         p = stepper.first(prompt, lengths)
+        if K > 0:
+            return _speculative(net, stepper, drafter, p, cfg, prompt, lengths)
         if int(cfg.numBeams) > 1 or useBeamPath:
             return _beam(net, stepper, p, cfg)
         if pinned:
@@ -399,6 +500,92 @@ def _sample(stepper, p, cfg):
     # summed in fp64 and rounded once: a row's score does not depend on how many rows the batch has (torch's fp32
     # column sum picks its order by the shape), so a ragged batch scores every row as the row alone
     return GenerationResult(toks, _lengths(toks, eos), logps.sum(0, dtype=torch.float64).float())
+
+
+def _speculative_check(stepper, drafter, Tp, cfg):
+    """What speculative decoding needs of the network(s), checked before the prompt runs: one vocabulary, state that
+    rnnSetPositions can set back, and position tables that hold a chunk which overshoots the last position by K."""
+    N, K = int(cfg.maxNewTokens), int(cfg.numDraftTokens)
+    roles = [("the network", stepper)] + ([("the assistant", drafter)] if drafter is not None else [])
+    if drafter is not None and _vocab(drafter.net) != _vocab(stepper.net):
+        raise DL4JInvalidInputException(
+            f"generate: the assistant's vocabulary has {_vocab(drafter.net)} tokens, the network's "
+            f"{_vocab(stepper.net)}; speculative decoding needs one vocabulary")
+    for role, s in roles:
+        _labelled(f"generate: {role}", positionable_layers, s.token_layers())
+        limits = [l.rnnPinLimit() for _, l in s.token_layers() if hasattr(l, "rnnPinLimit")]
+        limit = min([n for n in limits if n is not None], default=None)
+        if limit is not None and Tp + N + K > limit:
+            raise DL4JInvalidInputException(
+                f"generate: {role} holds {limit} positions, fewer than the prompt's {Tp} + maxNewTokens {N} + "
+                f"numDraftTokens {K} (a round's chunk may overshoot the last position by numDraftTokens)")
+
+
+def _speculative(net, stepper, drafter, p, cfg, prompt, lengths):
+    """Speculative decoding: the first token comes from the row sampler on the prompt's distribution; then per round
+    K tokens are drafted (``drafter``: K + 1 single steps of the assistant, the row sampler drawing d_(i+1) from each
+    of the first K outputs, which are kept; the last step only fills the assistant's cache row, so both networks hold
+    the same K + 1 new rows — or one prompt-lookup launch), the network takes the chunk [next, d_1 .. d_K] in one
+    step, the verify launch emits every row's accepted drafts and one more token, the commit launch turns the rows'
+    new lengths into one shortfall array, and the host reads two integers (rows not finished, the longest row) — the
+    round's only device-to-host copy — and sets both networks' positions to them. Rejected drafts cost nothing to
+    take back: their cache rows lie past the row's position and the next chunk overwrites them. Finished rows ride
+    along at their frozen position."""
+    from ..ops import generation_native as GN
+    mb, dev, N, K = p.shape[0], p.device, int(cfg.maxNewTokens), int(cfg.numDraftTokens)
+    Tp, eos, pad, greedy = prompt.shape[1], cfg.eosToken, int(cfg.padToken), not cfg.doSample
+    stats = {"rounds": 0, "draftTokens": 0, "acceptedTokens": 0}
+    net.lastGenerationStats = stats
+    rng = _stream(cfg, dev) if cfg.doSample else None
+    fin = torch.zeros(mb, dtype=torch.uint8, device=dev)
+    tm = torch.zeros(K + 1, mb, dtype=torch.int64, device=dev)   # row 0: the next input; 1 .. K: an assistant's drafts
+    lp = torch.zeros(mb, dtype=torch.float32, device=dev)
+    GN.sample_rows(p, cfg.temperature, 0, 1.0, greedy, rng, fin, eos, pad, None, out=(tm[0], lp), advance=True)
+    tokens = torch.full((mb, N), pad, dtype=torch.int64, device=dev)
+    logps = torch.zeros(mb, N, dtype=torch.float32, device=dev)
+    tokens[:, 0] = tm[0]
+    logps[:, 0] = lp
+    if N > 1:
+        length = torch.full((mb,), Tp, dtype=torch.int32, device=dev) if lengths is None else \
+            lengths.to(device=dev, dtype=torch.int32)
+        cursor = torch.ones(mb, dtype=torch.int32, device=dev)
+        chunk = torch.zeros(mb, K + 1, dtype=torch.int64, device=dev)
+        chunk[:, 0] = tm[0]
+        short = torch.zeros(mb, dtype=torch.int32, device=dev)
+        slot = torch.zeros(2, dtype=torch.int32, device=dev)
+        counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        hist = qbuf = None
+        if drafter is None:
+            hist = torch.zeros(mb, Tp + N, dtype=torch.int64, device=dev)
+            hist[:, :Tp] = prompt
+            hist.scatter_(1, length.to(torch.int64).reshape(mb, 1), tm[0].reshape(mb, 1))
+        else:
+            drafter.first(prompt, lengths)
+            qbuf = torch.empty(K, mb, p.shape[1], dtype=p.dtype, device=dev)
+        GN.spec_commit(length, fin, short, slot)
+        while True:
+            unfinished, bound = slot.tolist()                    # the one host read of a round
+            stepper.set_positions(bound, short)
+            if drafter is not None:
+                drafter.set_positions(bound, short)
+            if unfinished == 0:
+                break
+            if drafter is None:
+                GN.ngram_draft(hist, length, cfg.draftNgram, K, chunk[:, 1:])
+            else:
+                for i in range(K):
+                    q = drafter.step(tm[i])
+                    GN.sample_rows(q, cfg.temperature, 0, 1.0, greedy, rng, None, None, pad, None,
+                                   out=(tm[i + 1], lp), advance=True)
+                    GN.spec_keep(q, qbuf[i], tm[i + 1], chunk[:, i + 1])
+                drafter.step(tm[K])
+            GN.spec_verify(stepper.chunk(chunk), None if drafter is None else qbuf.permute(1, 0, 2), chunk[:, 1:],
+                           cfg.temperature, greedy, rng, length, cursor, fin, eos, pad, tokens, logps, tm[0],
+                           chunk[:, 0], hist, counters)
+            GN.spec_commit(length, fin, short, slot)
+            stats["rounds"] += 1
+        stats["draftTokens"], stats["acceptedTokens"] = counters.tolist()
+    return GenerationResult(tokens, _lengths(tokens, eos), logps.sum(1, dtype=torch.float64).float())
 
 
 def _pin_capacity(stepper, Tp, N):

@@ -833,13 +833,27 @@ class ComputationGraph(BaseNetwork):
         from ..generation import pin_layers
         pin_layers(self, self._layers_downstream(input, "rnnPinState"), capacity)
 
-    def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, **configFields):
+    def rnnSetPositions(self, bound, short, input=None):
+        """Set the positions of the stored rnnTimeStep state of every layer downstream of network input ``input``
+        (a name; default: the last input) again, as MultiLayerNetwork.rnnSetPositions: each such layer that holds
+        state takes ``bound`` as its count of tokens seen and the tensor ``short`` itself (int32 [mb], contiguous, on
+        the network's device) as its per-row shortfall; layers fed only by other inputs are left alone. A downstream
+        layer whose state cannot be set back (LSTM family, SimpleRnn, wrappers) makes the call raise
+        DL4JInvalidInputException before any layer is changed."""
+        from ..generation import set_positions
+        set_positions(self, self._layers_downstream(input, "rnnSetPositions"), bound, short)
+
+    def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, assistant=None,
+                 **configFields):
         """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py); ``others``
         maps the remaining network inputs to their arrays for the first call, ``masks`` as in rnnTimeStep.
-        ``promptLengths`` [mb]: the prompts are right-padded to Tp and row b is that long.
+        ``promptLengths`` [mb]: the prompts are right-padded to Tp and row b is that long. ``assistant``: with
+        ``numDraftTokens`` the network that drafts for speculative decoding (without one: prompt lookup); it takes
+        the same ``others`` / ``masks``.
         -> GenerationResult(tokens [mb, maxNewTokens], lengths [mb], scores [mb])."""
         from ..generation import generate
-        return generate(self, prompt, config, others, masks, promptLengths=promptLengths, **configFields)
+        return generate(self, prompt, config, others, masks, promptLengths=promptLengths, assistant=assistant,
+                        **configFields)
 
     def rnnGetPreviousState(self, layerName):
         """Stored rnnTimeStep state of one recurrent layer (reference ComputationGraph.rnnGetPreviousState,

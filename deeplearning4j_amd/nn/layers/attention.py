@@ -259,6 +259,9 @@ class CrossAttentionLayerImpl(MemoryKVState, LayerImpl):
     def rnnTrimState(self, lengths, dryRun=False):
         """The stored memory projection does not depend on how long the rows of the own stream are: nothing to do."""
 
+    def rnnSetPositions(self, bound, short, dryRun=False):
+        """The stored memory projection has no position of the own stream: nothing to do."""
+
     def rnnPinInfo(self):
         """The stored memory projection has no position that advances: nothing to pin."""
         return None

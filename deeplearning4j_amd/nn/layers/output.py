@@ -192,6 +192,8 @@ class LossLayerImpl(BaseOutputLayerImpl):
 
 class RnnOutputLayerImpl(BaseOutputLayerImpl):
     GRADS_OVERWRITE = True        # weight_grad_ / bias_grad_ write the whole W / b views
+    chunkRowsInTree = False       # rnnTimeStep: reorder a chunk's rows with the in-tree copy (speculative rounds)
+
     def _in2d(self, x):
         self._mb = x.shape[0]
         return _rnn_to_2d(x) if x.dim() == 3 else x
@@ -225,7 +227,17 @@ class RnnOutputLayerImpl(BaseOutputLayerImpl):
         x = self.applyDropOutIfNecessary(x, False)
         self.input = x
         self.maskArray = None
-        self._x2 = self._in2d(x)
+        x2 = None
+        if self.chunkRowsInTree and x.dim() == 3 and x.shape[2] > 1:
+            # a speculative round's chunk (nn/generation.py sets the flag around that one call): its token-major rows
+            # become time-major ones in one in-tree strided-copy launch, the same values as _rnn_to_2d's torch copy,
+            # which every other call keeps
+            from ...ops import nd4j_kernels as NK
+            mb, n, T = x.shape
+            x2 = NK.cast_pad_last(x.permute(2, 0, 1), x.dtype, n)
+            if x2 is not None:
+                self._mb, x2 = mb, x2.reshape(T * mb, n)
+        self._x2 = x2 if x2 is not None else self._in2d(x)
         self._z = z = self.preOutput2d(self._x2)
         self._cache = None
         from ...ops import native

@@ -267,6 +267,15 @@ def cannot_pin(layer):
         "pinned, only key/value caches and position embeddings advance on the device")
 
 
+def cannot_reposition(layer):
+    """rnnSetPositions on a layer that keeps rnnTimeStep state it cannot take back (a recurrence, or a wrapper around
+    one): always refused, naming the layer."""
+    from ...exceptions import DL4JInvalidInputException
+    raise DL4JInvalidInputException(
+        f"rnnSetPositions on layer {layer.index} ({type(layer.conf).__name__}): this layer's rnnTimeStep state cannot "
+        "be set back to an earlier position, only key/value caches and position embeddings can")
+
+
 def forward_trim(inner, lengths, dryRun):
     """rnnTrimState of a wrapper layer: the wrapped layer's, refused where that one keeps state it cannot trim."""
     if hasattr(inner, "rnnTrimState"):

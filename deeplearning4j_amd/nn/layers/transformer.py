@@ -453,6 +453,21 @@ class KVCacheState:
         if not dryRun:
             self._kv_short = short.to(self._kv.device)
 
+    def rnnSetPositions(self, bound, short, dryRun=False):
+        """Set the rows' positions again (the network's rnnSetPositions): the host count becomes ``bound``
+        (1 <= bound <= tokens seen) and ``short`` (int32 [mb], contiguous, on the cache's device; kept as it is, not
+        copied, so a later in-place update on the device moves every layer that shares it) the shortfall: row b holds
+        ``bound - short[b]`` tokens, and what the cache holds past that is overwritten by the next append. Any number
+        of times per sequence, also after rnnTrimState; nothing is launched or read. The caller vouches for
+        ``0 <= short[b] < bound`` (the kernels clamp). ``dryRun`` only validates. A layer without a cache has nothing
+        to do. A rotary layer's surviving rows hold keys rotated by their own row index, which stays valid."""
+        if self._kv is None:
+            return
+        _refuse_pinned(self, "rnnSetPositions", self._kv_pinned)
+        _positions_check(self, bound, short, self._kv_len, self._kv.shape[0], self._kv.device)
+        if not dryRun:
+            self._kv_len, self._kv_short = int(bound), short
+
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of the cache becomes the old row ``parents[i]`` (int32 device tensor [mbNew]; mbNew may differ from
         the stored minibatch size). The valid rows are gathered into a second buffer of the same capacity
@@ -647,6 +662,24 @@ def _trim_shortfall(layer, lengths, seen, mb, trimmed):
             f"{who}: every length must be in 1..{seen} (the tokens seen since rnnClearPreviousState()), got "
             f"{n.tolist()}")
     return (seen - n).to(torch.int32)
+
+
+def _positions_check(layer, bound, short, seen, mb, device):
+    """A layer's validation of rnnSetPositions(bound, short) with ``seen`` tokens stored in ``mb`` rows."""
+    from ...exceptions import DL4JInvalidInputException
+    who = f"rnnSetPositions on layer {layer.index} ({type(layer.conf).__name__})"
+    if isinstance(bound, bool) or not isinstance(bound, int) or not 1 <= bound <= seen:
+        raise DL4JInvalidInputException(
+            f"{who}: bound must be an integer in 1..{seen} (the tokens seen since rnnClearPreviousState()), got "
+            f"{bound!r}")
+    if not (torch.is_tensor(short) and short.dtype == torch.int32 and tuple(short.shape) == (mb,) and
+            short.is_contiguous()):
+        got = f"{short.dtype} {tuple(short.shape)}" if torch.is_tensor(short) else type(short).__name__
+        raise DL4JInvalidInputException(
+            f"{who}: short must be a contiguous int32 tensor [{mb}] (one entry per row of the stored state), got "
+            f"{got}")
+    if short.device != device:
+        raise DL4JInvalidInputException(f"{who}: short is on {short.device}, the stored state on {device}")
 
 
 def _reorder_short(short, parents, groupSize):
@@ -1301,6 +1334,16 @@ class BertEmbeddingLayerImpl(DropoutSites, LayerImpl):
         short = _trim_shortfall(self, lengths, pos, mb, self._short is not None)
         if not dryRun:
             self._short = short.to(self.params["Wword"].device)
+
+    def rnnSetPositions(self, bound, short, dryRun=False):
+        """Set the rows' positions again, as KVCacheState.rnnSetPositions: the count of tokens seen becomes ``bound``
+        and row b's next token takes position ``bound - short[b]``; ``short`` is kept as it is, not copied."""
+        if self._seen is None:
+            return
+        _refuse_pinned(self, "rnnSetPositions", self._pinned)
+        _positions_check(self, bound, short, self._seen[0], self._seen[1], self.params["Wword"].device)
+        if not dryRun:
+            self._seen, self._short = (int(bound), self._seen[1]), short
 
     def rnnReorderState(self, parents, groupSize=None):
         if self._seen is not None:

@@ -504,12 +504,28 @@ class MultiLayerNetwork(BaseNetwork):
         refuse_pinned(self, "rnnTrimState")
         trim_layers([(f"layer {i}", l) for i, l in enumerate(self.layers)], lengths)
 
-    def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, **configFields):
+    def rnnSetPositions(self, bound, short):
+        """Set the positions of the stored rnnTimeStep state again: every layer that holds state takes ``bound`` as
+        its count of tokens seen (1 <= bound <= the tokens seen; every such layer must have seen the same count in the
+        same number of rows) and the tensor ``short`` itself (int32 [mb], contiguous, on the network's device) as its
+        per-row shortfall, so row b holds ``bound - short[b]`` tokens and what the caches hold past that is
+        overwritten by the next append. Nothing is launched or read; the caller vouches for ``0 <= short[b] < bound``.
+        The tensor is shared, not copied: an in-place update on the device moves every layer of every network that
+        was handed it. Any number of times per sequence, also after rnnTrimState; refused while pinned. A layer whose
+        state cannot be set back (LSTM family, SimpleRnn, wrappers) makes the call raise DL4JInvalidInputException
+        before any layer is changed."""
+        from .generation import set_positions
+        set_positions(self, [(f"layer {i}", l) for i, l in enumerate(self.layers)], bound, short)
+
+    def generate(self, prompt, config=None, others=None, masks=None, promptLengths=None, assistant=None,
+                 **configFields):
         """Token generation from ``prompt`` [mb, Tp] (greedy, sampling or beam search; nn/generation.py).
-        ``promptLengths`` [mb]: the prompts are right-padded to Tp and row b is that long.
+        ``promptLengths`` [mb]: the prompts are right-padded to Tp and row b is that long. ``assistant``: with
+        ``numDraftTokens`` the network that drafts for speculative decoding (without one: prompt lookup).
         -> GenerationResult(tokens [mb, maxNewTokens], lengths [mb], scores [mb])."""
         from .generation import generate
-        return generate(self, prompt, config, others, masks, promptLengths=promptLengths, **configFields)
+        return generate(self, prompt, config, others, masks, promptLengths=promptLengths, assistant=assistant,
+                        **configFields)
 
     def rnnGetPreviousState(self, layer):
         return self.layers[layer].rnnGetPreviousState()

@@ -48,7 +48,15 @@
              hidden-768 model: generate() and generate(useGraph=True) at prefix 1024 and 4032, and a causal-LM
              training step of batch 32 at 2048 tokens.
 
+  --speculative K[,K..] [--draft-layers L | --lookup]  speculative decoding: the verify / commit / n-gram draft
+             kernels alone at V in {77, 32000, 128000}; then generate(numDraftTokens=K) against generate() on the
+             12-layer, hidden-768 model (prefix 128), drafts from an L-layer assistant of the same width (default 2) or
+             from prompt lookup, the variants alternating within every pass: time per round and per plain step, the
+             acceptance observed (random weights: no statement about trained models) and the break-even acceptance.
+             With ``--model --tree PATH`` the plain generate() rows can be taken from the parent commit's checkout.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
+       python tools/bench_generate.py --speculative 2,4,8 [--lookup] [--out profiles/speculative.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
        python tools/bench_generate.py --graph [--parent-lib PATH] [--out profiles/generation_graph.txt]
        python tools/bench_generate.py --cache fp8 [--batch 32] [--out FILE]
@@ -648,6 +656,104 @@ def _compare_models(nets, kinds, V, batches, n, passes, prefixes=(128, 1024), tr
     say()
 
 
+def speculative_kernels_mode(passes, reps):
+    """The verify, commit and draft kernels of csrc/speculative.hip alone."""
+    say(f"== speculative decoding kernels, bf16 distributions, K = 4, GPU time per call in us (median of {passes} "
+        f"passes of {reps} launches; min .. max); verify: q == p, so every draft is accepted and all K + 1 rows are "
+        "read (the most a call reads); reject@0: the first draft has p = 0, one row is read and resampled")
+    K, N = 4, 16
+    for mb in (1, 32):
+        for V in (77, 32000, 128000):
+            g = torch.Generator().manual_seed(mb + V)
+            p = torch.softmax(torch.randn(K + 1, mb, V, generator=g) * 2.0, 2).to(torch.bfloat16).to(DEV)
+            q = p[:K].clone()
+            d = torch.multinomial(p[:K].float().reshape(K * mb, V), 1).reshape(K, mb).t().contiguous()
+            p0 = p.clone()
+            p0[0].scatter_(1, d[:, :1], 0.0)
+            st = [torch.zeros(mb, dtype=torch.int32, device=DEV) for _ in range(3)]
+            fin = torch.zeros(mb, dtype=torch.uint8, device=DEV)
+            toks = torch.zeros(mb, N, dtype=torch.int64, device=DEV)
+            logps = torch.zeros(mb, N, dtype=torch.float32, device=DEV)
+            nxt = torch.zeros(mb, dtype=torch.int64, device=DEV)
+            slot = torch.zeros(2, dtype=torch.int32, device=DEV)
+            rng = PhiloxStream(DEV)
+
+            def verify(pp, greedy):
+                st[1].zero_()
+                return GN.spec_verify_native(pp.permute(1, 0, 2), q.permute(1, 0, 2), d, 0.8, greedy, rng, st[0],
+                                             st[1], fin, None, 0, toks, logps, nxt)
+
+            hist = torch.randint(0, V, (mb, 193), generator=g).to(DEV)
+            hlen = torch.full((mb,), 192, dtype=torch.int32, device=DEV)
+            dr = torch.zeros(mb, K, dtype=torch.int64, device=DEV)
+            rows = (("verify sampled", lambda: verify(p, False)), ("reject@0 sampled", lambda: verify(p0, False)),
+                    ("commit", lambda: GN.spec_commit(st[0], fin, st[2], slot)),
+                    ("n-gram draft, 192 tokens", lambda: GN.ngram_draft_native(hist, hlen, 3, K, dr)))
+            for name, fn in rows:
+                if name.startswith(("commit", "n-gram")) and V != 77:
+                    continue                                     # these do not read the distributions
+                t = _med(fn, passes, reps)                       # includes the zero_() launch of the cursor reset
+                say(f"mb={mb:2d} V={V:6d} {name:26s}: {t[0]:8.1f} ({t[1]:.1f} .. {t[2]:.1f})")
+    say()
+
+
+def speculative_mode(Ks, batches, n, passes, draft_layers, lookup):
+    """generate(numDraftTokens=K) against generate() on the 12-layer, hidden-768 model, alternating within a pass."""
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, P = 77, 128
+
+    def model(layers, seed):
+        return TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=768, layers=layers, heads=12, seed=seed,
+                                         maxPositions=512, dataType=DataType.BFLOAT16).init(device=DEV)
+    net = model(12, 12345)
+    assistant = None if lookup else model(draft_layers, 777)
+    source = "prompt lookup (draftNgram 3)" if lookup else f"a {draft_layers}-layer assistant of the same width"
+    say(f"== generate(numDraftTokens=K) with {source} against generate() on TextGenerationTransformer(768, 12 layers, "
+        f"12 heads), bf16, V = {V}, greedy, prefix {P}, {n} new tokens; whole calls (prompt included) on the host clock, "
+        f"ended by a device synchronise; median of {passes} passes (min .. max), the variants alternating within a pass")
+    say("   the weights are random: the acceptance observed here says nothing about trained models. ms/round and "
+        f"ms/step come from the same calls with {max(2, n // 4)} tokens (a call's time is a + b * rounds); break-even = "
+        "the share of the K drafts a round must have accepted to emit tokens as fast as plain steps, "
+        "(round / step - 1) / K")
+    few = max(2, n // 4)
+    for mb in batches:
+        prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb)).to(DEV)
+        variants = [("plain", {})] + [(f"K={k}", dict(numDraftTokens=k, assistant=assistant)) for k in Ks]
+
+        def call(kw, tokens):
+            r = net.generate(prompt, maxNewTokens=tokens, **kw)
+            return r, net.lastGenerationStats
+
+        info = []
+        for _, kw in variants:
+            call(kw, few)
+            info.append((call(kw, n)[1], call(kw, few)[1]))
+        times = [[[], []] for _ in variants]
+        for _ in range(passes):
+            for i, (_, kw) in enumerate(variants):
+                times[i][0].append(_sync_time(lambda: call(kw, n)))
+                times[i][1].append(_sync_time(lambda: call(kw, few)))
+        med = [[sorted(t)[len(t) // 2] for t in pair] for pair in times]
+        step = (med[0][0] - med[0][1]) / (n - few) * 1e3
+        for i, ((vn, _), (sn, sf)) in enumerate(zip(variants, info)):
+            t = times[i][0]
+            line = f"batch {mb:2d} {vn:6s}: {mb * n / med[i][0]:9.1f} tok/s  {med[i][0] * 1e3:8.1f} ms per call " \
+                   f"({min(t) * 1e3:.1f} .. {max(t) * 1e3:.1f})"
+            if i == 0:
+                line += f"  {step:6.2f} ms/step"
+            else:
+                rounds = max(1, sn["rounds"] - sf["rounds"])
+                rnd = (med[i][0] - med[i][1]) / rounds * 1e3
+                k = Ks[i - 1]
+                line += f"  x {med[0][0] / med[i][0]:5.3f} | {rnd:6.2f} ms/round ({sn['rounds']} rounds), round/step " \
+                        f"{rnd / step:5.2f}, break-even acceptance {(rnd / step - 1) / k:5.2f}; observed " \
+                        f"{sn['acceptedTokens']}/{sn['draftTokens']} drafts accepted"
+            say(line)
+    net.rnnClearPreviousState()
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -669,6 +775,11 @@ def main():
     ap.add_argument("--window", type=int, default=None,
                     help="sliding-window attention (attentionWindow in every block) against none: generate(), "
                          "useGraph=True at prefix 1024 and 4032, a training step at 2048 tokens")
+    ap.add_argument("--speculative", default=None,
+                    help="speculative decoding: numDraftTokens values (comma separated) against plain generate(), and "
+                         "the verify / commit / draft kernels alone")
+    ap.add_argument("--draft-layers", type=int, default=2, help="--speculative: the assistant's number of blocks")
+    ap.add_argument("--lookup", action="store_true", help="--speculative: draft by prompt lookup, without an assistant")
     ap.add_argument("--tree", default=None, help="import the package from this checkout instead of the tool's own")
     ap.add_argument("--parent-lib", default=None,
                     help="kernel library built from the parent commit (--ragged, --graph)")
@@ -702,6 +813,10 @@ def main():
         block_mode(a.batch, a.tokens, a.passes)
     if a.window:
         window_mode(a.window, a.batch, a.tokens, a.passes)
+    if a.speculative:
+        speculative_kernels_mode(a.passes, a.reps)
+        speculative_mode([int(k) for k in a.speculative.split(",")], a.batch, a.tokens, a.passes, a.draft_layers,
+                         a.lookup)
 
 
 if __name__ == "__main__":
