@@ -68,6 +68,8 @@ class LayerImpl:
             self.params[key].copy_(val.reshape(self.params[key].shape))
             if self.cparams.get(key) is not None and self.cparams[key] is not self.params[key]:
                 self.cparams[key].copy_(self.params[key])
+        if self._wq:
+            self._wq = {}               # the quantised copies follow at their next use
 
     def setParamTable(self, table):
         for k, v in table.items():
@@ -119,6 +121,37 @@ class LayerImpl:
         if p is not None and p.dtype == torch.float32 and getattr(self.conf, "weightNoise", None) is None:
             return p
         return self.W(key)
+
+    # -------------------------------------------------------------------------- weight-only quantised decoding
+    # rnnSetWeightDataType of the network: the matrices a layer lists in wqKeys() are held a second time as MXFP8 /
+    # MXFP4 (ops.transformer_native.QuantWeight) and read by rnnTimeStep only. The copies are derived state: each
+    # remembers the weight version it was made from (ops.conv_native.WEIGHT_VERSION, bumped by every update of the
+    # network's parameters or compute copies) and is requantised on its next use after that moved on.
+    _wq_fmt = None        # None, "fp8" or "fp4"
+    _wq = None            # key -> (weight version, QuantWeight)
+    _wq_step = False      # an output layer inside an rnnTimeStep whose projection reads the quantised W
+
+    def wqKeys(self):
+        """The weight matrices [nIn, nOut] this layer's rnnTimeStep reads quantised (none by default)."""
+        return ()
+
+    def wqSetFormat(self, fmt):
+        self._wq_fmt, self._wq = fmt, {}
+
+    def wqWeight(self, key):
+        from ...ops import conv_native, transformer_native as TN
+        v = conv_native.WEIGHT_VERSION[0]
+        ent = self._wq.get(key)
+        if ent is None or ent[0] != v:
+            with torch.no_grad():
+                ent = self._wq[key] = (v, TN.wq_quantize(self.W(key), self._wq_fmt))
+        return ent[1]
+
+    def wqLinear(self, x, key, bias=None, act=None, out=None, beta=0.0):
+        """``act(x @ deq(Wq[key]) + bias + beta * out)`` on the quantised copy of parameter ``key``."""
+        from ...ops import transformer_native as TN
+        from ...ops.gemm import bias_vec
+        return TN.wq_linear(x, self.wqWeight(key), bias_vec(bias), act, out, beta)
 
     def type(self):
         return "FEED_FORWARD"

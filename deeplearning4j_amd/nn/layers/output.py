@@ -56,6 +56,8 @@ class BaseOutputLayerImpl(LayerImpl):
         if not self.has_params:
             return x
         W = self.W("W")
+        if self._wq_step:               # an rnnTimeStep with rnnSetWeightDataType: the quantised copy of W
+            return self.wqLinear(x.to(W.dtype), "W", self.Wbias("b") if "b" in self.params else None)
         return matmul(x.to(W.dtype), W, bias=self.Wbias("b") if "b" in self.params else None)
 
     # 2d views of input / labels / mask -------------------------------------------------------
@@ -215,10 +217,23 @@ class RnnOutputLayerImpl(BaseOutputLayerImpl):
     def _eps_from2d(self, e):
         return _2d_to_rnn(e, self._mb) if self.input.dim() == 3 else e
 
+    def wqKeys(self):
+        return ("W",) if self.has_params else ()
+
     def rnnTimeStep(self, x, mask=None):
         """``activate(x, False)`` for one chunk of a generation loop. 16-bit softmax outputs on the GPU take the
         in-tree row-softmax kernel (fp32 arithmetic, one rounding, as the activation's own path), so a cached
-        decoding step launches no library kernel; everything else is ``activate`` itself."""
+        decoding step launches no library kernel; everything else is ``activate`` itself. With
+        rnnSetWeightDataType the projection reads the quantised copy of W (``output()`` and ``fit()`` never do)."""
+        if self._wq_fmt is None:
+            return self._rnn_time_step(x)
+        self._wq_step = True
+        try:
+            return self._rnn_time_step(x)
+        finally:
+            self._wq_step = False
+
+    def _rnn_time_step(self, x):
         from ... import ops
         if not (x.is_cuda and self.has_params and isinstance(self.conf.activation, ActivationSoftmax) and
                 self.W("W").dtype in (torch.bfloat16, torch.float16) and ops.use_native(x, "softmax")):

@@ -852,20 +852,31 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         self._check_state_mb(x)
         B, E, T = x.shape
         xt = _token_major(x).to(self.W("Wqkv").dtype)
+        wq = self._wq_fmt is not None           # rnnSetWeightDataType: the dense products read the quantised copies
         if c.preNorm():
             xt = xt.contiguous()
             n1, _, _ = _rms_fwd(xt, None, self.params["ln1g"], c.layerNormEps)
-            qkv = matmul(n1, self.W("Wqkv"), bias=self.Wbias("bqkv"))
         else:
-            qkv = matmul(xt, self.W("Wqkv"), bias=self.Wbias("bqkv"))
+            n1 = xt
+        if wq:
+            qkv = self.wqLinear(n1, "Wqkv", self.Wbias("bqkv"))
+        else:
+            qkv = matmul(n1, self.W("Wqkv"), bias=self.Wbias("bqkv"))
         ctx = self.cachedAttention(qkv.reshape(B, T, -1), c.nHeads, Hkv=c.kvHeads(),
                                    ropeTheta=c.ropeTheta if c.rotary() else None,
                                    window=c.attentionWindow).reshape(B * T, -1)
-        a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
+        if wq:
+            a = self.wqLinear(ctx, "Wo", self.Wbias("bo"))
+        else:
+            a = matmul(ctx, self.W("Wo"), bias=self.Wbias("bo"))
         if c.preNorm():
             n2, h, _ = _rms_fwd(a, xt, self.params["ln2g"], c.layerNormEps, s_out=a)
             if c.nExperts is not None:
                 y = self._moe_fwd(n2, acc=h)[0]                 # y = h + f2: the add rides on the combine
+                y = y.reshape(B, T, E).permute(0, 2, 1)
+                return y[:, :, 0] if one else y
+            if wq:
+                y = self.wqLinear(self._ffn1_wq(n2), "W2", self.Wbias("b2"), out=h, beta=1.0)   # y = h + f·W2 + b2
                 y = y.reshape(B, T, E).permute(0, 2, 1)
                 return y[:, :, 0] if one else y
             f, _ = self._ffn1(n2, False)
@@ -875,14 +886,27 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
                 y = _add_into(h, matmul(f, self.W("W2"), bias=self.Wbias("b2")))
         else:
             h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
-            if c.nExperts is None:
+            if c.nExperts is not None:
+                f2 = self._moe_fwd(h1)[0]
+            elif wq:
+                f2 = self.wqLinear(self._ffn1_wq(h1), "W2", self.Wbias("b2"))
+            else:
                 f, _ = self._ffn1(h1, False)
                 f2 = matmul(f, self.W("W2"), bias=self.Wbias("b2"))
-            else:
-                f2 = self._moe_fwd(h1)[0]
             y, _ = _ln_fwd(f2, h1, self.params["ln2g"], self.params["ln2b"], c.layerNormEps)
         y = y.reshape(B, T, E).permute(0, 2, 1)
         return y[:, :, 0] if one else y
+
+    def wqKeys(self):
+        """The attention projections and the dense feed-forward matrices (the SwiGLU [Wg | Wu] is W1). Expert
+        matrices and the router stay 16-bit."""
+        return ("Wqkv", "Wo") + (("W1", "W2") if self.conf.nExperts is None else ())
+
+    def _ffn1_wq(self, h):
+        """``_ffn1`` of a decoding step on the quantised W1: GELU in the product's epilogue, or the SwiGLU gate."""
+        if self.conf.swiglu():
+            return _swiglu_fwd(self.wqLinear(h, "W1", self.Wbias("b1")))
+        return self.wqLinear(h, "W1", self.Wbias("b1"), act="gelu")
 
     def backpropGradient(self, eps, **kw):
         c = self.conf

@@ -52,6 +52,11 @@ def _run(cmd):
     return r.stdout
 
 
+# per-source flags: the weight-quantised GEMM is compiled without packed fp32 arithmetic (its fp32 math is the scalar
+# epilogue; the packed forms buy nothing there)
+EXTRA_FLAGS = {"gemm_wq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def build_kernels(verbose=True, jobs=None):
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(BUILD, exist_ok=True)
@@ -66,7 +71,8 @@ def build_kernels(verbose=True, jobs=None):
     flags = ["-O3", "-fPIC", f"--offload-arch={ARCH}", "-std=c++17", "-munsafe-fp-atomics", "-I", CSRC]
     jobs = jobs or min(8, os.cpu_count() or 4, 16)
     with cf.ThreadPoolExecutor(jobs) as ex:
-        futs = {ex.submit(_run, [HIPCC] + flags + ["-c", s, "-o", o]): s for s, o in todo}
+        futs = {ex.submit(_run, [HIPCC] + flags + EXTRA_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o]): s
+                for s, o in todo}
         for f in cf.as_completed(futs):
             f.result()
             if verbose:

@@ -55,6 +55,11 @@
              acceptance observed (random weights: no statement about trained models) and the break-even acceptance.
              With ``--model --tree PATH`` the plain generate() rows can be taken from the parent commit's checkout.
 
+  --weights fp8 [fp4]  weight-only quantised decoding: generate() and generate(useGraph=True) of the 12-layer,
+             hidden-768 model built with weightDataType against the same model with 16-bit weights (one network per
+             format, the same parameters), prefix 128 and 1024, the variants alternating within every pass; the step
+             alone from calls of two lengths and the share of greedy tokens equal to the 16-bit model's.
+
 Usage: python tools/bench_generate.py --sampler --gather --model [--out profiles/generation.txt]
        python tools/bench_generate.py --speculative 2,4,8 [--lookup] [--out profiles/speculative.txt]
        python tools/bench_generate.py --ragged [--parent-lib PATH] [--out profiles/ragged_generation.txt]
@@ -490,6 +495,53 @@ def cache_fp8_mode(batches, n, passes):
     say()
 
 
+def weights_mode(fmts, batches, n, passes):
+    """generate() and generate(useGraph=True) with weight-only quantised decoding (rnnSetWeightDataType) against the
+    16-bit weights of the same network, the variants alternating within a pass; the step alone from calls of two
+    lengths; the share of greedy tokens equal to the 16-bit model's."""
+    from deeplearning4j_amd.models import TextGenerationTransformer
+    from deeplearning4j_amd.nn.conf import DataType
+    V, MAXP = 77, 2048
+    nets = {f: TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=768, layers=12, heads=12,
+                                         maxPositions=MAXP, dataType=DataType.BFLOAT16,
+                                         weightDataType=f).init(device=DEV) for f in [None] + fmts}
+    say(f"== generate() with weight-only quantised decoding against 16-bit weights on TextGenerationTransformer(768, "
+        f"12 layers, 12 heads), bf16, V = {V}, greedy, {n} new tokens; whole calls (prompt included) on the host clock, "
+        f"ended by a device synchronise; median of {passes} passes (min .. max), the variants alternating within a "
+        "pass; one network per format from the same seed (the same parameters)")
+
+    def call(prompt, fmt, tokens=n, **kw):
+        nets[fmt].rnnClearPreviousState()
+        return nets[fmt].generate(prompt, maxNewTokens=tokens, **kw)
+
+    for mb in batches:
+        for P in (128, 1024):
+            prompt = torch.randint(0, V, (mb, P), generator=torch.Generator().manual_seed(mb + P)).to(DEV)
+            variants = [(f"{f or '16-bit'} {m}", f, kw) for m, kw in (("eager", {}), ("graph", dict(useGraph=True)))
+                        for f in [None] + fmts]
+            outs = [call(prompt, f, **kw).tokens for _, f, kw in variants]
+            few = max(2, n // 4)
+            for _, f, kw in variants:
+                call(prompt, f, few, **kw)
+            times, short = [[] for _ in variants], [[] for _ in variants]
+            for _ in range(passes):
+                for i, (_, f, kw) in enumerate(variants):
+                    times[i].append(_sync_time(lambda: call(prompt, f, **kw)))
+                    short[i].append(_sync_time(lambda: call(prompt, f, few, **kw)))
+            say(f"batch {mb:2d} prefix {P:4d}:")
+            base = {}
+            for i, (vn, f, kw) in enumerate(variants):
+                m, ms = sorted(times[i])[passes // 2], sorted(short[i])[passes // 2]
+                step = (m - ms) / (n - few) * 1e3
+                mode = vn.split()[1]
+                base.setdefault(mode, (m, step))
+                say(f"    {vn:13s}: {mb * n / m:9.1f} tok/s  {m * 1e3:8.1f} ms per call ({min(times[i]) * 1e3:.1f} .. "
+                    f"{max(times[i]) * 1e3:.1f})  step alone {step:6.3f} ms  vs 16-bit: tok/s {base[mode][0] / m:5.3f}x "
+                    f"step {base[mode][1] / step:5.3f}x  greedy tokens equal to 16-bit eager's: "
+                    f"{(outs[i] == outs[0]).float().mean().item() * 100:5.1f} %")
+    say()
+
+
 def kv_heads_mode(kv_heads, batches, n, passes):
     """generate() and generate(useGraph=True) of the 12-layer, hidden-768 model with nKVHeads key/value heads against
     the 12-head model: one network per head count (the projection shapes differ), the variants alternating."""
@@ -764,6 +816,9 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--cache", choices=["fp8"], default=None,
                     help="compare generate() with the fp8 key/value cache and with the 16-bit one")
+    ap.add_argument("--weights", choices=["fp8", "fp4"], nargs="+", default=None,
+                    help="weight-only quantised decoding (rnnSetWeightDataType) against 16-bit weights: generate() "
+                         "and useGraph=True at prefix 128 and 1024")
     ap.add_argument("--kv-heads", default=None,
                     help="grouped-query attention: nKVHeads values (divisors of 12, comma separated) against 12")
     ap.add_argument("--rotary", action="store_true",
@@ -805,6 +860,8 @@ def main():
         graph_mode(a.batch, a.tokens, a.passes, a.parent_lib)
     if a.cache:
         cache_fp8_mode(a.batch, a.tokens, a.passes)
+    if a.weights:
+        weights_mode(a.weights, a.batch, a.tokens, a.passes)
     if a.kv_heads:
         kv_heads_mode([int(h) for h in a.kv_heads.split(",")], a.batch, a.tokens, a.passes)
     if a.rotary:
