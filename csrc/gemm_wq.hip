@@ -26,6 +26,15 @@
 // (blockIdx.y); those partials go to an fp32 workspace [S][M][Np] and dl4j's merge launch sums them in split order and
 // applies the epilogue: no float atomics anywhere, two runs give the same bits. The launch geometry depends on
 // (bits, M, N, K) only and nothing is read back.
+//
+// dl4j_wq_gemm_grouped: the same block for the experts of a mixture-of-experts step of Ntok <= 64 tokens. The X packed
+// matrices lie one after another; the grid is (column blocks, X, S). Block (nb, e, s) reads cnt[e] / off[e] of the
+// routing plan (csrc/moe.hip) on the device: an expert without assignments leaves before its first weight load, the
+// others multiply only the first ceil(cnt[e] / 16) of the MF = ceil(Ntok / 16) column fragments (a token's experts are
+// distinct, so cnt[e] <= Ntok). Panel row r is either gathered, x[src_of[off[e] + r] / k] of the token-major
+// activations (no gathered copy and no gather launch), or row off[e] + r of an expert-sorted buffer; rows from cnt[e]
+// on are zeros. Output row off[e] + r of the expert-sorted buffer, live rows only. Split-K partials are kept for live
+// rows only, [S][Ntok * k][Np] at the compact row (exclusive prefix of cnt)[e] + r, and merged in split order.
 #include "common.h"
 #include "mfma_tile.h"
 
@@ -246,6 +255,153 @@ __global__ __launch_bounds__(256) void wq_merge_kernel(const float* __restrict__
   wq_epilogue<hb>(epi, s, m, n, N);
 }
 
+// The routing plan of csrc/moe.hip as the grouped product reads it (device pointers, int32).
+struct WqPlan {
+  const int* cnt;      // [X] assignments per expert
+  const int* off;      // [X + 1] first row of every expert's segment of the sorted buffers
+  const int* src_of;   // [Rcap] assignment n*k + j of a live row; read in gather mode only
+  int Ntok, k, X, A;   // A = Ntok * k
+  long long Rcap;
+};
+
+// Block (nb, e, s) of the grouped product: wq_gemm_kernel's body on expert e's packed matrix, over the expert's live
+// rows only. rows = cnt[e], held to the MF fragments and to the sorted buffer whatever the plan holds.
+template <int BITS, typename hb, int MF, bool GATHER>
+__global__ __launch_bounds__(256) void wq_gemm_grouped_kernel(const uint4* __restrict__ codes,
+                                                              const unsigned char* __restrict__ scales,
+                                                              long long cstride, long long sstride,
+                                                              const hb* __restrict__ x, int ldx, WqPlan p, int N, int K,
+                                                              int KTn, int cpb, float* __restrict__ ws, WqEpi epi) {
+  using F = WqFmt<BITS>;
+  constexpr int CT = F::CT, CW = 16 * CT;
+  __shared__ __attribute__((aligned(16))) hb xs[MF * 16 * WQ_LDX];        // reused for the wave reduction below
+  __shared__ int rowsrc[MF * 16];                                          // the x row of panel row r, -1: zeros
+  static_assert(sizeof(hb) * MF * 16 * WQ_LDX >= 4 * CT * MF * 64 * sizeof(wq_f4), "reduction fits the x panel");
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, c = lane & 15;
+  const int nb = blockIdx.x, e = blockIdx.y;
+  const int off = p.off[e];
+  const long long room = p.Rcap - off;
+  const int rows = off < 0 ? 0 : (int)min((long long)min(p.cnt[e], MF * 16), room);
+  if (rows <= 0) return;                                                   // block-uniform: no byte of an idle expert
+  const int mfl = (rows + 15) >> 4;                                        // live fragments
+  codes += (long long)e * cstride;
+  scales += (long long)e * sstride;
+  if (tid < MF * 16) {
+    int src = -1;
+    if (tid < rows) {
+      if (GATHER) {
+        const int a = p.src_of[off + tid];
+        src = (a >= 0 && a < p.A) ? a / p.k : -1;
+      } else {
+        src = off + tid;
+      }
+    }
+    rowsrc[tid] = src;
+  }
+  const int NC = (KTn + 3) >> 2;
+  const int ch0 = blockIdx.z * cpb, ch1 = min(NC, ch0 + cpb);
+  wq_f4 acc[CT][MF];
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int f = 0; f < MF; ++f) acc[ct][f] = wq_f4{0.f, 0.f, 0.f, 0.f};
+
+  for (int ch = ch0; ch < ch1; ++ch) {
+    const int kt = ch * 4 + wave;
+    const bool live = kt < KTn;                                        // wave-uniform
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    unsigned sc = 0x7f7f7f7fu;
+    if (live) {
+      const long long tile = (long long)nb * KTn + kt;
+      w = codes[tile * 64 + lane];
+      sc = F::load_scales(scales + (tile * 16 + c) * (CT * 2));
+    }
+    __syncthreads();                                                   // rowsrc is there; the previous chunk is read
+    const int kc = ch * WQ_KC;
+    for (int i = tid; i < mfl * 16 * (WQ_KC / 8); i += 256) {
+      const int r = i >> 5, k8 = (i & 31) * 8;
+      const int src = rowsrc[r];
+      WV8<hb> v = WV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+      if (src >= 0 && kc + k8 < K) v = *reinterpret_cast<const WV8<hb>*>(x + (long long)src * ldx + kc + k8);
+      *reinterpret_cast<WV8<hb>*>(xs + r * WQ_LDX + k8) = v;
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int koff = wave * WQ_KT + j * 32 + q * 8;
+        WV8<hb> b[MF];
+#pragma unroll
+        for (int f = 0; f < MF; ++f) {
+          b[f] = WV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+          if (f < mfl) b[f] = *reinterpret_cast<const WV8<hb>*>(xs + (f * 16 + c) * WQ_LDX + koff);
+        }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+          const WV8<hb> a = F::template frag<hb>(w, sc, ct, j);
+#pragma unroll
+          for (int f = 0; f < MF; ++f)
+            if (f < mfl) acc[ct][f] = wq_mma(a, b[f], acc[ct][f]);     // block-uniform: dead fragments cost nothing
+        }
+      }
+    }
+  }
+  // the four waves' sums, in wave order
+  __syncthreads();
+  wq_f4* red = reinterpret_cast<wq_f4*>(xs);
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int f = 0; f < MF; ++f) red[((wave * CT + ct) * MF + f) * 64 + lane] = acc[ct][f];
+  __syncthreads();
+  const int Np = gridDim.x * CW;
+  int pre = 0;                                                           // the compact row of the expert's first
+  if (gridDim.z > 1)
+    for (int i = 0; i < e; ++i) pre += p.cnt[i];
+  WqEpi le = epi;
+  if (epi.bias) le.bias = reinterpret_cast<const float*>(epi.bias) + (long long)e * N;
+  for (int idx = tid; idx < CT * mfl * 64; idx += 256) {
+    const int l = idx & 63, f = (idx >> 6) % mfl, ct = (idx >> 6) / mfl;
+    wq_f4 s = red[((0 * CT + ct) * MF + f) * 64 + l];
+#pragma unroll
+    for (int wv = 1; wv < 4; ++wv) s += red[((wv * CT + ct) * MF + f) * 64 + l];
+    const int m = f * 16 + (l & 15), n = nb * CW + ct * 16 + 4 * (l >> 4);
+    if (m >= rows) continue;
+    if (gridDim.z > 1) {
+      const int cr = pre + m;
+      if (cr >= 0 && cr < p.A) *reinterpret_cast<wq_f4*>(ws + ((long long)blockIdx.z * p.A + cr) * Np + n) = s;
+    } else {
+      wq_epilogue<hb>(le, s, off + m, n, N);
+    }
+  }
+}
+
+// split-K merge of the grouped product: compact row cr belongs to the expert e whose prefix of cnt covers it; the S
+// partial planes [A, Np] summed in split order, then the epilogue into row off[e] + r
+template <typename hb>
+__global__ __launch_bounds__(256) void wq_merge_grouped_kernel(const float* __restrict__ ws, int S, WqPlan p, int mrows,
+                                                               int N, int Np, WqEpi epi) {
+  const int q4 = Np >> 2;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.A * q4) return;
+  const int cr = idx / q4, n = (idx - cr * q4) * 4;
+  if (n >= N) return;
+  int e = 0, run = 0;
+  for (; e < p.X; ++e) {
+    const int ce = p.cnt[e];
+    if (cr < run + ce) break;
+    run += ce;
+  }
+  if (e >= p.X) return;
+  const int r = cr - run, off = p.off[e];
+  if (r < 0 || r >= mrows || off < 0 || (long long)off + r >= p.Rcap) return;     // what the product's blocks wrote
+  wq_f4 s = *reinterpret_cast<const wq_f4*>(ws + (long long)cr * Np + n);
+  for (int sp = 1; sp < S; ++sp) s += *reinterpret_cast<const wq_f4*>(ws + ((long long)sp * p.A + cr) * Np + n);
+  WqEpi le = epi;
+  if (epi.bias) le.bias = reinterpret_cast<const float*>(epi.bias) + (long long)e * N;
+  wq_epilogue<hb>(le, s, off + r, n, N);
+}
+
 // One wave per tile (nb, kt): W [K, N] with element strides (sk, sn) -> the tile's 1024 code bytes and scale bytes.
 // A group's 32 values sit in the four lanes q = 0..3 of a column c: its maximum is two cross-lane exchanges.
 template <int BITS, typename hb>
@@ -337,6 +493,27 @@ void wq_split(int bits, int M, int N, int K, int* S, int* cpb) {
   *S = (NC + *cpb - 1) / *cpb;
 }
 
+// wq_split for the grouped product, from (bits, Ntok, k, X, N, K) alone: min(X, Ntok * k) experts count as active (the
+// blocks of the others leave at once), and the partials of the Ntok * k live rows are weighed against those experts'
+// weight bytes
+void wq_split_grouped(int bits, int Ntok, int k, int X, int N, int K, int* S, int* cpb) {
+  const int nbk = (N + wq_cw(bits) - 1) / wq_cw(bits);
+  const int NC = ((K + WQ_KT - 1) / WQ_KT + 3) / 4;
+  const int A = Ntok * k, active = X < A ? X : A;
+  const long long blocks = (long long)nbk * active;
+  long long s = (512 + blocks - 1) / blocks;
+  const long long cap = (long long)active * K * bits / (64LL * A);
+  if (s > cap) s = cap;
+  if (s > NC) s = NC;
+  if (s < 1) s = 1;
+  *cpb = (NC + (int)s - 1) / (int)s;
+  *S = (NC + *cpb - 1) / *cpb;
+}
+
+inline bool wq_grouped_ok(int bits, int Ntok, int k, int X, long long N, long long K) {
+  return wq_shape_ok(bits, K, N) && Ntok >= 1 && Ntok <= 64 && k >= 1 && k <= 8 && X >= 1 && X <= 64 && k <= X;
+}
+
 }  // namespace
 
 // Bytes of the packed codes and of the scales of W [K, N] in format `bits` (8 / 4); -1: a shape the format refuses
@@ -426,5 +603,71 @@ DL4J_API int dl4j_wq_gemm(int bits, int dtype, const void* x, long long ldx, int
   const dim3 mg((unsigned)(((long long)M * (Np / 4) + 255) / 256));
   if (dtype == 1) hipLaunchKernelGGL(wq_merge_kernel<__bf16>, mg, dim3(256), 0, s, (const float*)ws, S, M, (int)N, Np, epi);
   else hipLaunchKernelGGL(wq_merge_kernel<_Float16>, mg, dim3(256), 0, s, (const float*)ws, S, M, (int)N, Np, epi);
+  return (int)hipGetLastError();
+}
+
+// Floats of split-K workspace dl4j_wq_gemm_grouped needs for (bits, Ntok, k, X, N, K): 0 when the product runs
+// unsplit, -1 for a shape it refuses.
+DL4J_API long long dl4j_wq_gemm_grouped_workspace(int bits, int Ntok, int k, int X, long long N, long long K) {
+  if (!wq_grouped_ok(bits, Ntok, k, X, N, K)) return -1;
+  int S, cpb;
+  wq_split_grouped(bits, Ntok, k, X, (int)N, (int)K, &S, &cpb);
+  const long long Np = (N + wq_cw(bits) - 1) / wq_cw(bits) * wq_cw(bits);
+  return S > 1 ? (long long)S * Ntok * k * Np : 0;
+}
+
+// The experts' products of a mixture-of-experts step of Ntok <= 64 tokens on X packed matrices [K, N] (expert e's codes
+// at codes + e * code_stride bytes, its scales at scales + e * scale_stride; strides multiples of 16, at least
+// dl4j_wq_packed_bytes): out[off[e] + r] = act(row_r · deq(W_e) + bias[e]) for r < cnt[e], with cnt [X], off [X + 1]
+// and src_of [Rcap] the plan of dl4j_moe_route for (Ntok, k, X). gather 1: row_r = x[src_of[off[e] + r] / k], x the
+// token-major activations [Ntok, ldx]; gather 0: row_r = x[off[e] + r], x an expert-sorted buffer [Rcap, ldx] (src_of
+// may be null). out [Rcap, ldo]: pad rows and the segments of idle experts are not written. dtype 1 bf16 / 2 fp16;
+// bias fp32 [X, N] or null; act 0 none / 4 GELU; ws: the floats dl4j_wq_gemm_grouped_workspace asks for (may be null
+// when 0). The plan is read on the device only. -1: refused (shape, Ntok > 64, alignment, dtype), nothing launched.
+DL4J_API int dl4j_wq_gemm_grouped(int bits, int dtype, const void* x, long long ldx, int gather, int Ntok, int k, int X,
+                                  long long Rcap, long long N, long long K, const void* codes, const void* scales,
+                                  long long code_stride, long long scale_stride, const int* cnt, const int* off,
+                                  const int* src_of, void* out, long long ldo, const float* bias, int act, void* ws,
+                                  hipStream_t s) {
+  if (!wq_grouped_ok(bits, Ntok, k, X, N, K) || (dtype != 1 && dtype != 2) || (gather != 0 && gather != 1)) return -1;
+  long long cb, sb;
+  dl4j_wq_packed_bytes(bits, K, N, &cb, &sb);
+  if (code_stride < cb || code_stride % 16 || scale_stride < sb || scale_stride % 16) return -1;
+  if (!wq_al16(x) || ldx % 8 != 0 || ldx < K || ldx > 0x7fffffffLL || !wq_al16(codes) || !wq_al16(scales)) return -1;
+  if (!out || ldo < N || ldo > 0x7fffffffLL || Rcap < (long long)Ntok * k || Rcap > 0x7fffffffLL) return -1;
+  const auto al4 = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
+  if (!al4(cnt) || !al4(off) || (gather && !al4(src_of)) || (bias && !al4(bias)) || (act != 0 && act != 4)) return -1;
+  int S, cpb;
+  wq_split_grouped(bits, Ntok, k, X, (int)N, (int)K, &S, &cpb);
+  if (S > 1 && !wq_al16(ws)) return -1;
+  const int KTn = (int)((K + WQ_KT - 1) / WQ_KT), cw = wq_cw(bits);
+  const int nbk = (int)((N + cw - 1) / cw);
+  const WqEpi epi{out, bias, (int)ldo, 0, 0, act};
+  const WqPlan plan{cnt, off, src_of, Ntok, k, X, Ntok * k, Rcap};
+  const dim3 grid((unsigned)nbk, (unsigned)X, (unsigned)S);
+  const int mf = Ntok <= 16 ? 1 : (Ntok <= 32 ? 2 : 4);
+#define L(B, T, F, G) hipLaunchKernelGGL((wq_gemm_grouped_kernel<B, T, F, G>), grid, dim3(256), 0, s,                \
+                                         (const uint4*)codes, (const unsigned char*)scales, code_stride / 16,        \
+                                         scale_stride, (const T*)x, (int)ldx, plan, (int)N, (int)K, KTn, cpb,        \
+                                         (float*)ws, epi)
+#define LG(B, T, F) do { if (gather) L(B, T, F, true); else L(B, T, F, false); } while (0)
+#define LM(B, T) do { if (mf == 1) LG(B, T, 1); else if (mf == 2) LG(B, T, 2); else LG(B, T, 4); } while (0)
+  if (bits == 8 && dtype == 1) LM(8, __bf16);
+  else if (bits == 8) LM(8, _Float16);
+  else if (dtype == 1) LM(4, __bf16);
+  else LM(4, _Float16);
+#undef LM
+#undef LG
+#undef L
+  int rc = (int)hipGetLastError();
+  if (rc != 0 || S == 1) return rc;
+  const int Np = nbk * cw;
+  const dim3 mg((unsigned)(((long long)plan.A * (Np / 4) + 255) / 256));
+  if (dtype == 1)
+    hipLaunchKernelGGL(wq_merge_grouped_kernel<__bf16>, mg, dim3(256), 0, s, (const float*)ws, S, plan, mf * 16, (int)N,
+                       Np, epi);
+  else
+    hipLaunchKernelGGL(wq_merge_grouped_kernel<_Float16>, mg, dim3(256), 0, s, (const float*)ws, S, plan, mf * 16,
+                       (int)N, Np, epi);
   return (int)hipGetLastError();
 }

@@ -974,12 +974,15 @@ class TextGenerationTransformer(ZooModel):
     def __init__(self, numLabels=77, seed=12345, inputShape=None, hidden=256, layers=4, heads=4, ffn=None,
                  maxPositions=512, learningRate=1e-3, cacheDataType=None, nKVHeads=None, positionEncoding=None,
                  ropeTheta=10000.0, normalization="layer", normPlacement="post", ffnActivation="gelu",
-                 attentionWindow=None, nExperts=None, nExpertsPerToken=2, weightDataType=None, **kw):
+                 attentionWindow=None, nExperts=None, nExpertsPerToken=2, weightDataType=None,
+                 expertWeightDataType=None, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
         # None, "fp8" or "fp4": weight-only quantised decoding (net.rnnSetWeightDataType, applied by init()). It is
         # runtime state of the network, not part of the configuration, so the JSON never carries it
         self.weightDataType = weightDataType
+        # the same for the expert matrices of mixture-of-experts blocks (rnnSetWeightDataType(..., experts=))
+        self.expertWeightDataType = expertWeightDataType
         self.ffn = int(ffn) if ffn else 4 * hidden
         self.maxPositions, self.learningRate = maxPositions, learningRate
         self.cacheDataType = cacheDataType      # None, or "fp8": the key/value cache format of every block
@@ -1058,8 +1061,8 @@ class TextGenerationTransformer(ZooModel):
     def init(self, device=None):
         net = ComputationGraph(self.conf())
         net.init(device=device)
-        if self.weightDataType is not None:
-            net.rnnSetWeightDataType(self.weightDataType)
+        if self.weightDataType is not None or self.expertWeightDataType is not None:
+            net.rnnSetWeightDataType(self.weightDataType, experts=self.expertWeightDataType)
         return net
 
 

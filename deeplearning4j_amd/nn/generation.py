@@ -197,31 +197,36 @@ def set_cache_data_type(named, value):
         l.conf.cacheDataType = value
 
 
-def set_weight_data_type(named, value):
-    """rnnSetWeightDataType of a network over its (label, layer) pairs: every matrix of ``layer.wqKeys()`` is
-    validated (the value, nIn % 32 == 0, finite: one read-back for the whole network), then every layer takes the
-    format and drops the copies it held; they are quantised at their first use."""
-    if value is not None and value not in ("fp8", "fp4"):
-        raise DL4JInvalidConfigException(
-            f"rnnSetWeightDataType: None (the compute dtype), \"fp8\" or \"fp4\", got {value!r}")
-    todo = [(label, l) for label, l in named if getattr(l, "wqKeys", tuple)()]
-    if value is not None:
-        finite = []
-        for label, l in todo:
-            for k in l.wqKeys():
-                if l.params[k].shape[0] % 32:
-                    raise DL4JInvalidConfigException(
-                        f"rnnSetWeightDataType: {label} ({type(l.conf).__name__}) parameter {k!r} has nIn = "
-                        f"{l.params[k].shape[0]}; the groups of 32 need nIn % 32 == 0")
-                finite.append((label, l, k, torch.isfinite(l.params[k]).all()))
-        bad = torch.stack([f for _, _, _, f in finite]).logical_not().tolist() if finite else []
-        for (label, l, k, _), b in zip(finite, bad):
-            if b:
-                raise DL4JInvalidInputException(
-                    f"rnnSetWeightDataType: {label} ({type(l.conf).__name__}) parameter {k!r} holds a non-finite "
-                    "weight")
+def set_weight_data_type(named, value, experts=None):
+    """rnnSetWeightDataType of a network over its (label, layer) pairs: every matrix of ``layer.wqKeys()`` under
+    ``value`` and every expert matrix of ``layer.wqExpertKeys()`` under ``experts`` is validated (the value, nIn % 32
+    == 0 (per expert for the experts), finite: one read-back for the whole network), then every layer takes both
+    formats and drops the copies it held; they are quantised at their first use."""
+    for what, v in (("", value), (" experts", experts)):
+        if v is not None and v not in ("fp8", "fp4"):
+            raise DL4JInvalidConfigException(
+                f"rnnSetWeightDataType{what}: None (the compute dtype), \"fp8\" or \"fp4\", got {v!r}")
+    todo = [(label, l) for label, l in named
+            if getattr(l, "wqKeys", tuple)() or getattr(l, "wqExpertKeys", tuple)()]
+    finite = []
+    for label, l in todo:
+        keys = [(k, 1) for k in (l.wqKeys() if value is not None else ())]
+        keys += [(k, l.conf.nExperts) for k in (l.wqExpertKeys() if experts is not None else ())]
+        for k, X in keys:
+            nin = l.params[k].shape[0] // X
+            if nin % 32:
+                raise DL4JInvalidConfigException(
+                    f"rnnSetWeightDataType: {label} ({type(l.conf).__name__}) parameter {k!r} has nIn = "
+                    f"{nin}{' per expert' if X > 1 else ''}; the groups of 32 need nIn % 32 == 0")
+            finite.append((label, l, k, torch.isfinite(l.params[k]).all()))
+    bad = torch.stack([f for _, _, _, f in finite]).logical_not().tolist() if finite else []
+    for (label, l, k, _), b in zip(finite, bad):
+        if b:
+            raise DL4JInvalidInputException(
+                f"rnnSetWeightDataType: {label} ({type(l.conf).__name__}) parameter {k!r} holds a non-finite "
+                "weight")
     for _, l in todo:
-        l.wqSetFormat(value)
+        l.wqSetFormat(value, experts)
 
 
 def _labelled(label, fn, *a, **kw):

@@ -784,12 +784,14 @@ class ComputationGraph(BaseNetwork):
         from ..generation import set_cache_data_type
         set_cache_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value)
 
-    def rnnSetWeightDataType(self, value):
-        """Weight-only quantised decoding, as MultiLayerNetwork.rnnSetWeightDataType: None, "fp8" or "fp4" for the
-        weight matrices rnnTimeStep reads in TransformerEncoderLayer (not its experts or router) and RnnOutputLayer.
-        Refused, naming the vertex and changing nothing, for an unknown value, nIn % 32 != 0 or a non-finite weight."""
+    def rnnSetWeightDataType(self, value, experts=None):
+        """Weight-only quantised decoding, as MultiLayerNetwork.rnnSetWeightDataType: ``value`` None, "fp8" or "fp4"
+        for the weight matrices rnnTimeStep reads in TransformerEncoderLayer and RnnOutputLayer, ``experts`` the same
+        for the expert matrices W1 / W2 of mixture-of-experts blocks (never the router); every call sets both.
+        Refused, naming the vertex and changing nothing, for an unknown value, nIn % 32 != 0 (per expert for the
+        experts) or a non-finite weight."""
         from ..generation import set_weight_data_type
-        set_weight_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value)
+        set_weight_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value, experts)
 
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32

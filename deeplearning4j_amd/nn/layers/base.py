@@ -128,6 +128,7 @@ class LayerImpl:
     # remembers the weight version it was made from (ops.conv_native.WEIGHT_VERSION, bumped by every update of the
     # network's parameters or compute copies) and is requantised on its next use after that moved on.
     _wq_fmt = None        # None, "fp8" or "fp4"
+    _wq_expert_fmt = None     # the same for the matrices of wqExpertKeys(), independent of _wq_fmt
     _wq = None            # key -> (weight version, QuantWeight)
     _wq_step = False      # an output layer inside an rnnTimeStep whose projection reads the quantised W
 
@@ -135,8 +136,13 @@ class LayerImpl:
         """The weight matrices [nIn, nOut] this layer's rnnTimeStep reads quantised (none by default)."""
         return ()
 
-    def wqSetFormat(self, fmt):
-        self._wq_fmt, self._wq = fmt, {}
+    def wqExpertKeys(self):
+        """The stacked expert matrices [X * nIn, nOut] this layer's rnnTimeStep reads quantised per expert (none by
+        default)."""
+        return ()
+
+    def wqSetFormat(self, fmt, experts=None):
+        self._wq_fmt, self._wq_expert_fmt, self._wq = fmt, experts, {}
 
     def wqWeight(self, key):
         from ...ops import conv_native, transformer_native as TN
@@ -145,6 +151,18 @@ class LayerImpl:
         if ent is None or ent[0] != v:
             with torch.no_grad():
                 ent = self._wq[key] = (v, TN.wq_quantize(self.W(key), self._wq_fmt))
+        return ent[1]
+
+    def wqExperts(self, key, X):
+        """The QuantExperts of the stacked expert parameter ``key`` [X * nIn, nOut], requantised as wqWeight's."""
+        from ...ops import conv_native, transformer_native as TN
+        v = conv_native.WEIGHT_VERSION[0]
+        ent = self._wq.get(("experts", key))
+        if ent is None or ent[0] != v:
+            W = self.W(key)
+            with torch.no_grad():
+                qe = TN.wq_quantize_experts(W.view(X, W.shape[0] // X, W.shape[1]), self._wq_expert_fmt)
+            ent = self._wq[("experts", key)] = (v, qe)
         return ent[1]
 
     def wqLinear(self, x, key, bias=None, act=None, out=None, beta=0.0):

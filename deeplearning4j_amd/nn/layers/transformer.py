@@ -745,19 +745,29 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         z1 = torch.empty(h.shape[0], self.W("W1").shape[1], dtype=h.dtype, device=h.device)
         return matmul(h, self.W("W1"), bias=self.Wbias("b1"), act="gelu", z=z1), z1
 
-    def _moe_fwd(self, n, acc=None):
+    def _moe_fwd(self, n, acc=None, step=False):
         """The sparse feed-forward of n [N, E] -> (f2 [N, E] (+ ``acc``, written over it on the kernels), ctx =
-        (plan, gate, Xp, Z1p, Fp, Yp) for ``_moe_bwd``)."""
+        (plan, gate, Xp, Z1p, Fp, Yp) for ``_moe_bwd``). ``step``: the call of an rnnTimeStep, whose two grouped
+        products read the quantised experts when the layer holds an expert format (the first gathers its rows by
+        the plan itself, so there is no Xp)."""
+        from ...ops import transformer_native as TN
         c = self.conf
         X, k, E = c.nExperts, c.nExpertsPerToken, n.shape[1]
         sixteen = n.dtype in (torch.bfloat16, torch.float16)
         logits = mmul(n, self.W("Wr"), out_dtype=torch.float32 if sixteen else None)
         plan, gate = _moe_op("moe_route", n, logits, k)
-        W1, W2 = self.W("W1"), self.W("W2")
-        xp = _moe_op("moe_gather", n, n, plan)
-        z1p = _moe_op("gemm_grouped", n, xp, W1.view(X, E, -1), _moe_bias(self.Wbias("b1")), plan)
-        fp = _swiglu_fwd(z1p) if c.swiglu() else _gelu_fwd(z1p)
-        yp = _moe_op("gemm_grouped", n, fp, W2.view(X, -1, E), _moe_bias(self.Wbias("b2")), plan)
+        if step and self._wq_expert_fmt is not None:
+            xp = None
+            z1p = TN.wq_grouped_linear(n, self.wqExperts("W1", X), _moe_bias(self.Wbias("b1")), plan, True,
+                                       None if c.swiglu() else "gelu")
+            fp = _swiglu_fwd(z1p) if c.swiglu() else z1p
+            yp = TN.wq_grouped_linear(fp, self.wqExperts("W2", X), _moe_bias(self.Wbias("b2")), plan, False)
+        else:
+            W1, W2 = self.W("W1"), self.W("W2")
+            xp = _moe_op("moe_gather", n, n, plan)
+            z1p = _moe_op("gemm_grouped", n, xp, W1.view(X, E, -1), _moe_bias(self.Wbias("b1")), plan)
+            fp = _swiglu_fwd(z1p) if c.swiglu() else _gelu_fwd(z1p)
+            yp = _moe_op("gemm_grouped", n, fp, W2.view(X, -1, E), _moe_bias(self.Wbias("b2")), plan)
         if acc is not None and _native(n, "moe"):
             f2 = _moe_op("moe_combine", n, yp, plan, gate, acc, out=acc)
         else:
@@ -872,7 +882,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         if c.preNorm():
             n2, h, _ = _rms_fwd(a, xt, self.params["ln2g"], c.layerNormEps, s_out=a)
             if c.nExperts is not None:
-                y = self._moe_fwd(n2, acc=h)[0]                 # y = h + f2: the add rides on the combine
+                y = self._moe_fwd(n2, acc=h, step=True)[0]      # y = h + f2: the add rides on the combine
                 y = y.reshape(B, T, E).permute(0, 2, 1)
                 return y[:, :, 0] if one else y
             if wq:
@@ -887,7 +897,7 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         else:
             h1, _ = _ln_fwd(a, xt, self.params["ln1g"], self.params["ln1b"], c.layerNormEps)
             if c.nExperts is not None:
-                f2 = self._moe_fwd(h1)[0]
+                f2 = self._moe_fwd(h1, step=True)[0]
             elif wq:
                 f2 = self.wqLinear(self._ffn1_wq(h1), "W2", self.Wbias("b2"))
             else:
@@ -901,6 +911,11 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         """The attention projections and the dense feed-forward matrices (the SwiGLU [Wg | Wu] is W1). Expert
         matrices and the router stay 16-bit."""
         return ("Wqkv", "Wo") + (("W1", "W2") if self.conf.nExperts is None else ())
+
+    def wqExpertKeys(self):
+        """The stacked expert matrices W1 [X*E, F1] and W2 [X*F, E] of a mixture-of-experts block, quantised per
+        expert under the network's expert format (the router and the biases stay as they are)."""
+        return ("W1", "W2") if self.conf.nExperts is not None else ()
 
     def _ffn1_wq(self, h):
         """``_ffn1`` of a decoding step on the quantised W1: GELU in the product's epilogue, or the SwiGLU gate."""

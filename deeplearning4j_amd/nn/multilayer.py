@@ -483,20 +483,24 @@ class MultiLayerNetwork(BaseNetwork):
         from .generation import set_cache_data_type
         set_cache_data_type([(f"layer {i}", l) for i, l in enumerate(self.layers)], value)
 
-    def rnnSetWeightDataType(self, value):
+    def rnnSetWeightDataType(self, value, experts=None):
         """Weight-only quantised decoding: None (the compute dtype, the default), "fp8" (MXFP8: e4m3fn codes, 8.25
         bits per weight) or "fp4" (MXFP4: e2m1 codes, 4.25 bits), with one power-of-two scale per 32 consecutive nIn
-        of an output column. It covers the matrices a decoding step reads: Wqkv, Wo and the dense W1 / W2 (the SwiGLU
-        [Wg | Wu] included) of every TransformerEncoderLayer and W of every RnnOutputLayer. Mixture-of-experts expert
-        matrices and the router stay 16-bit, as do all other layer types.
+        of an output column. ``value`` covers the matrices a decoding step reads: Wqkv, Wo and the dense W1 / W2 (the
+        SwiGLU [Wg | Wu] included) of every TransformerEncoderLayer and W of every RnnOutputLayer. ``experts`` (the
+        same three values, independent of ``value``) covers the expert matrices W1 [X*E, F1] and W2 [X*F, E] of every
+        mixture-of-experts TransformerEncoderLayer, each expert quantised on its own; without experts it is a no-op.
+        Every call sets both formats, so a call without ``experts`` returns the experts to 16 bits. The router, the
+        biases and all other layer types stay as they are.
 
         Only rnnTimeStep (and with it generate() in every mode) reads the quantised copies; output(), fit() and the
         backward pass never see them. The copies are derived state: they are requantised after every parameter
         update, are not serialised, and the master parameters stay in memory, so this cuts the bytes a step reads,
         not the size of the model. Refused, naming the layer and before any layer is changed, for an unknown value,
-        a matrix whose nIn is not a multiple of 32, or a non-finite weight (one read-back here)."""
+        a matrix whose nIn (per expert for the experts) is not a multiple of 32, or a non-finite weight (one
+        read-back here)."""
         from .generation import set_weight_data_type
-        set_weight_data_type([(f"layer {i}", l) for i, l in enumerate(self.layers)], value)
+        set_weight_data_type([(f"layer {i}", l) for i, l in enumerate(self.layers)], value, experts)
 
     def rnnReorderState(self, parents, groupSize=None):
         """Row i of every layer's stored rnnTimeStep state becomes the old row ``parents[i]`` (``parents``: int32

@@ -55,6 +55,9 @@
              acceptance observed (random weights: no statement about trained models) and the break-even acceptance.
              With ``--model --tree PATH`` the plain generate() rows can be taken from the parent commit's checkout.
 
+  --experts fp8 [fp4]  the same comparison for quantised mixture-of-experts experts (expertWeightDataType) on the
+             12-layer model with 8 experts, k = 2 and ffnSize 2048 (rotary / rms / pre / swiglu).
+
   --weights fp8 [fp4]  weight-only quantised decoding: generate() and generate(useGraph=True) of the 12-layer,
              hidden-768 model built with weightDataType against the same model with 16-bit weights (one network per
              format, the same parameters), prefix 128 and 1024, the variants alternating within every pass; the step
@@ -495,17 +498,23 @@ def cache_fp8_mode(batches, n, passes):
     say()
 
 
-def weights_mode(fmts, batches, n, passes):
+def weights_mode(fmts, batches, n, passes, experts=False):
     """generate() and generate(useGraph=True) with weight-only quantised decoding (rnnSetWeightDataType) against the
     16-bit weights of the same network, the variants alternating within a pass; the step alone from calls of two
-    lengths; the share of greedy tokens equal to the 16-bit model's."""
+    lengths; the share of greedy tokens equal to the 16-bit model's. ``experts``: the 8-expert model of
+    tools/bench_moe.py --model with the format on its experts only (expertWeightDataType)."""
     from deeplearning4j_amd.models import TextGenerationTransformer
     from deeplearning4j_amd.nn.conf import DataType
     V, MAXP = 77, 2048
+    kind = dict(ffn=2048, nExperts=8, nExpertsPerToken=2, positionEncoding="rotary", normalization="rms",
+                normPlacement="pre", ffnActivation="swiglu") if experts else {}
+    key = "expertWeightDataType" if experts else "weightDataType"
     nets = {f: TextGenerationTransformer(numLabels=V, inputShape=[128], hidden=768, layers=12, heads=12,
                                          maxPositions=MAXP, dataType=DataType.BFLOAT16,
-                                         weightDataType=f).init(device=DEV) for f in [None] + fmts}
-    say(f"== generate() with weight-only quantised decoding against 16-bit weights on TextGenerationTransformer(768, "
+                                         **kind, **{key: f}).init(device=DEV) for f in [None] + fmts}
+    what = "quantised experts (8 experts, k = 2, ffnSize 2048, rotary / rms / pre / swiglu) against 16-bit experts" \
+        if experts else "weight-only quantised decoding against 16-bit weights"
+    say(f"== generate() with {what} on TextGenerationTransformer(768, "
         f"12 layers, 12 heads), bf16, V = {V}, greedy, {n} new tokens; whole calls (prompt included) on the host clock, "
         f"ended by a device synchronise; median of {passes} passes (min .. max), the variants alternating within a "
         "pass; one network per format from the same seed (the same parameters)")
@@ -819,6 +828,9 @@ def main():
     ap.add_argument("--weights", choices=["fp8", "fp4"], nargs="+", default=None,
                     help="weight-only quantised decoding (rnnSetWeightDataType) against 16-bit weights: generate() "
                          "and useGraph=True at prefix 128 and 1024")
+    ap.add_argument("--experts", choices=["fp8", "fp4"], nargs="+", default=None,
+                    help="quantised mixture-of-experts experts (rnnSetWeightDataType(None, experts=)) against 16-bit "
+                         "experts on the 12-layer 8-expert model: generate() and useGraph=True at prefix 128 and 1024")
     ap.add_argument("--kv-heads", default=None,
                     help="grouped-query attention: nKVHeads values (divisors of 12, comma separated) against 12")
     ap.add_argument("--rotary", action="store_true",
@@ -862,6 +874,8 @@ def main():
         cache_fp8_mode(a.batch, a.tokens, a.passes)
     if a.weights:
         weights_mode(a.weights, a.batch, a.tokens, a.passes)
+    if a.experts:
+        weights_mode(a.experts, a.batch, a.tokens, a.passes, experts=True)
     if a.kv_heads:
         kv_heads_mode([int(h) for h in a.kv_heads.split(",")], a.batch, a.tokens, a.passes)
     if a.rotary:

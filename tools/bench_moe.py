@@ -7,6 +7,11 @@ Each mode writes its own section of profiles/moe.txt (a section is replaced when
                                          ffnSize 2048 against the dense model of ffnSize = k * 2048 (equal active
                                          parameters): tokens/s of generate() and generate(useGraph=True) at batch
                                          1 / 32 and prefix 128 / 1024, and a training step at batch 32 x 128
+  python tools/bench_moe.py --experts fp8 fp4
+                                         quantised experts (dl4j_wq_gemm_grouped of csrc/gemm_wq.hip): the two grouped
+                                         products of a decode step at 64 and 2 assignments (batch 32 and 1) against
+                                         moe_gather + gemm_grouped on the 16-bit experts, the variants alternating
+                                         within every pass; written to profiles/moe_weight_quant.txt
   DL4J_AMD_NATIVE=0 python tools/bench_moe.py --margin
                                          the router-logit difference between the 16-bit torch path and fp32 on the CPU
                                          on the model of tests/test_gpu_moe.py: the measurement behind its MARGIN
@@ -111,6 +116,62 @@ def kernels():
         rows.append(f"  gather  {tg:7.1f} us = {2 * a * E * 2 / tg / 1e6:.3f} TB/s (+-{sg:.1f}%)   combine {tc:7.1f} us = "
                     f"{(a + n) * E * 2 / tc / 1e6:.3f} TB/s (+-{sc:.1f}%)   cache-gather copy of {a} rows {tk:7.1f} us = "
                     f"{2 * a * E * 2 / tk / 1e6:.3f} TB/s (+-{sk:.1f}%)")
+    return rows
+
+
+def experts(fmts):
+    """The two grouped products of a decode step (GELU-free: W1 [E, 2F] as in the swiglu block) on quantised experts
+    against today's gather + grouped GEMM on the 16-bit experts; one pass times every variant once (20 calls), so the
+    variants alternate; median and spread over the passes, TB/s over the bytes of the experts that have assignments."""
+    import torch
+    from deeplearning4j_amd.ops import transformer_native as TN
+    dt, dev = torch.bfloat16, torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(0)
+    w1 = (torch.randn(X, E, 2 * F, generator=g) * E ** -0.5).to(dt).to(dev)
+    w2 = (torch.randn(X, F, E, generator=g) * F ** -0.5).to(dt).to(dev)
+    q1 = {f: TN.wq_quantize_experts(w1, f) for f in fmts}
+    q2 = {f: TN.wq_quantize_experts(w2, f) for f in fmts}
+    rows = [f"bf16, E={E}, F={F}, swiglu (W1 [E, 2F]), X={X}, k={K}; {PASSES} passes, every variant 20 calls per pass "
+            "(the variants alternate), median us (+- spread between the passes); TB/s over the active experts' bytes"]
+    for n in (32, 1):
+        x = torch.randn(n, E, generator=g).to(dt).to(dev)
+        plan, _ = TN.moe_route(_logits(n, False), K)
+        xp = TN.moe_gather(x, plan)
+        z = TN.gemm_grouped(xp, w1, None, plan)
+        f_ = TN.swiglu(z)
+        y = TN.gemm_grouped(f_, w2, None, plan)
+        live = int((plan.cnt > 0).sum())
+
+        def first16():
+            TN.moe_gather(x, plan, out=xp)
+            return TN.gemm_grouped(xp, w1, None, plan, out=z)
+        variants = [("16-bit gather + grouped W1", first16, live * E * 2 * F * 2),
+                    ("16-bit grouped W2", lambda: TN.gemm_grouped(f_, w2, None, plan, out=y), live * F * E * 2)]
+        for f in fmts:
+            bits = TN.WQ_FORMATS[f] + 0.25
+            variants.append((f"{f} skinny W1 (gather fused)",
+                             lambda f=f: TN.wq_gemm_grouped(x, q1[f], None, plan, True, None, z),
+                             live * E * 2 * F * bits / 8))
+            variants.append((f"{f} skinny W2 (sorted rows)",
+                             lambda f=f: TN.wq_gemm_grouped(f_, q2[f], None, plan, False, None, y),
+                             live * F * E * bits / 8))
+        for _, fn, _ in variants:
+            assert fn() is not None, "a kernel refused its operands"
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(PASSES):
+            for i, (_, fn, _) in enumerate(variants):
+                t0 = time.perf_counter()
+                for _ in range(20):
+                    fn()
+                torch.cuda.synchronize()
+                times[i].append((time.perf_counter() - t0) / 20 * 1e6)
+        rows.append(f"A={n * K} (batch {n}): cnt={plan.cnt.cpu().tolist()}, {live} active experts")
+        for (name, _, nbytes), t in zip(variants, times):
+            med = statistics.median(t)
+            base = statistics.median(times[0 if "W1" in name else 1])
+            rows.append(f"  {name:30s} {med:8.1f} us (+-{(max(t) - min(t)) / med * 100:.1f}%) = {nbytes / med / 1e6:.3f} "
+                        f"TB/s  {base / med:5.2f}x the 16-bit path")
     return rows
 
 
@@ -242,11 +303,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--margin", action="store_true")
     ap.add_argument("--model", action="store_true")
+    ap.add_argument("--experts", choices=["fp8", "fp4"], nargs="+", default=None)
     ap.add_argument("--stdout", action="store_true", help="print only, leave profiles/moe.txt alone")
     args = ap.parse_args()
     if args.margin and os.environ.get("DL4J_AMD_NATIVE", "1") != "0":
         print("note: --margin measures the torch path; run it with DL4J_AMD_NATIVE=0", file=sys.stderr)
-    if args.margin:
+    global OUT
+    if args.experts:
+        OUT = os.path.join(ROOT, "profiles", "moe_weight_quant.txt")
+        title, rows = "tools/bench_moe.py --experts " + " ".join(args.experts), experts(args.experts)
+    elif args.margin:
         title, rows = "tools/bench_moe.py --margin (DL4J_AMD_NATIVE=0)", margin()
     elif args.model:
         title, rows = "tools/bench_moe.py --model", model()
