@@ -978,7 +978,8 @@ class TextGenerationTransformer(ZooModel):
                  expertWeightDataType=None, **kw):
         super().__init__(numLabels, seed, inputShape, **kw)
         self.hidden, self.layers, self.heads = hidden, layers, heads
-        # None, "fp8" or "fp4": weight-only quantised decoding (net.rnnSetWeightDataType, applied by init()). It is
+        # None, "fp8", "fp4" (weight-only quantised decoding) or "native" (the 16-bit weights in place on the skinny
+        # decoding kernels): net.rnnSetWeightDataType, applied by init(). It is
         # runtime state of the network, not part of the configuration, so the JSON never carries it
         self.weightDataType = weightDataType
         # the same for the expert matrices of mixture-of-experts blocks (rnnSetWeightDataType(..., experts=))

@@ -199,19 +199,21 @@ def set_cache_data_type(named, value):
 
 def set_weight_data_type(named, value, experts=None):
     """rnnSetWeightDataType of a network over its (label, layer) pairs: every matrix of ``layer.wqKeys()`` under
-    ``value`` and every expert matrix of ``layer.wqExpertKeys()`` under ``experts`` is validated (the value, nIn % 32
-    == 0 (per expert for the experts), finite: one read-back for the whole network), then every layer takes both
-    formats and drops the copies it held; they are quantised at their first use."""
+    ``value`` and every expert matrix of ``layer.wqExpertKeys()`` under ``experts`` is validated (the value, and for
+    the quantised formats nIn % 32 == 0 (per expert for the experts) and finite: one read-back for the whole
+    network), then every layer takes both formats and drops the copies it held; they are quantised at their first
+    use. "native" (the compute dtype read in place by the skinny kernels) derives nothing and checks nothing."""
     for what, v in (("", value), (" experts", experts)):
-        if v is not None and v not in ("fp8", "fp4"):
+        if v is not None and v not in ("fp8", "fp4", "native"):
             raise DL4JInvalidConfigException(
-                f"rnnSetWeightDataType{what}: None (the compute dtype), \"fp8\" or \"fp4\", got {v!r}")
+                f"rnnSetWeightDataType{what}: None (the compute dtype), \"fp8\", \"fp4\" or \"native\" (the "
+                f"compute dtype on the skinny decoding kernels), got {v!r}")
     todo = [(label, l) for label, l in named
             if getattr(l, "wqKeys", tuple)() or getattr(l, "wqExpertKeys", tuple)()]
     finite = []
     for label, l in todo:
-        keys = [(k, 1) for k in (l.wqKeys() if value is not None else ())]
-        keys += [(k, l.conf.nExperts) for k in (l.wqExpertKeys() if experts is not None else ())]
+        keys = [(k, 1) for k in (l.wqKeys() if value in ("fp8", "fp4") else ())]
+        keys += [(k, l.conf.nExperts) for k in (l.wqExpertKeys() if experts in ("fp8", "fp4") else ())]
         for k, X in keys:
             nin = l.params[k].shape[0] // X
             if nin % 32:

@@ -785,11 +785,12 @@ class ComputationGraph(BaseNetwork):
         set_cache_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value)
 
     def rnnSetWeightDataType(self, value, experts=None):
-        """Weight-only quantised decoding, as MultiLayerNetwork.rnnSetWeightDataType: ``value`` None, "fp8" or "fp4"
-        for the weight matrices rnnTimeStep reads in TransformerEncoderLayer and RnnOutputLayer, ``experts`` the same
-        for the expert matrices W1 / W2 of mixture-of-experts blocks (never the router); every call sets both.
-        Refused, naming the vertex and changing nothing, for an unknown value, nIn % 32 != 0 (per expert for the
-        experts) or a non-finite weight."""
+        """Weight-only quantised decoding, as MultiLayerNetwork.rnnSetWeightDataType: ``value`` None, "fp8", "fp4" or
+        "native" for the weight matrices rnnTimeStep reads in TransformerEncoderLayer and RnnOutputLayer,
+        ``experts`` the same for the expert matrices W1 / W2 of mixture-of-experts blocks (never the router); every
+        call sets both. "native" is the compute dtype read in place by the skinny decoding kernels: no copy, no
+        quantisation error, no checks. Refused, naming the vertex and changing nothing, for an unknown value, and for
+        "fp8" / "fp4" nIn % 32 != 0 (per expert for the experts) or a non-finite weight."""
         from ..generation import set_weight_data_type
         set_weight_data_type([(f"vertex {n!r}", l) for n, l in self.layers_by_name.items()], value, experts)
 

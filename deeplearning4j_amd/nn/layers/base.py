@@ -126,8 +126,9 @@ class LayerImpl:
     # rnnSetWeightDataType of the network: the matrices a layer lists in wqKeys() are held a second time as MXFP8 /
     # MXFP4 (ops.transformer_native.QuantWeight) and read by rnnTimeStep only. The copies are derived state: each
     # remembers the weight version it was made from (ops.conv_native.WEIGHT_VERSION, bumped by every update of the
-    # network's parameters or compute copies) and is requantised on its next use after that moved on.
-    _wq_fmt = None        # None, "fp8" or "fp4"
+    # network's parameters or compute copies) and is requantised on its next use after that moved on. Under "native"
+    # nothing is held: the step's products read the compute-dtype views W(key) in place on the skinny kernels.
+    _wq_fmt = None        # None, "fp8", "fp4" or "native"
     _wq_expert_fmt = None     # the same for the matrices of wqExpertKeys(), independent of _wq_fmt
     _wq = None            # key -> (weight version, QuantWeight)
     _wq_step = False      # an output layer inside an rnnTimeStep whose projection reads the quantised W
@@ -166,9 +167,12 @@ class LayerImpl:
         return ent[1]
 
     def wqLinear(self, x, key, bias=None, act=None, out=None, beta=0.0):
-        """``act(x @ deq(Wq[key]) + bias + beta * out)`` on the quantised copy of parameter ``key``."""
+        """``act(x @ deq(Wq[key]) + bias + beta * out)`` on the quantised copy of parameter ``key``; under "native"
+        the skinny 16-bit product on W(key) itself."""
         from ...ops import transformer_native as TN
         from ...ops.gemm import bias_vec
+        if self._wq_fmt == "native":
+            return TN.skinny_linear(x, self.W(key), bias_vec(bias), act, out, beta)
         return TN.wq_linear(x, self.wqWeight(key), bias_vec(bias), act, out, beta)
 
     def type(self):

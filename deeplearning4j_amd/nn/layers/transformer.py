@@ -756,7 +756,13 @@ class TransformerEncoderLayerImpl(KVCacheState, DropoutSites, LayerImpl):
         sixteen = n.dtype in (torch.bfloat16, torch.float16)
         logits = mmul(n, self.W("Wr"), out_dtype=torch.float32 if sixteen else None)
         plan, gate = _moe_op("moe_route", n, logits, k)
-        if step and self._wq_expert_fmt is not None:
+        if step and self._wq_expert_fmt == "native":
+            xp = None                                   # the 16-bit experts in place on the skinny grouped product
+            z1p = TN.skinny_grouped_linear(n, self.W("W1").view(X, E, -1), _moe_bias(self.Wbias("b1")), plan, True,
+                                           None if c.swiglu() else "gelu")
+            fp = _swiglu_fwd(z1p) if c.swiglu() else z1p
+            yp = TN.skinny_grouped_linear(fp, self.W("W2").view(X, -1, E), _moe_bias(self.Wbias("b2")), plan, False)
+        elif step and self._wq_expert_fmt is not None:
             xp = None
             z1p = TN.wq_grouped_linear(n, self.wqExperts("W1", X), _moe_bias(self.Wbias("b1")), plan, True,
                                        None if c.swiglu() else "gelu")

@@ -498,7 +498,12 @@ class MultiLayerNetwork(BaseNetwork):
         update, are not serialised, and the master parameters stay in memory, so this cuts the bytes a step reads,
         not the size of the model. Refused, naming the layer and before any layer is changed, for an unknown value,
         a matrix whose nIn (per expert for the experts) is not a multiple of 32, or a non-finite weight (one
-        read-back here)."""
+        read-back here).
+
+        "native" (either argument, independently) keeps the compute dtype and holds no copy: rnnTimeStep chunks of up
+        to 64 rows multiply the 16-bit parameter views in place on the skinny decoding kernels (csrc/gemm_skinny.hip)
+        instead of the training-shaped GEMM, with no quantisation error, no nIn % 32 condition and no read-back;
+        more rows take the usual products."""
         from .generation import set_weight_data_type
         set_weight_data_type([(f"layer {i}", l) for i, l in enumerate(self.layers)], value, experts)
 

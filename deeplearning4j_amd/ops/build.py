@@ -52,9 +52,10 @@ def _run(cmd):
     return r.stdout
 
 
-# per-source flags: the weight-quantised GEMM is compiled without packed fp32 arithmetic (its fp32 math is the scalar
-# epilogue; the packed forms buy nothing there)
-EXTRA_FLAGS = {"gemm_wq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-source flags: the weight-quantised and the skinny 16-bit GEMM are compiled without packed fp32 arithmetic (their
+# fp32 math is the scalar epilogue; the packed forms buy nothing there)
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"gemm_wq.hip": _NO_PACKED_FP32, "gemm_skinny.hip": _NO_PACKED_FP32}
 
 
 def build_kernels(verbose=True, jobs=None):

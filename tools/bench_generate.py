@@ -825,10 +825,10 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--cache", choices=["fp8"], default=None,
                     help="compare generate() with the fp8 key/value cache and with the 16-bit one")
-    ap.add_argument("--weights", choices=["fp8", "fp4"], nargs="+", default=None,
+    ap.add_argument("--weights", choices=["fp8", "fp4", "native"], nargs="+", default=None,
                     help="weight-only quantised decoding (rnnSetWeightDataType) against 16-bit weights: generate() "
                          "and useGraph=True at prefix 128 and 1024")
-    ap.add_argument("--experts", choices=["fp8", "fp4"], nargs="+", default=None,
+    ap.add_argument("--experts", choices=["fp8", "fp4", "native"], nargs="+", default=None,
                     help="quantised mixture-of-experts experts (rnnSetWeightDataType(None, experts=)) against 16-bit "
                          "experts on the 12-layer 8-expert model: generate() and useGraph=True at prefix 128 and 1024")
     ap.add_argument("--kv-heads", default=None,

@@ -129,8 +129,8 @@ def experts(fmts):
     g = torch.Generator().manual_seed(0)
     w1 = (torch.randn(X, E, 2 * F, generator=g) * E ** -0.5).to(dt).to(dev)
     w2 = (torch.randn(X, F, E, generator=g) * F ** -0.5).to(dt).to(dev)
-    q1 = {f: TN.wq_quantize_experts(w1, f) for f in fmts}
-    q2 = {f: TN.wq_quantize_experts(w2, f) for f in fmts}
+    q1 = {f: TN.wq_quantize_experts(w1, f) for f in fmts if f != "native"}
+    q2 = {f: TN.wq_quantize_experts(w2, f) for f in fmts if f != "native"}
     rows = [f"bf16, E={E}, F={F}, swiglu (W1 [E, 2F]), X={X}, k={K}; {PASSES} passes, every variant 20 calls per pass "
             "(the variants alternate), median us (+- spread between the passes); TB/s over the active experts' bytes"]
     for n in (32, 1):
@@ -148,6 +148,13 @@ def experts(fmts):
         variants = [("16-bit gather + grouped W1", first16, live * E * 2 * F * 2),
                     ("16-bit grouped W2", lambda: TN.gemm_grouped(f_, w2, None, plan, out=y), live * F * E * 2)]
         for f in fmts:
+            if f == "native":           # the 16-bit experts in place on the skinny grouped kernel (csrc/gemm_skinny.hip)
+                variants.append(("16-bit skinny W1 (gather fused)",
+                                 lambda: TN.skinny_gemm_grouped(x, w1, None, plan, True, None, z),
+                                 live * E * 2 * F * 2))
+                variants.append(("16-bit skinny W2 (sorted rows)",
+                                 lambda: TN.skinny_gemm_grouped(f_, w2, None, plan, False, None, y), live * F * E * 2))
+                continue
             bits = TN.WQ_FORMATS[f] + 0.25
             variants.append((f"{f} skinny W1 (gather fused)",
                              lambda f=f: TN.wq_gemm_grouped(x, q1[f], None, plan, True, None, z),
@@ -303,14 +310,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--margin", action="store_true")
     ap.add_argument("--model", action="store_true")
-    ap.add_argument("--experts", choices=["fp8", "fp4"], nargs="+", default=None)
+    ap.add_argument("--experts", choices=["fp8", "fp4", "native"], nargs="+", default=None)
     ap.add_argument("--stdout", action="store_true", help="print only, leave profiles/moe.txt alone")
     args = ap.parse_args()
     if args.margin and os.environ.get("DL4J_AMD_NATIVE", "1") != "0":
         print("note: --margin measures the torch path; run it with DL4J_AMD_NATIVE=0", file=sys.stderr)
     global OUT
     if args.experts:
-        OUT = os.path.join(ROOT, "profiles", "moe_weight_quant.txt")
+        OUT = os.path.join(ROOT, "profiles",
+                           "skinny_gemm.txt" if "native" in args.experts else "moe_weight_quant.txt")
         title, rows = "tools/bench_moe.py --experts " + " ".join(args.experts), experts(args.experts)
     elif args.margin:
         title, rows = "tools/bench_moe.py --margin (DL4J_AMD_NATIVE=0)", margin()

@@ -5,7 +5,12 @@ projection, M = 1 and 32, bf16. GPU time per call by device events (ops.timing.g
 within every pass, median of the passes (min .. max); TB/s over the bytes a call reads (weights, scales, x, bias)
 next to the rate of a device-to-device copy of 256 MiB measured in the same run.
 
-Usage: python tools/bench_wq.py [--passes 7] [--reps 50] [--out profiles/weight_quant.txt]"""
+--native: the skinny 16-bit kernel on the weights in place (csrc/gemm_skinny.hip, ``dl4j_skinny_gemm``) against ``mmul``
+on the same weights, M = 1, 32 and 64, bf16 and fp16, next to the fp8 rows of the same run: the four block shapes
+N-contiguous as the blocks hold them, with both load widths (4 / 8 columns per lane) and the kernel's rule, the
+vocabulary projection K-contiguous as RnnOutputLayer holds it.
+
+Usage: python tools/bench_wq.py [--native] [--passes 7] [--reps 50] [--out profiles/weight_quant.txt]"""
 import argparse
 import sys
 
@@ -28,16 +33,59 @@ def say(s=""):
         _out.flush()
 
 
+def native(a):
+    say(f"GPU time per call in us, median of {a.passes} passes of {a.reps} launches (min .. max), the variants "
+        "alternating within a pass; bias in the epilogue; TB/s over the weight bytes; x = the 16-bit mmul's time over "
+        "the variant's")
+    for dt in (torch.bfloat16, torch.float16):
+        for M in (1, 32, 64):
+            for K, N in SHAPES:
+                g = torch.Generator().manual_seed(K + N)
+                W = (torch.randn(K, N, generator=g) * 0.05).to(dt).to(DEV)
+                kcon = N == 32000
+                if kcon:
+                    W = W.t().contiguous().t()
+                x = torch.randn(M, K, generator=g).to(dt).to(DEV)
+                bias = torch.randn(N, generator=g).to(DEV)
+                out = torch.empty(M, N, dtype=dt, device=DEV)
+                q8 = TN.wq_quantize(W, "fp8")
+                runs = [("16-bit mmul", lambda: mmul(x, W, out=out, bias=bias), 2 * K * N)]
+                if kcon:
+                    runs.append(("skinny K-contiguous", lambda: TN.skinny_gemm(x, W, bias, None, out), 2 * K * N))
+                else:
+                    runs += [(f"skinny width {wd or 'rule'}",
+                              lambda wd=wd: TN.skinny_gemm(x, W, bias, None, out, width=wd), 2 * K * N)
+                             for wd in (4, 8, 0)]
+                runs.append(("fp8 wq_gemm", lambda: TN.wq_gemm(x, q8, bias, None, out),
+                             q8.codes.numel() + q8.scales.numel()))
+                for _, fn, _ in runs:
+                    assert fn() is not None                         # the 16-bit product's autotuner, first launches
+                times = [[] for _ in runs]
+                for _ in range(a.passes):
+                    for i, (_, fn, _) in enumerate(runs):
+                        times[i].append(gpu_time(fn, reps=a.reps, warmup=3))
+                med = [sorted(t)[len(t) // 2] for t in times]
+                say(f"{str(dt).split('.')[1]}  M {M:2d}  K {K:5d}  N {N:5d}:")
+                for (name, _, wb), t, m in zip(runs, times, med):
+                    say(f"    {name:19s}: {m * 1e3:7.2f} us ({min(t) * 1e3:.2f} .. {max(t) * 1e3:.2f})  "
+                        f"{wb / m / 1e9:5.2f} TB/s  {med[0] / m:5.2f}x")
+    say()
+
+
 def main():
     global _out
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--passes", type=int, default=7)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--native", action="store_true", help="the skinny 16-bit kernel against mmul (see above)")
     a = ap.parse_args()
     if a.out:
         _out = open(a.out, "w")
-    say(f"# tools/bench_wq.py on {torch.cuda.get_device_name(0)}, torch {torch.__version__}")
+    say(f"# tools/bench_wq.py{' --native' if a.native else ''} on {torch.cuda.get_device_name(0)}, "
+        f"torch {torch.__version__}")
+    if a.native:
+        return native(a)
     src = torch.empty(256 << 20, dtype=torch.uint8, device=DEV)
     dst = torch.empty_like(src)
     t = sorted(gpu_time(lambda: dst.copy_(src), reps=20, warmup=3) for _ in range(a.passes))
