@@ -689,6 +689,11 @@ const OpEntry kOps[] = {
     {"dl4j_lstm_bwd_coop", "int(...)", "cooperative LSTM backward"},
     {"dl4j_lstm_pack_rw", "int(int,void*,ll,ll,int,void*,void*,float*,stream)", "recurrent weight packing"},
     {"dl4j_lstm_bwd_prep", "int(...)", "LSTM backward glue"},
+    {"dl4j_gru_fwd", "int(...)", "whole-sequence GRU forward"},
+    {"dl4j_gru_bwd", "int(...)", "whole-sequence GRU backward"},
+    {"dl4j_rnn_fwd", "int(...)", "whole-sequence SimpleRnn forward (tanh / relu)"},
+    {"dl4j_rnn_bwd", "int(...)", "whole-sequence SimpleRnn backward"},
+    {"dl4j_rnn_pack_rw", "int(int,void*,ll,ll,int,int,void*,void*,stream)", "recurrent weight packing, G gate blocks"},
     {"dl4j_ln_fwd", "int(...)", "LayerNorm (+residual) forward"},
     {"dl4j_ln_bwd", "int(...)", "LayerNorm backward (+ producing bias gradient)"},
     {"dl4j_gelu", "int(int,void*,void*,void*,ll,stream)", "exact GELU / backward"},

@@ -313,6 +313,29 @@ def _simple_rnn_setter(p, kw):
     _set(p, "b", np.asarray(_w(kw, "bias", "b")).reshape(1, -1))
 
 
+def gru_keras_weights(kernel, recurrent_kernel, bias):
+    """Keras GRU weights (``reset_after=True``: kernel [nIn, 3H] and recurrent_kernel [H, 3H] in block order
+    [z | r | h], bias [2, 3H] = input bias over recurrent bias) -> this framework's GRU parameters (W, RW, b, bRn) in
+    block order [r | z | n]: b = input bias + recurrent bias on the r / z blocks and the input bias alone on the n
+    block; bRn = the recurrent bias's n block, which sits inside the reset gate's product."""
+    W, U, bb = np.asarray(kernel), np.asarray(recurrent_kernel), np.asarray(bias)
+    H = U.shape[0]
+    if U.shape != (H, 3 * H) or W.shape[-1] != 3 * H or bb.shape != (2, 3 * H):
+        raise InvalidKerasConfigurationException(
+            f"GRU weights kernel {W.shape}, recurrent_kernel {U.shape}, bias {bb.shape}: expected [nIn, 3H], [H, 3H] "
+            "and the reset_after=True bias [2, 3H]")
+    perm = lambda a: np.concatenate([a[..., H:2 * H], a[..., :H], a[..., 2 * H:]], axis=-1)  # noqa: E731
+    bi, br = perm(bb[0]), perm(bb[1])
+    b = np.concatenate([bi[:2 * H] + br[:2 * H], bi[2 * H:]])
+    return perm(W), perm(U), b.reshape(1, -1), br[2 * H:].reshape(1, -1)
+
+
+def _gru_setter(p, kw, d=""):
+    W, U, b, bRn = gru_keras_weights(_w(kw, "kernel"), _w(kw, "recurrent_kernel"), _w(kw, "bias"))
+    for key, arr in (("W", W), ("RW", U), ("b", b), ("bRn", bRn)):
+        _set(p, d + key, arr)
+
+
 def _embedding_setter(p, kw):
     _set(p, "W", _w(kw, "embeddings", "W"))
 
@@ -459,7 +482,7 @@ def _masks_zero(k):
 def _mask_zero_wrap(m):
     """A recurrent layer fed by a mask_zero Embedding: MaskZeroLayer(layer) (inside the LastTimeStep wrapper when
     return_sequences is false), as KER:layers/recurrent/KerasLstm.java / KerasSimpleRnn.java."""
-    if m.keras_class not in ("LSTM", "SimpleRNN", "Bidirectional"):
+    if m.keras_class not in ("LSTM", "GRU", "SimpleRNN", "Bidirectional"):
         return m
     if isinstance(m.obj, L.LastTimeStep):
         m.obj.underlying = L.MaskZeroLayer(underlying=m.obj.underlying, maskingValue=0.0)
@@ -603,6 +626,21 @@ def _map_layer_core(kl, ctx):
         if cfg.get("go_backwards", False):
             raise UnsupportedKerasConfigurationException("go_backwards recurrent layers")
         return _KLayer(name, "layer", lay, setter=setter, keras_class=cls, cfg=cfg)
+    if cls == "GRU":
+        from ..nn.conf.activations import ActivationHardSigmoid, ActivationSigmoid
+        gate = _act(cfg.get("recurrent_activation", "sigmoid")).getActivationFunction()
+        if not cfg.get("reset_after", False):
+            raise UnsupportedKerasConfigurationException(
+                "GRU with reset_after=False (the candidate's recurrent product depends on the reset gate)")
+        if not isinstance(gate, (ActivationSigmoid, ActivationHardSigmoid)):
+            raise UnsupportedKerasConfigurationException(f"GRU recurrent_activation {cfg['recurrent_activation']!r}")
+        if cfg.get("go_backwards", False):
+            raise UnsupportedKerasConfigurationException("go_backwards recurrent layers")
+        lay = L.GRU(nOut=int(cfg["units"]), activation=act() if "activation" in cfg else Activation.TANH,
+                    gateActivationFn=gate)
+        if not cfg.get("return_sequences", False):
+            lay = L.LastTimeStep(underlying=lay)
+        return _KLayer(name, "layer", lay, setter=_gru_setter, keras_class=cls, cfg=cfg)
     if cls == "Bidirectional":
         inner = cfg["layer"]
         icfg = inner["config"]
@@ -619,6 +657,9 @@ def _map_layer_core(kl, ctx):
                 pre = f"{direction}_{iname}"
                 sk = {k[len(pre) + 1:]: v for k, v in kw.items() if k.startswith(pre + "/") or
                       k.startswith(pre + "_")}
+                if icls == "GRU":
+                    _gru_setter(p, sk, d)
+                    continue
                 if icls == "LSTM":
                     W, U, bb = _lstm_arrays(sk)
                 else:

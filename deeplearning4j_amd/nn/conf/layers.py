@@ -1128,6 +1128,34 @@ class SimpleRnn(BaseRecurrentLayer):
                 ParamSpec("b", [1, self.nOut], "c", "bias")]
 
 
+class GRU(BaseRecurrentLayer):
+    """Gated recurrent unit in the cuDNN / PyTorch convention (Keras ``reset_after=True``), gate blocks [r | z | n]:
+    r = gate(x W_r + h RW_r + b_r); z = gate(x W_z + h RW_z + b_z); n = act(x W_n + b_n + r * (h RW_n + bRn));
+    h_t = (1 - z) * n + z * h_{t-1}. The recurrent biases of r and z are the same degree of freedom as b's, so only
+    the candidate's (bRn, inside the reset product) is a parameter of its own."""
+    FIELDS = {"gateActivationFn": None}
+    _CONVERTERS = dict(BaseRecurrentLayer._CONVERTERS, gateActivationFn=to_activation)
+    _ALIASES = dict(BaseRecurrentLayer._ALIASES, gateActivationFunction="gateActivationFn")
+    RUNTIME = "deeplearning4j_amd.nn.layers.recurrent:GRUImpl"
+
+    def finalize_defaults(self):
+        from .activations import ActivationSigmoid, ActivationTanH
+        if self.activation is None:
+            self.activation = ActivationTanH()
+        super().finalize_defaults()
+        if self.gateActivationFn is None:
+            self.gateActivationFn = ActivationSigmoid()
+
+    def param_specs(self):
+        H = self.nOut
+        return [ParamSpec("W", [self.nIn, 3 * H], "f", "weight", self.nIn, 3 * H),
+                ParamSpec("RW", [H, 3 * H], "f", "recurrent", H, 3 * H),
+                ParamSpec("b", [1, 3 * H], "c", "bias"), ParamSpec("bRn", [1, H], "c", "bias")]
+
+    def is_bias(self, key):
+        return key in ("b", "bRn")
+
+
 class BaseWrapperLayer(Layer):
     FIELDS = {"underlying": None}
 

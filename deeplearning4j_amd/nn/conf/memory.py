@@ -271,10 +271,10 @@ def layer_memory_report(lc, inputType, outputType, name=None, compute_bytes=None
         c = getattr(base, "nOut", 0) or 0
         wfi = wft = 4 * c + 2 * 1024 * c  # ctx + per-block partial sums
         cache_var = inE
-    elif bt in ("LSTM", "GravesLSTM", "GravesBidirectionalLSTM", "SimpleRnn"):
+    elif bt in ("LSTM", "GravesLSTM", "GravesBidirectionalLSTM", "GRU", "SimpleRnn"):
         T = getattr(inputType, "timeSeriesLength", 1) or 1
         n = getattr(base, "nOut", 0) or 0
-        gates = 4 if bt != "SimpleRnn" else 1
+        gates = {"SimpleRnn": 1, "GRU": 3}.get(bt, 4)
         wvi = gates * n * T
         wvt = 3 * gates * n * T           # gate pre-activations + activations + cell states kept for backprop
     elif bt in ("SubsamplingLayer", "Pooling2D"):

@@ -362,8 +362,8 @@ class ListBuilder:
         n_in = getattr(first, "nIn", 0) or 0
         if n_in <= 0:
             return None
-        from .layers import Bidirectional, GravesBidirectionalLSTM, GravesLSTM, LSTM, SimpleRnn
-        if isinstance(first, (LSTM, GravesLSTM, GravesBidirectionalLSTM, SimpleRnn)) and \
+        from .layers import Bidirectional, GravesBidirectionalLSTM, GravesLSTM, GRU, LSTM, SimpleRnn
+        if isinstance(first, (LSTM, GravesLSTM, GravesBidirectionalLSTM, GRU, SimpleRnn)) and \
                 not isinstance(first, Bidirectional):
             return InputType.recurrent(n_in)
         if type(first) in (DenseLayer, EmbeddingLayer, OutputLayer):

@@ -1,4 +1,4 @@
-"""Recurrent runtime layers: LSTM, GravesLSTM (peepholes), GravesBidirectionalLSTM, SimpleRnn,
+"""Recurrent runtime layers: LSTM, GravesLSTM (peepholes), GravesBidirectionalLSTM, GRU, SimpleRnn,
 Bidirectional, LastTimeStep.
 
 LSTM math = reference nn/layers/recurrent/LSTMHelpers.java (forward :189-358, backward :392-690):
@@ -509,7 +509,172 @@ class GravesBidirectionalLSTMImpl(BaseRecurrentImpl):
         raise NotImplementedError("GravesBidirectionalLSTM does not support rnnTimeStep (needs the full sequence)")
 
 
+def _seq_kernel_ok(x, W, H, cell):
+    """The whole-sequence GRU / SimpleRnn kernels (csrc/gru.hip) apply: GPU tensor, kernel-supported H / dtype, not
+    switched off (DL4J_AMD_KERNEL_GRU / DL4J_AMD_KERNEL_RNN)."""
+    from ...ops import rnn_native
+    return x.is_cuda and rnn_native.gru_supported(H, W.dtype) and ops.use_native(x, cell)
+
+
+def _col_sums(d):
+    """fp32 / fp64 column sums of the deltas [R, C] (the bias gradients), on the channel-sum kernel on the GPU."""
+    if d.is_cuda and d.dtype == torch.float32 and ops.use_native(d, "bias_grad"):
+        from ...ops import native
+        r = native.channel_sum(d)
+        if r is not None:
+            return r
+    return d.sum(dim=0)
+
+
+def _gru_fwd(x, W, RW, b, bRn, h0, H, act, gate_act, mask, need_cache):
+    """x: [mb, nIn, T]. Returns out [mb, H, T], hT, cache. Gate blocks [r | z | n] (Keras reset_after=True):
+    r = gate(zx_r + a_r); z = gate(zx_z + a_z); q = a_n + bRn; n = act(zx_n + r*q); h = ((1-z)*n + z*h_prev)*mask
+    with a = h_prev·RW and zx = x·W + b for all steps from one GEMM."""
+    mb, nIn, T = x.shape
+    dt = W.dtype
+    _adt = acc_dtype(W)
+    xt = _time_major_rows(x, dt)
+    zx = matmul(xt, W, bias=b).reshape(T, mb, 3 * H)
+    if isinstance(act, ActivationTanH) and isinstance(gate_act, ActivationSigmoid) and _seq_kernel_ok(x, W, H, "gru"):
+        from ...ops import rnn_native
+        packs = rnn_native.pack_rw_blocks(RW, H, 3, need_bwd=need_cache)
+        r = rnn_native.gru_seq_fwd(zx, RW, bRn, H, h0, mask, need_cache, packs=packs, out16=True)
+        if r is not None:
+            out_tmh, hT, gates, o16 = r
+            out = o16.permute(1, 2, 0) if o16 is not None else out_tmh.permute(1, 2, 0).to(dt)
+            cache = {"native": True, "gates": gates, "out": out_tmh, "h0": h0, "xt": xt, "packs": packs} \
+                if need_cache else None
+            return out, hT, cache
+    from ...ops import fallback
+    fallback.note(x, "gru", f"H {H} / dtype {dt} / {type(act).__name__}: per-step torch path")
+    h = torch.zeros(mb, H, dtype=_adt, device=x.device) if h0 is None else _acc(h0)
+    bq = _acc(bRn).reshape(1, H)
+    outs = []
+    cache = {k: [] for k in ("pr", "pz", "pn", "r", "z", "n", "q", "h_prev")} if need_cache else None
+    for t in range(T):
+        a = _acc(matmul(h.to(dt), RW))
+        zt = _acc(zx[t])
+        pr, pz = zt[:, :H] + a[:, :H], zt[:, H:2 * H] + a[:, H:2 * H]
+        r, z = gate_act.getActivation(pr, True), gate_act.getActivation(pz, True)
+        q = a[:, 2 * H:] + bq
+        pn = zt[:, 2 * H:] + r * q
+        n = act.getActivation(pn, True)
+        hn = (1 - z) * n + z * h
+        if mask is not None:
+            hn = hn * _acc(mask[:, t]).reshape(-1, 1)
+        if need_cache:
+            for k, v in (("pr", pr), ("pz", pz), ("pn", pn), ("r", r), ("z", z), ("n", n), ("q", q), ("h_prev", h)):
+                cache[k].append(v)
+        h = hn
+        outs.append(h)
+    if need_cache:
+        cache["xt"] = xt
+    return torch.stack(outs, dim=2).to(dt), h, cache
+
+
+def _gru_weight_grads(dz4, xt, hprev, W, H, grads, need_dx, T, mb):
+    """The GEMMs after the time loop, from the deltas dz4 [T*mb, 4H] = [dzr | dzz | dzn | dzn*r] read in place as
+    strided operands: dW = xᵀ·dz4[:, :3H]; dRW = h_prevᵀ·[dz4[:, :2H] | dz4[:, 3H:]], written per column range of the
+    'f'-ordered gradient view; db, dbRn = column sums; dx = dz4[:, :3H]·Wᵀ."""
+    dt = W.dtype
+    lo = dz4.is_cuda and dt in (torch.bfloat16, torch.float16)
+    d = dz4.to(dt) if lo else dz4                       # 16-bit operands, fp32 accumulation into the gradient views
+    hp = hprev.to(d.dtype)
+    weight_grad_(grads["W"], (xt if lo else _acc(xt)).t(), d[:, :3 * H])
+    gRW = grads["RW"]
+    weight_grad_(gRW[:, :2 * H], hp.t(), d[:, :2 * H])
+    weight_grad_(gRW[:, 2 * H:], hp.t(), d[:, 3 * H:])
+    sums = _col_sums(dz4)
+    copy_grad_(grads["b"], sums[:3 * H])
+    copy_grad_(grads["bRn"], sums[3 * H:])
+    if not need_dx:
+        return None
+    return matmul(d[:, :3 * H].to(dt), W.t()).reshape(T, mb, -1).permute(1, 2, 0)
+
+
+def _gru_bwd(eps, cache, W, RW, H, act, gate_act, mask, tbptt_back, grads, need_dx=True):
+    """eps: [mb, H, T]. Writes dW / dRW / db / dbRn into the gradient views; returns eps_in [mb, nIn, T] or None."""
+    mb, _, T = eps.shape
+    t_end = max(0, T - tbptt_back) if tbptt_back else 0
+    if cache.get("native"):
+        from ...ops import rnn_native
+        r = rnn_native.gru_seq_bwd(eps.permute(2, 0, 1), cache["gates"], cache["out"], cache["h0"], RW, H, mask, None,
+                                   t_end, packs=cache["packs"])
+        if r is None:
+            raise RuntimeError("native GRU forward cache but the backward kernel rejected the shape")
+        out = cache["out"]
+        h0 = torch.zeros(1, mb, H, device=out.device) if cache["h0"] is None else _acc(cache["h0"]).reshape(1, mb, H)
+        hprev = torch.cat([h0.to(out.dtype), out[:-1]], dim=0).reshape(T * mb, H)
+        return _gru_weight_grads(r[0].reshape(T * mb, 4 * H), cache["xt"], hprev, W, H, grads, need_dx, T, mb)
+    _adt = acc_dtype(W)
+    RWa = _acc(RW)
+    dh_next = torch.zeros(mb, H, device=eps.device, dtype=_adt)
+    dz4 = torch.zeros(T, mb, 4 * H, device=eps.device, dtype=_adt)
+    e = _acc(eps)
+    for t in range(T - 1, t_end - 1, -1):
+        dh = e[:, :, t] + dh_next
+        if mask is not None:
+            dh = dh * _acc(mask[:, t]).reshape(-1, 1)
+        r, z, n, q, hp = (cache[k][t] for k in ("r", "z", "n", "q", "h_prev"))
+        dzn = act.backprop(cache["pn"][t], dh * (1 - z))
+        dzz = gate_act.backprop(cache["pz"][t], dh * (hp - n))
+        dzr = gate_act.backprop(cache["pr"][t], dzn * q)
+        dq = dzn * r
+        dz4[t] = torch.cat([dzr, dzz, dzn, dq], dim=1)
+        dh_next = dh * z + matmul(torch.cat([dzr, dzz, dq], dim=1), RWa.t())
+    hprev = torch.stack(cache["h_prev"], 0).reshape(T * mb, H)
+    return _gru_weight_grads(dz4.reshape(T * mb, 4 * H), cache["xt"], hprev, W, H, grads, need_dx, T, mb)
+
+
+class GRUImpl(BaseRecurrentImpl):
+    GRADS_OVERWRITE = True        # every gradient view is written whole every backward (no accumulation)
+
+    def _run(self, x, h0, mask, need_cache):
+        c = self.conf
+        return _gru_fwd(x, self.W("W"), self.W("RW"), self.Wbias("b"), self.W("bRn"), h0, c.nOut, c.activation,
+                        c.gateActivationFn, mask, need_cache)
+
+    def activate(self, x, training=False, mask=None, stored_state=False, store_last_for_tbptt=False):
+        if x.dim() == 2:
+            x = x.unsqueeze(2)
+        self.training = training
+        x = self.applyDropOutIfNecessary(x, training)
+        self.input = x
+        self.maskArray = mask
+        h0 = self.tBpttStateMap.get("prevAct") if stored_state else None
+        out, h, self._cache = self._run(x, h0, mask, training)
+        if store_last_for_tbptt:
+            self.tBpttStateMap = {"prevAct": h.detach()}
+        return out
+
+    def rnnTimeStep(self, x, mask=None):
+        self._check_state_mb(x)
+        is2d = x.dim() == 2
+        if is2d:
+            x = x.unsqueeze(2)
+        out, h, _ = self._run(x, self.stateMap.get("prevAct"), mask, False)
+        self.stateMap = {"prevAct": h}
+        return out[:, :, 0] if is2d else out
+
+    def backpropGradient(self, eps, tbptt_back=None):
+        if eps.dim() == 2:
+            eps = eps.unsqueeze(2)
+        c = self.conf
+        dx = _gru_bwd(eps, self._cache, self.W("W"), self.W("RW"), c.nOut, c.activation, c.gateActivationFn,
+                      self.maskArray, tbptt_back, self.grads, getattr(self, "need_input_grad", True))
+        if dx is None:
+            return self.make_gradient(), None
+        return self.make_gradient(), self.backpropDropOut(dx.to(eps.dtype))
+
+
 class SimpleRnnImpl(BaseRecurrentImpl):
+    def _kernel_act(self, x, W):
+        """"tanh" / "relu" when the whole-sequence kernel (csrc/gru.hip) takes this layer's recurrence, else None."""
+        from ..conf.activations import ActivationReLU
+        a = self.conf.activation
+        name = "tanh" if isinstance(a, ActivationTanH) else ("relu" if type(a) is ActivationReLU else None)
+        return name if name is not None and _seq_kernel_ok(x, W, self.conf.nOut, "rnn") else None
+
     def _fwd(self, x, h0, mask, need_cache):
         mb, nIn, T = x.shape
         _adt = acc_dtype(self.W("W"))
@@ -517,6 +682,16 @@ class SimpleRnnImpl(BaseRecurrentImpl):
         dt = W.dtype
         xt = x.permute(2, 0, 1).reshape(T * mb, nIn).to(dt)
         zx = matmul(xt, W, bias=b).reshape(T, mb, -1)
+        name = self._kernel_act(x, W)
+        if name is not None:
+            from ...ops import rnn_native
+            H = self.conf.nOut
+            packs = rnn_native.pack_rw_blocks(RW, H, 1, need_bwd=need_cache)
+            r = rnn_native.rnn_seq_fwd(zx, RW, H, name, h0, mask, packs=packs)
+            if r is not None:
+                out_tmh, hT, _ = r
+                self._c = {"native": name, "out": out_tmh, "h0": h0, "xt": xt, "packs": packs} if need_cache else None
+                return out_tmh.permute(1, 2, 0).to(x.dtype), hT
         h = torch.zeros(mb, self.conf.nOut, device=x.device, dtype=_adt) if h0 is None else _acc(h0)
         zs, hs, outs = [], [], []
         for t in range(T):
@@ -558,9 +733,27 @@ class SimpleRnnImpl(BaseRecurrentImpl):
         _adt = acc_dtype(self.W("W"))
         RW = _acc(self.W("RW"))
         c = self._c
+        t_end = max(0, T - tbptt_back) if tbptt_back else 0
+        if c.get("native"):
+            from ...ops import rnn_native
+            r = rnn_native.rnn_seq_bwd(eps.permute(2, 0, 1), c["out"], self.W("RW"), H, c["native"], self.maskArray,
+                                       None, t_end, packs=c["packs"])
+            if r is None:
+                raise RuntimeError("native SimpleRnn forward cache but the backward kernel rejected the shape")
+            out = c["out"]
+            h0 = torch.zeros(1, mb, H, device=out.device) if c["h0"] is None else _acc(c["h0"]).reshape(1, mb, H)
+            W = self.W("W")
+            lo = W.dtype in (torch.bfloat16, torch.float16)
+            dzf = r[0].reshape(T * mb, H)
+            d = dzf.to(W.dtype) if lo else dzf
+            hprev = torch.cat([h0.to(out.dtype), out[:-1]], dim=0).reshape(T * mb, H).to(d.dtype)
+            weight_grad_(self.grads["W"], (c["xt"] if lo else _acc(c["xt"])).t(), d)
+            weight_grad_(self.grads["RW"], hprev.t(), d)
+            copy_grad_(self.grads["b"], _col_sums(dzf))
+            dx = matmul(d, W.t()).reshape(T, mb, -1).permute(1, 2, 0)
+            return self.make_gradient(), self.backpropDropOut(dx.to(eps.dtype))
         dh_next = torch.zeros(mb, H, device=eps.device, dtype=_adt)
         dz_all = torch.zeros(T, mb, H, device=eps.device, dtype=_adt)
-        t_end = max(0, T - tbptt_back) if tbptt_back else 0
         for t in range(T - 1, t_end - 1, -1):
             dh = _acc(eps[:, :, t]) + dh_next
             if self.maskArray is not None:

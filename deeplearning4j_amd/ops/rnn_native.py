@@ -5,6 +5,9 @@
 h·RW, fused gates + peepholes + mask, cell state in registers). ``lstm_seq_bwd`` runs the backward time loop
 (gate deltas + dh = dz·RWᵀ per step) and returns the fp32 gate deltas for the weight GEMMs. Both return
 ``None`` when the shape/dtype is outside the kernels (the caller then runs the per-step path).
+
+``gru_seq_fwd`` / ``gru_seq_bwd`` and ``rnn_seq_fwd`` / ``rnn_seq_bwd`` do the same for the GRU and SimpleRnn
+recurrences (csrc/gru.hip: the single-workgroup design for every supported H, no cooperative variant).
 """
 import ctypes
 import threading
@@ -353,6 +356,135 @@ def lstm_seq_bwd(eps_tmh, gates, call, c0, RW, H, peephole, mask=None, dh_last=N
     return dz, dh0, dc0
 
 
+
+
+# ---- GRU / SimpleRnn whole-sequence kernels (csrc/gru.hip)
+_ACTC = {"tanh": 0, "relu": 1}
+
+
+def gru_supported(H, dtype):
+    """csrc/gru.hip pick_nt: H a multiple of the MFMA k-step (32 for 16-bit, 16 for fp32) and at most 8 waves of
+    16 * NT hidden units, NT in 1 / 2 / 4 (H <= 512, and above 128 / 256 a multiple of 32 / 64)."""
+    if dtype not in _DTC or H < 16 or H % (16 if dtype == torch.float32 else 32):
+        return False
+    return H // 16 <= 8 or (H % 32 == 0 and H // 32 <= 8) or (H % 64 == 0 and H // 64 <= 8)
+
+
+def _cell_on(t, cell):
+    """The ``cell`` ("gru" / "rnn") kernels may take tensor ``t``: on the GPU and not switched off by
+    DL4J_AMD_KERNEL_GRU=0 / DL4J_AMD_KERNEL_RNN=0."""
+    from .dispatch import use_native
+    return use_native(t, cell)
+
+
+def pack_rw_blocks(RW, H, G, need_bwd=True):
+    """RWPacks (no peepholes) of an [H, G*H] recurrent weight view for the csrc/gru.hip kernels (G = 3 GRU, 1
+    SimpleRnn), both images in one launch; None when the kernels do not take this dtype / H."""
+    dt = RW.dtype
+    if not RW.is_cuda or not gru_supported(H, dt) or tuple(RW.shape) != (H, G * H):
+        return None
+    lib = native.load()
+    fe = 8 if dt in (torch.bfloat16, torch.float16) else 4
+    shape = lambda n, k: (n // 16, k // (4 * fe), 4, 16, fe)  # noqa: E731
+    fwd = arena.empty(shape(G * H, H), dt, RW.device)
+    bwd = arena.empty(shape(H, G * H), dt, RW.device) if need_bwd else None
+    rc = lib.dl4j_rnn_pack_rw(_DTC[dt], _ptr(RW), RW.stride(0), RW.stride(1), H, G, _ptr(fwd), _ptr(bwd), _stream())
+    if rc == -1:
+        return None
+    _check(rc, "rnn_pack_rw")
+    return RWPacks(fwd, bwd, None, H, dt)
+
+
+def _cell_fwd(cell, act, zx, RW, H, G, bRn, h0, mask, need_cache, packs, out16):
+    T, mb, GH = zx.shape
+    dt = zx.dtype
+    if GH != G * H or not gru_supported(H, dt) or T < 1 or mb < 1 or not _cell_on(zx, cell):
+        return None
+    if packs is None or packs.dtype != dt or packs.H != H:
+        packs = pack_rw_blocks(RW, H, G, need_bwd=False)
+        if packs is None:
+            return None
+    m = _f32c(mask.reshape(mb, -1)) if mask is not None else None
+    if m is not None and m.shape[1] != T:
+        return None
+    lib = native.load()
+    dev = zx.device
+    zx = zx.contiguous()
+    out = arena.empty((T, mb, H), torch.float32, dev)
+    o16 = arena.empty((T, mb, H), dt, dev) if out16 and dt != torch.float32 else None
+    hT = torch.empty(mb, H, device=dev, dtype=torch.float32)
+    h0c = _f32c(h0)
+    if cell == "gru":
+        gates = arena.empty((T, mb, 4 * H), torch.float32, dev) if need_cache else None
+        rc = lib.dl4j_gru_fwd(_DTC[dt], _ptr(zx), _ptr(packs.fwd), _ptr(_f32c(bRn.reshape(-1))), _ptr(h0c), _ptr(m),
+                              _ptr(out), _ptr(o16), _ptr(gates), _ptr(hT), T, mb, H, _stream())
+    else:
+        gates = None
+        rc = lib.dl4j_rnn_fwd(_DTC[dt], _ACTC[act], _ptr(zx), _ptr(packs.fwd), _ptr(h0c), _ptr(m), _ptr(out),
+                              _ptr(o16), _ptr(hT), T, mb, H, _stream())
+    if rc == -1:
+        return None
+    _check(rc, cell + "_fwd")
+    return out, hT, gates, o16
+
+
+def _cell_bwd(cell, act, eps_tmh, gates, out, h0, RW, H, G, mask, dh_last, t_end, packs):
+    T, mb, _ = eps_tmh.shape
+    dt = RW.dtype
+    if not gru_supported(H, dt) or not 0 <= t_end < T or not _cell_on(eps_tmh, cell):
+        return None
+    if packs is None or packs.bwd is None or packs.dtype != dt or packs.H != H:
+        packs = pack_rw_blocks(RW, H, G)
+        if packs is None:
+            return None
+    lib = native.load()
+    dev = eps_tmh.device
+    e, edt = _eps_arg(eps_tmh)
+    m = _f32c(mask.reshape(mb, -1)) if mask is not None else None
+    dz = arena.empty((T, mb, (4 if cell == "gru" else 1) * H), torch.float32, dev)
+    if t_end > 0:
+        dz[:t_end].zero_()
+    dh0 = torch.empty(mb, H, device=dev, dtype=torch.float32)
+    if cell == "gru":
+        rc = lib.dl4j_gru_bwd(_DTC[dt], _ptr(e), edt, _ptr(gates), _ptr(out), _ptr(_f32c(h0)), _ptr(packs.bwd),
+                              _ptr(m), _ptr(_f32c(dh_last)), _ptr(dz), _ptr(dh0), T, mb, H, int(t_end), _stream())
+    else:
+        rc = lib.dl4j_rnn_bwd(_DTC[dt], _ACTC[act], _ptr(e), edt, _ptr(out), _ptr(packs.bwd), _ptr(m),
+                              _ptr(_f32c(dh_last)), _ptr(dz), _ptr(dh0), T, mb, H, int(t_end), _stream())
+    if rc == -1:
+        return None
+    _check(rc, cell + "_bwd")
+    return dz, dh0
+
+
+def gru_seq_fwd(zx, RW, bRn, H, h0=None, mask=None, need_cache=True, packs=None, out16=False):
+    """zx: [T, mb, 3H] (compute dtype, = x·W + b, blocks [r | z | n]); RW: [H, 3H]; bRn: [H] recurrent bias of the
+    candidate; packs: ``pack_rw_blocks(RW, H, 3)`` (else packed here). Returns (out [T, mb, H] fp32, hT,
+    gates [T, mb, 4H] fp32 = [r | z | n | q] or None, out16) or None when the shape / dtype is outside the kernels."""
+    return _cell_fwd("gru", None, zx, RW, H, 3, bRn, h0, mask, need_cache, packs, out16)
+
+
+def gru_seq_bwd(eps_tmh, gates, out, h0, RW, H, mask=None, dh_last=None, t_end=0, packs=None):
+    """eps_tmh: [T, mb, H] (fp32 / bf16 / fp16); gates / out: the forward's caches. Returns (dz [T, mb, 4H] fp32 =
+    [dzr | dzz | dzn | dzn*r]: columns :3H are the input-side deltas, columns :2H and 3H: the recurrent-side ones;
+    dh0) or None."""
+    return _cell_bwd("gru", None, eps_tmh, gates, out, h0, RW, H, 3, mask, dh_last, t_end, packs)
+
+
+def rnn_seq_fwd(zx, RW, H, act, h0=None, mask=None, packs=None, out16=False):
+    """SimpleRnn recurrence h_t = act(zx_t + h_{t-1}·RW) * mask_t, act "tanh" or "relu"; zx [T, mb, H], RW [H, H].
+    Returns (out [T, mb, H] fp32, hT, out16) or None. The backward needs no cache beyond ``out``."""
+    if act not in _ACTC:
+        return None
+    r = _cell_fwd("rnn", act, zx, RW, H, 1, None, h0, mask, False, packs, out16)
+    return None if r is None else (r[0], r[1], r[3])
+
+
+def rnn_seq_bwd(eps_tmh, out, RW, H, act, mask=None, dh_last=None, t_end=0, packs=None):
+    """Returns (dz [T, mb, H] fp32, dh0) or None."""
+    if act not in _ACTC:
+        return None
+    return _cell_bwd("rnn", act, eps_tmh, None, out, None, RW, H, 1, mask, dh_last, t_end, packs)
 
 
 def lstm_bwd_prep(dz, out, h0, call, c0, peephole, dtype):
