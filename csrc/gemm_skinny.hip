@@ -33,23 +33,12 @@
 // expert's blocks leave before their first weight load, the others multiply the first ceil(cnt[e] / 16) fragments,
 // the panel rows are gathered through src_of or read from the expert-sorted buffer, only live rows are written, and
 // split-K partials are kept compactly, [S][Ntok * k][Np].
-#include "common.h"
-#include "mfma_tile.h"
+//
+// The epilogue, the split-K partial layout and merge launches, the routing-plan prelude of the grouped product, the
+// split rule and the operand checks are csrc/skinny_body.h's, shared with csrc/gemm_wq.hip.
+#include "skinny_body.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float sk_f4;
-typedef __attribute__((ext_vector_type(4))) unsigned sk_u4;
-typedef __attribute__((ext_vector_type(2))) unsigned sk_u2;
-template <typename T> using SV8 = T __attribute__((ext_vector_type(8)));
-template <typename T> using SV4 = T __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ sk_f4 sk_mma(SV8<__bf16> a, SV8<__bf16> b, sk_f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ sk_f4 sk_mma(SV8<_Float16> a, SV8<_Float16> b, sk_f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 template <int LAY> struct SkLay;
 template <> struct SkLay<0> {
@@ -215,55 +204,6 @@ __device__ __forceinline__ void sk_block(const hb* __restrict__ W, long long ldw
   }
 }
 
-struct SkEpi {
-  void* out;             // [M, ldo] 16-bit
-  const void* bias;      // [N] or null
-  int ldo, bias_dt, beta, act;
-};
-
-// G consecutive columns n .. n + G - 1 of row m (G 4 / 8): bias, beta·out, activation, one rounding; one vector store
-// where the G columns exist and out + n is aligned to it, masked element stores elsewhere
-template <typename hb, int G>
-__device__ __forceinline__ void sk_epilogue(const SkEpi& e, const float* v, int m, int n, int N) {
-  if (n >= N) return;
-  hb* o = reinterpret_cast<hb*>(e.out) + (long long)m * e.ldo + n;
-  typedef hb OV __attribute__((ext_vector_type(G)));
-  const bool whole = n + G <= N && (reinterpret_cast<uintptr_t>(o) & (2 * G - 1)) == 0;
-  float t[G];
-#pragma unroll
-  for (int r = 0; r < G; ++r) t[r] = v[r];
-  if (e.bias) {
-#pragma unroll
-    for (int r = 0; r < G; ++r)
-      if (n + r < N) t[r] += ld_any(e.bias, e.bias_dt, n + r);
-  }
-  if (e.beta) {
-    if (whole) {
-      const OV old = *reinterpret_cast<const OV*>(o);
-#pragma unroll
-      for (int r = 0; r < G; ++r) t[r] += (float)old[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < G; ++r)
-        if (n + r < N) t[r] += (float)o[r];
-    }
-  }
-  if (e.act == 4) {
-#pragma unroll
-    for (int r = 0; r < G; ++r) t[r] = gelu_f(t[r]);
-  }
-  if (whole) {
-    OV nv;
-#pragma unroll
-    for (int r = 0; r < G; ++r) nv[r] = (hb)t[r];
-    *reinterpret_cast<OV*>(o) = nv;
-  } else {
-#pragma unroll
-    for (int r = 0; r < G; ++r)
-      if (n + r < N) o[r] = (hb)t[r];
-  }
-}
-
 // wave 3's accumulators of fragment f as the lane's NC consecutive columns
 template <int LAY, int MF>
 __device__ __forceinline__ void sk_lane_row(const sk_f4 (&acc)[SkLay<LAY>::NFR][MF], int f, float* vals) {
@@ -308,37 +248,13 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(const hb* __restrict__
     if (m >= M) continue;
     float vals[NC];
     sk_lane_row<LAY, MF>(acc, f, vals);
-    if (gridDim.y > 1) sk_store_partial<NC>(ws + ((long long)blockIdx.y * M + m) * Np + n, vals);
+    if (gridDim.y > 1) sk_store_partial<NC>(sk_partial(ws, blockIdx.y, M, m, Np, n), vals);
     else sk_finish<hb, NC>(epi, vals, m, n, N);
   }
 }
 
-// split-K merge: the S partial planes [M, Np] summed in split order, then the epilogue
-template <typename hb>
-__global__ __launch_bounds__(256) void skinny_merge_kernel(const float* __restrict__ ws, int S, int M, int N, int Np,
-                                                           SkEpi epi) {
-  const int q4 = Np >> 2;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= M * q4) return;
-  const int m = idx / q4, n = (idx - m * q4) * 4;
-  if (n >= N) return;
-  sk_f4 s = *reinterpret_cast<const sk_f4*>(ws + (long long)m * Np + n);
-  for (int p = 1; p < S; ++p) s += *reinterpret_cast<const sk_f4*>(ws + ((long long)p * M + m) * Np + n);
-  const float vals[4] = {s[0], s[1], s[2], s[3]};
-  sk_epilogue<hb, 4>(epi, vals, m, n, N);
-}
-
-// The routing plan of csrc/moe.hip as the grouped product reads it (device pointers, int32).
-struct SkPlan {
-  const int* cnt;      // [X] assignments per expert
-  const int* off;      // [X + 1] first row of every expert's segment of the sorted buffers
-  const int* src_of;   // [Rcap] assignment n*k + j of a live row; read in gather mode only
-  int Ntok, k, X, A;   // A = Ntok * k
-  long long Rcap;
-};
-
 // Block (nb, e, s) of the grouped product: skinny_gemm_kernel's body on expert e's rows of the stacked parameter, over
-// the expert's live rows only. rows = cnt[e], held to the MF fragments and to the sorted buffer whatever the plan holds.
+// the expert's live rows only.
 template <typename hb, int MF, int LAY, bool GATHER>
 __global__ __launch_bounds__(256) void skinny_grouped_kernel(const hb* __restrict__ W, long long ldw,
                                                              const hb* __restrict__ x, int ldx, SkPlan p, int N, int K,
@@ -349,81 +265,36 @@ __global__ __launch_bounds__(256) void skinny_grouped_kernel(const hb* __restric
   __shared__ int rowsrc[MF * 16];                                          // the x row of panel row r, -1: zeros
   const int tid = threadIdx.x;
   const int e = blockIdx.y;
-  const int off = p.off[e];
-  const long long room = p.Rcap - off;
-  const int rows = off < 0 ? 0 : (int)min((long long)min(p.cnt[e], MF * 16), room);
-  if (rows <= 0) return;                                                   // block-uniform: no byte of an idle expert
-  const int mfl = (rows + 15) >> 4;                                        // live fragments
-  if (tid < MF * 16) {
-    int src = -1;
-    if (tid < rows) {
-      if (GATHER) {
-        const int a = p.src_of[off + tid];
-        src = (a >= 0 && a < p.A) ? a / p.k : -1;
-      } else {
-        src = off + tid;
-      }
-    }
-    rowsrc[tid] = src;
-  }
+  const SkGroup g = sk_group<MF>(p, e);
+  if (g.rows <= 0) return;                                                 // block-uniform: no byte of an idle expert
+  sk_group_rows<MF, GATHER>(p, g, rowsrc);
   const int NCH = (K + L::KC - 1) / L::KC;
   const int ch0 = blockIdx.z * cpb, ch1 = min(NCH, ch0 + cpb);
   const int n0 = blockIdx.x * L::CW;
   sk_f4 acc[L::NFR][MF];
   // rowsrc is read behind the body's first barrier
-  sk_block<hb, MF, LAY>(W + (long long)e * K * ldw, ldw, x, ldx, [&](int r) { return rowsrc[r]; }, mfl, N, K, n0, ch0,
-                        ch1, smem, acc);
+  sk_block<hb, MF, LAY>(W + (long long)e * K * ldw, ldw, x, ldx, [&](int r) { return rowsrc[r]; }, g.mfl, N, K, n0,
+                        ch0, ch1, smem, acc);
   if ((tid >> 6) != 3) return;
   const int lane = tid & 63, q = lane >> 4, c = lane & 15;
   const int Np = gridDim.x * L::CW, n = n0 + NC * q;
-  int pre = 0;                                                             // the compact row of the expert's first
-  if (gridDim.z > 1)
-    for (int i = 0; i < e; ++i) pre += p.cnt[i];
-  SkEpi le = epi;
-  if (epi.bias) le.bias = reinterpret_cast<const float*>(epi.bias) + (long long)e * N;
+  const int pre = gridDim.z > 1 ? sk_group_pre(p, e) : 0;
+  const SkEpi le = sk_expert_epi(epi, e, N);
 #pragma unroll
   for (int f = 0; f < MF; ++f) {
     const int m = f * 16 + c;
-    if (f >= mfl || m >= rows) continue;
+    if (f >= g.mfl || m >= g.rows) continue;
     float vals[NC];
     sk_lane_row<LAY, MF>(acc, f, vals);
     if (gridDim.z > 1) {
-      const int cr = pre + m;
-      if (cr >= 0 && cr < p.A) sk_store_partial<NC>(ws + ((long long)blockIdx.z * p.A + cr) * Np + n, vals);
+      const int cr = pre + m;                                              // the compact row
+      if (cr >= 0 && cr < p.A) sk_store_partial<NC>(sk_partial(ws, blockIdx.z, p.A, cr, Np, n), vals);
     } else {
-      sk_finish<hb, NC>(le, vals, off + m, n, N);
+      sk_finish<hb, NC>(le, vals, g.off + m, n, N);
     }
   }
 }
 
-// split-K merge of the grouped product: compact row cr belongs to the expert e whose prefix of cnt covers it; the S
-// partial planes [A, Np] summed in split order, then the epilogue into row off[e] + r
-template <typename hb>
-__global__ __launch_bounds__(256) void skinny_merge_grouped_kernel(const float* __restrict__ ws, int S, SkPlan p,
-                                                                   int mrows, int N, int Np, SkEpi epi) {
-  const int q4 = Np >> 2;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.A * q4) return;
-  const int cr = idx / q4, n = (idx - cr * q4) * 4;
-  if (n >= N) return;
-  int e = 0, run = 0;
-  for (; e < p.X; ++e) {
-    const int ce = p.cnt[e];
-    if (cr < run + ce) break;
-    run += ce;
-  }
-  if (e >= p.X) return;
-  const int r = cr - run, off = p.off[e];
-  if (r < 0 || r >= mrows || off < 0 || (long long)off + r >= p.Rcap) return;     // what the product's blocks wrote
-  sk_f4 s = *reinterpret_cast<const sk_f4*>(ws + (long long)cr * Np + n);
-  for (int sp = 1; sp < S; ++sp) s += *reinterpret_cast<const sk_f4*>(ws + ((long long)sp * p.A + cr) * Np + n);
-  SkEpi le = epi;
-  if (epi.bias) le.bias = reinterpret_cast<const float*>(epi.bias) + (long long)e * N;
-  const float vals[4] = {s[0], s[1], s[2], s[3]};
-  sk_epilogue<hb, 4>(le, vals, off + r, n, N);
-}
-
-inline bool sk_al16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int sk_cw(int lay) { return lay == 0 ? 16 : (lay == 1 ? 128 : 64); }
 inline int sk_kc(int lay) { return lay == 0 ? 256 : 128; }
 inline bool sk_shape_ok(long long K, long long N) { return K >= 1 && N >= 1 && K <= (1 << 24) && N <= (1 << 24); }
@@ -450,41 +321,21 @@ inline int sk_layout(int width, int M, long long N, long long K, long long sk, l
   return -1;
 }
 
-// split count and chunks per block from (layout, M, N, K) alone: enough blocks for two per compute unit, but never so
-// many that the fp32 partials (written and read once: 8 S M Np bytes) outweigh the weight bytes (2 K Np)
-void sk_split(int lay, int M, long long N, long long K, int* S, int* cpb) {
-  const long long nbk = (N + sk_cw(lay) - 1) / sk_cw(lay);
-  const int NCH = (int)((K + sk_kc(lay) - 1) / sk_kc(lay));
-  long long s = (512 + nbk - 1) / nbk;
-  const long long cap = K / (4LL * M);
-  if (s > cap) s = cap;
-  if (s > NCH) s = NCH;
-  if (s < 1) s = 1;
-  *cpb = (NCH + (int)s - 1) / (int)s;
-  *S = (NCH + *cpb - 1) / *cpb;
+// split count and chunks per block from (layout, M, N, K) alone: sk_split_plan on the layout's column blocks and chunk
+// depth, 16 weight bits per element
+inline void sk_split(int lay, int M, long long N, long long K, int* S, int* cpb) {
+  sk_split_plan(sk_cw(lay), sk_kc(lay), 16, M, N, K, S, cpb);
 }
-
-// sk_split for the grouped product, from (layout, Ntok, k, X, N, K) alone: min(X, Ntok * k) experts count as active
-// (the blocks of the others leave at once), and the partials of the Ntok * k live rows are weighed against those
-// experts' weight bytes
-void sk_split_grouped(int lay, int Ntok, int k, int X, long long N, long long K, int* S, int* cpb) {
-  const long long nbk = (N + sk_cw(lay) - 1) / sk_cw(lay);
-  const int NCH = (int)((K + sk_kc(lay) - 1) / sk_kc(lay));
-  const int A = Ntok * k, active = X < A ? X : A;
-  const long long blocks = nbk * active;
-  long long s = (512 + blocks - 1) / blocks;
-  const long long cap = (long long)active * K / (4LL * A);
-  if (s > cap) s = cap;
-  if (s > NCH) s = NCH;
-  if (s < 1) s = 1;
-  *cpb = (NCH + (int)s - 1) / (int)s;
-  *S = (NCH + *cpb - 1) / *cpb;
+// sk_split for the grouped product, from (layout, Ntok, k, X, N, K) alone
+inline void sk_split_grouped(int lay, int Ntok, int k, int X, long long N, long long K, int* S, int* cpb) {
+  sk_split_plan_grouped(sk_cw(lay), sk_kc(lay), 16, Ntok, k, X, N, K, S, cpb);
 }
 
 inline bool sk_grouped_ok(int width, int Ntok, int k, int X, long long N, long long K) {
-  return (width == 0 || width == 4 || width == 8) && sk_shape_ok(K, N) && Ntok >= 1 && Ntok <= 64 && k >= 1 &&
-         k <= 8 && X >= 1 && X <= 64 && k <= X && (long long)X * K <= (1LL << 31);
+  return (width == 0 || width == 4 || width == 8) && sk_shape_ok(K, N) && sk_routing_ok(Ntok, k, X) &&
+         (long long)X * K <= (1LL << 31);
 }
+
 inline int sk_grouped_layout(int width, int Ntok, int k, int X, long long N, long long K) {
   const int A = Ntok * k;
   const int wd = width ? width : sk_width_rule(Ntok, N * (X < A ? X : A), K);
@@ -502,8 +353,7 @@ DL4J_API long long dl4j_skinny_gemm_workspace(int width, int M, long long N, lon
   if (lay < 0) return -1;
   int S, cpb;
   sk_split(lay, M, N, K, &S, &cpb);
-  const long long Np = (N + sk_cw(lay) - 1) / sk_cw(lay) * sk_cw(lay);
-  return S > 1 ? (long long)S * M * Np : 0;
+  return sk_ws_floats(S, M, N, sk_cw(lay));
 }
 
 // out [M, ldo] = act(x [M, ldx] · W + bias + beta·out), 1 <= M <= 64, W [K, N] of the same dtype read in place with
@@ -514,11 +364,10 @@ DL4J_API long long dl4j_skinny_gemm_workspace(int width, int M, long long N, lon
 DL4J_API int dl4j_skinny_gemm(int width, int dtype, const void* x, long long ldx, int M, long long N, long long K,
                               const void* W, long long sk, long long sn, void* out, long long ldo, const void* bias,
                               int bias_dt, int beta, int act, void* ws, hipStream_t s) {
-  if (!sk_shape_ok(K, N) || M < 1 || M > 64 || (dtype != 1 && dtype != 2)) return -1;
+  if (!sk_shape_ok(K, N) || !sk_dense_ok(M, beta, bias_dt) || !sk_operands_ok(dtype, x, ldx, K, out, ldo, N, act))
+    return -1;
   const int lay = sk_layout(width, M, N, K, sk, sn);
-  if (lay < 0 || !sk_al16(W) || !sk_al16(x) || ldx % 8 != 0 || ldx < K || ldx > 0x7fffffffLL) return -1;
-  if (!out || ldo < N || ldo > 0x7fffffffLL) return -1;
-  if ((act != 0 && act != 4) || (beta != 0 && beta != 1) || bias_dt < 0 || bias_dt > 2) return -1;
+  if (lay < 0 || !sk_al16(W)) return -1;
   int S, cpb;
   sk_split(lay, M, N, K, &S, &cpb);
   if (S > 1 && !sk_al16(ws)) return -1;
@@ -526,7 +375,7 @@ DL4J_API int dl4j_skinny_gemm(int width, int dtype, const void* x, long long ldx
   const long long ldw = lay == 0 ? sn : sk;
   const SkEpi epi{out, bias, (int)ldo, bias_dt, beta, act};
   const dim3 grid((unsigned)nbk, (unsigned)S);
-  const int mf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+  const int mf = sk_mf(M);
 #define L(T, F, Y) hipLaunchKernelGGL((skinny_gemm_kernel<T, F, Y>), grid, dim3(256), 0, s, (const T*)W, ldw,        \
                                       (const T*)x, (int)ldx, M, (int)N, (int)K, cpb, (float*)ws, epi)
 #define LY(T, F) do { if (lay == 0) L(T, F, 0); else if (lay == 1) L(T, F, 1); else L(T, F, 2); } while (0)
@@ -536,15 +385,8 @@ DL4J_API int dl4j_skinny_gemm(int width, int dtype, const void* x, long long ldx
 #undef LM
 #undef LY
 #undef L
-  int rc = (int)hipGetLastError();
-  if (rc != 0 || S == 1) return rc;
-  const int Np = nbk * cw;
-  const dim3 mg((unsigned)(((long long)M * (Np / 4) + 255) / 256));
-  if (dtype == 1)
-    hipLaunchKernelGGL(skinny_merge_kernel<__bf16>, mg, dim3(256), 0, s, (const float*)ws, S, M, (int)N, Np, epi);
-  else
-    hipLaunchKernelGGL(skinny_merge_kernel<_Float16>, mg, dim3(256), 0, s, (const float*)ws, S, M, (int)N, Np, epi);
-  return (int)hipGetLastError();
+  const int rc = (int)hipGetLastError();
+  return rc != 0 || S == 1 ? rc : sk_merge(dtype, ws, S, M, (int)N, nbk * cw, epi, s);
 }
 
 // Floats of split-K workspace dl4j_skinny_gemm_grouped needs for (width, Ntok, k, X, N, K): 0 when the product runs
@@ -554,8 +396,7 @@ DL4J_API long long dl4j_skinny_gemm_grouped_workspace(int width, int Ntok, int k
   const int lay = sk_grouped_layout(width, Ntok, k, X, N, K);
   int S, cpb;
   sk_split_grouped(lay, Ntok, k, X, N, K, &S, &cpb);
-  const long long Np = (N + sk_cw(lay) - 1) / sk_cw(lay) * sk_cw(lay);
-  return S > 1 ? (long long)S * Ntok * k * Np : 0;
+  return sk_ws_floats(S, (long long)Ntok * k, N, sk_cw(lay));
 }
 
 // The experts' products of a mixture-of-experts step of Ntok <= 64 tokens on the stacked N-contiguous parameter W
@@ -570,11 +411,8 @@ DL4J_API int dl4j_skinny_gemm_grouped(int width, int dtype, const void* x, long 
                                       int X, long long Rcap, long long N, long long K, const void* W, long long ldw,
                                       const int* cnt, const int* off, const int* src_of, void* out, long long ldo,
                                       const float* bias, int act, void* ws, hipStream_t s) {
-  if (!sk_grouped_ok(width, Ntok, k, X, N, K) || (dtype != 1 && dtype != 2) || (gather != 0 && gather != 1)) return -1;
-  if (!sk_al16(W) || ldw % 8 != 0 || ldw < N || !sk_al16(x) || ldx % 8 != 0 || ldx < K || ldx > 0x7fffffffLL) return -1;
-  if (!out || ldo < N || ldo > 0x7fffffffLL || Rcap < (long long)Ntok * k || Rcap > 0x7fffffffLL) return -1;
-  const auto al4 = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
-  if (!al4(cnt) || !al4(off) || (gather && !al4(src_of)) || (bias && !al4(bias)) || (act != 0 && act != 4)) return -1;
+  if (!sk_grouped_ok(width, Ntok, k, X, N, K) || !sk_operands_ok(dtype, x, ldx, K, out, ldo, N, act)) return -1;
+  if (!sk_plan_ok(gather, Ntok, k, Rcap, cnt, off, src_of, bias) || !sk_al16(W) || ldw % 8 != 0 || ldw < N) return -1;
   const int lay = sk_grouped_layout(width, Ntok, k, X, N, K);
   int S, cpb;
   sk_split_grouped(lay, Ntok, k, X, N, K, &S, &cpb);
@@ -583,7 +421,7 @@ DL4J_API int dl4j_skinny_gemm_grouped(int width, int dtype, const void* x, long 
   const SkEpi epi{out, bias, (int)ldo, 0, 0, act};
   const SkPlan plan{cnt, off, src_of, Ntok, k, X, Ntok * k, Rcap};
   const dim3 grid((unsigned)nbk, (unsigned)X, (unsigned)S);
-  const int mf = Ntok <= 16 ? 1 : (Ntok <= 32 ? 2 : 4);
+  const int mf = sk_mf(Ntok);
 #define L(T, F, Y, G) hipLaunchKernelGGL((skinny_grouped_kernel<T, F, Y, G>), grid, dim3(256), 0, s, (const T*)W,    \
                                          ldw, (const T*)x, (int)ldx, plan, (int)N, (int)K, cpb, (float*)ws, epi)
 #define LG(T, F, Y) do { if (gather) L(T, F, Y, true); else L(T, F, Y, false); } while (0)
@@ -595,15 +433,6 @@ DL4J_API int dl4j_skinny_gemm_grouped(int width, int dtype, const void* x, long 
 #undef LY
 #undef LG
 #undef L
-  int rc = (int)hipGetLastError();
-  if (rc != 0 || S == 1) return rc;
-  const int Np = nbk * cw;
-  const dim3 mg((unsigned)(((long long)plan.A * (Np / 4) + 255) / 256));
-  if (dtype == 1)
-    hipLaunchKernelGGL(skinny_merge_grouped_kernel<__bf16>, mg, dim3(256), 0, s, (const float*)ws, S, plan, mf * 16,
-                       (int)N, Np, epi);
-  else
-    hipLaunchKernelGGL(skinny_merge_grouped_kernel<_Float16>, mg, dim3(256), 0, s, (const float*)ws, S, plan, mf * 16,
-                       (int)N, Np, epi);
-  return (int)hipGetLastError();
+  const int rc = (int)hipGetLastError();
+  return rc != 0 || S == 1 ? rc : sk_merge_grouped(dtype, ws, S, plan, (int)N, nbk * cw, epi, s);
 }

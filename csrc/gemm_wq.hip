@@ -35,20 +35,12 @@
 // activations (no gathered copy and no gather launch), or row off[e] + r of an expert-sorted buffer; rows from cnt[e]
 // on are zeros. Output row off[e] + r of the expert-sorted buffer, live rows only. Split-K partials are kept for live
 // rows only, [S][Ntok * k][Np] at the compact row (exclusive prefix of cnt)[e] + r, and merged in split order.
-#include "common.h"
-#include "mfma_tile.h"
+//
+// The epilogue, the split-K partial layout and merge launches, the routing-plan prelude of the grouped product, the
+// split rule and the operand checks are csrc/skinny_body.h's, shared with csrc/gemm_skinny.hip.
+#include "skinny_body.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float wq_f4;
-template <typename T> using WV8 = T __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ wq_f4 wq_mma(WV8<__bf16> a, WV8<__bf16> b, wq_f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ wq_f4 wq_mma(WV8<_Float16> a, WV8<_Float16> b, wq_f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 constexpr int WQ_KT = 64;        // k per tile
 constexpr int WQ_KC = 256;       // k per chunk: one tile per wave
@@ -57,34 +49,34 @@ constexpr int WQ_LDX = WQ_KC + 8;
 __device__ __forceinline__ float wq_scale(unsigned byte) { return __uint_as_float(byte << 23); }
 
 // 8 codes -> the fragment: fp8 from two dwords, fp4 from one
-__device__ __forceinline__ WV8<__bf16> wq_deq8(unsigned a, unsigned b, float sc, __bf16) {
+__device__ __forceinline__ SV8<__bf16> wq_deq8(unsigned a, unsigned b, float sc, __bf16) {
   const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, sc, false);
   const auto p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, sc, true);
   const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, sc, false);
   const auto p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, sc, true);
-  return WV8<__bf16>{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+  return SV8<__bf16>{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
-__device__ __forceinline__ WV8<_Float16> wq_deq8(unsigned a, unsigned b, float sc, _Float16) {
+__device__ __forceinline__ SV8<_Float16> wq_deq8(unsigned a, unsigned b, float sc, _Float16) {
   const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(a, sc, false);
   const auto p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(a, sc, true);
   const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, sc, false);
   const auto p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, sc, true);
-  return WV8<_Float16>{(_Float16)p0[0], (_Float16)p0[1], (_Float16)p1[0], (_Float16)p1[1],
+  return SV8<_Float16>{(_Float16)p0[0], (_Float16)p0[1], (_Float16)p1[0], (_Float16)p1[1],
                        (_Float16)p2[0], (_Float16)p2[1], (_Float16)p3[0], (_Float16)p3[1]};
 }
-__device__ __forceinline__ WV8<__bf16> wq_deq4(unsigned a, float sc, __bf16) {
+__device__ __forceinline__ SV8<__bf16> wq_deq4(unsigned a, float sc, __bf16) {
   const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 0);
   const auto p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 1);
   const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 2);
   const auto p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 3);
-  return WV8<__bf16>{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+  return SV8<__bf16>{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
-__device__ __forceinline__ WV8<_Float16> wq_deq4(unsigned a, float sc, _Float16) {
+__device__ __forceinline__ SV8<_Float16> wq_deq4(unsigned a, float sc, _Float16) {
   const auto p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(a, sc, 0);
   const auto p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(a, sc, 1);
   const auto p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(a, sc, 2);
   const auto p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(a, sc, 3);
-  return WV8<_Float16>{(_Float16)p0[0], (_Float16)p0[1], (_Float16)p1[0], (_Float16)p1[1],
+  return SV8<_Float16>{(_Float16)p0[0], (_Float16)p0[1], (_Float16)p1[0], (_Float16)p1[1],
                        (_Float16)p2[0], (_Float16)p2[1], (_Float16)p3[0], (_Float16)p3[1]};
 }
 
@@ -93,7 +85,7 @@ template <int BITS> struct WqFmt;
 template <> struct WqFmt<8> {
   static constexpr int CT = 1;
   // fragment (ct, j) of the lane's 16 bytes w and its scale bytes sc
-  template <typename hb> static __device__ __forceinline__ WV8<hb> frag(const uint4& w, unsigned sc, int, int j) {
+  template <typename hb> static __device__ __forceinline__ SV8<hb> frag(const uint4& w, unsigned sc, int, int j) {
     const float s = wq_scale((sc >> (8 * j)) & 0xffu);
     return j == 0 ? wq_deq8(w.x, w.y, s, hb()) : wq_deq8(w.z, w.w, s, hb());
   }
@@ -118,7 +110,7 @@ template <> struct WqFmt<8> {
 };
 template <> struct WqFmt<4> {
   static constexpr int CT = 2;
-  template <typename hb> static __device__ __forceinline__ WV8<hb> frag(const uint4& w, unsigned sc, int ct, int j) {
+  template <typename hb> static __device__ __forceinline__ SV8<hb> frag(const uint4& w, unsigned sc, int ct, int j) {
     const int i = ct * 2 + j;
     const float s = wq_scale((sc >> (8 * i)) & 0xffu);
     const unsigned d = i == 0 ? w.x : (i == 1 ? w.y : (i == 2 ? w.z : w.w));
@@ -145,45 +137,22 @@ template <> struct WqFmt<4> {
   }
 };
 
-struct WqEpi {
-  void* out;             // [M, ldo] 16-bit
-  const void* bias;      // [N] or null
-  int ldo, bias_dt, beta, act;
-};
-
-// four consecutive columns n .. n + 3 of row m: bias, beta·out, activation, one rounding, masked store
-template <typename hb>
-__device__ __forceinline__ void wq_epilogue(const WqEpi& e, wq_f4 v, int m, int n, int N) {
-  hb* o = reinterpret_cast<hb*>(e.out) + (long long)m * e.ldo + n;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (n + r >= N) break;
-    float t = v[r];
-    if (e.bias) t += ld_any(e.bias, e.bias_dt, n + r);
-    if (e.beta) t += (float)o[r];
-    if (e.act == 4) t = gelu_f(t);
-    o[r] = (hb)t;
-  }
-}
-
-template <int BITS, typename hb, int MF>
-__global__ __launch_bounds__(256) void wq_gemm_kernel(const uint4* __restrict__ codes,
-                                                      const unsigned char* __restrict__ scales,
-                                                      const hb* __restrict__ x, int ldx, int M, int N, int K, int KTn,
-                                                      int cpb, float* __restrict__ ws, WqEpi epi) {
+// The K loop of one block and the waves' sum in wave order: tail(s, m, n) receives the block's sums for panel row m
+// and columns n .. n + 3, for every row of the live fragments. src(r): the x row of panel row r or -1 for zeros; mfl:
+// the live fragments (block-uniform). xs: the x panel [16 MF, WQ_LDX], reused for the wave reduction.
+template <int BITS, typename hb, int MF, typename Src, typename Tail>
+__device__ __forceinline__ void wq_block(const uint4* __restrict__ codes, const unsigned char* __restrict__ scales,
+                                         const hb* __restrict__ x, int ldx, Src src, int mfl, int K, int KTn, int nb,
+                                         int ch0, int ch1, hb* xs, Tail tail) {
   using F = WqFmt<BITS>;
   constexpr int CT = F::CT, CW = 16 * CT;
-  __shared__ __attribute__((aligned(16))) hb xs[MF * 16 * WQ_LDX];        // reused for the wave reduction below
-  static_assert(sizeof(hb) * MF * 16 * WQ_LDX >= 4 * CT * MF * 64 * sizeof(wq_f4), "reduction fits the x panel");
+  static_assert(sizeof(hb) * MF * 16 * WQ_LDX >= 4 * CT * MF * 64 * sizeof(sk_f4), "reduction fits the x panel");
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, c = lane & 15;
-  const int nb = blockIdx.x;
-  const int NC = (KTn + 3) >> 2;
-  const int ch0 = blockIdx.y * cpb, ch1 = min(NC, ch0 + cpb);
-  wq_f4 acc[CT][MF];
+  sk_f4 acc[CT][MF];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-    for (int f = 0; f < MF; ++f) acc[ct][f] = wq_f4{0.f, 0.f, 0.f, 0.f};
+    for (int f = 0; f < MF; ++f) acc[ct][f] = sk_f4{0.f, 0.f, 0.f, 0.f};
 
   for (int ch = ch0; ch < ch1; ++ch) {
     const int kt = ch * 4 + wave;
@@ -197,209 +166,97 @@ __global__ __launch_bounds__(256) void wq_gemm_kernel(const uint4* __restrict__ 
     }
     __syncthreads();                                                   // the previous chunk's fragment reads are done
     const int kc = ch * WQ_KC;
-    for (int i = tid; i < MF * 16 * (WQ_KC / 8); i += 256) {
+    for (int i = tid; i < mfl * 16 * (WQ_KC / 8); i += 256) {
       const int r = i >> 5, k8 = (i & 31) * 8;
-      WV8<hb> v = WV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-      if (r < M && kc + k8 < K) v = *reinterpret_cast<const WV8<hb>*>(x + (long long)r * ldx + kc + k8);
-      *reinterpret_cast<WV8<hb>*>(xs + r * WQ_LDX + k8) = v;
+      const int sr = src(r);
+      SV8<hb> v = SV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+      if (sr >= 0 && kc + k8 < K) v = *reinterpret_cast<const SV8<hb>*>(x + (long long)sr * ldx + kc + k8);
+      *reinterpret_cast<SV8<hb>*>(xs + r * WQ_LDX + k8) = v;
     }
     __syncthreads();
     if (live) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int koff = wave * WQ_KT + j * 32 + q * 8;
-        WV8<hb> b[MF];
+        SV8<hb> b[MF];
 #pragma unroll
-        for (int f = 0; f < MF; ++f) b[f] = *reinterpret_cast<const WV8<hb>*>(xs + (f * 16 + c) * WQ_LDX + koff);
+        for (int f = 0; f < MF; ++f) {
+          b[f] = SV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
+          if (f < mfl) b[f] = *reinterpret_cast<const SV8<hb>*>(xs + (f * 16 + c) * WQ_LDX + koff);
+        }
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
-          const WV8<hb> a = F::template frag<hb>(w, sc, ct, j);
+          const SV8<hb> a = F::template frag<hb>(w, sc, ct, j);
 #pragma unroll
-          for (int f = 0; f < MF; ++f) acc[ct][f] = wq_mma(a, b[f], acc[ct][f]);
+          for (int f = 0; f < MF; ++f)
+            if (f < mfl) acc[ct][f] = sk_mma(a, b[f], acc[ct][f]);     // block-uniform: dead fragments cost nothing
         }
       }
     }
   }
   // the four waves' sums, in wave order
   __syncthreads();
-  wq_f4* red = reinterpret_cast<wq_f4*>(xs);
+  sk_f4* red = reinterpret_cast<sk_f4*>(xs);
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
     for (int f = 0; f < MF; ++f) red[((wave * CT + ct) * MF + f) * 64 + lane] = acc[ct][f];
   __syncthreads();
-  const int Np = gridDim.x * CW;
-  for (int idx = tid; idx < CT * MF * 64; idx += 256) {
-    const int l = idx & 63, f = (idx >> 6) % MF, ct = (idx >> 6) / MF;
-    wq_f4 s = red[((0 * CT + ct) * MF + f) * 64 + l];
+  for (int idx = tid; idx < CT * mfl * 64; idx += 256) {
+    const int l = idx & 63, f = (idx >> 6) % mfl, ct = (idx >> 6) / mfl;
+    sk_f4 s = red[((0 * CT + ct) * MF + f) * 64 + l];
 #pragma unroll
     for (int wv = 1; wv < 4; ++wv) s += red[((wv * CT + ct) * MF + f) * 64 + l];
-    const int m = f * 16 + (l & 15), n = nb * CW + ct * 16 + 4 * (l >> 4);
-    if (m >= M) continue;
-    if (gridDim.y > 1) *reinterpret_cast<wq_f4*>(ws + ((long long)blockIdx.y * M + m) * Np + n) = s;
-    else wq_epilogue<hb>(epi, s, m, n, N);
+    tail(s, f * 16 + (l & 15), nb * CW + ct * 16 + 4 * (l >> 4));
   }
 }
 
-// split-K merge: the S partial planes [M, Np] summed in split order, then the epilogue
-template <typename hb>
-__global__ __launch_bounds__(256) void wq_merge_kernel(const float* __restrict__ ws, int S, int M, int N, int Np,
-                                                       WqEpi epi) {
-  const int q4 = Np >> 2;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= M * q4) return;
-  const int m = idx / q4, n = (idx - m * q4) * 4;
-  if (n >= N) return;
-  wq_f4 s = *reinterpret_cast<const wq_f4*>(ws + (long long)m * Np + n);
-  for (int p = 1; p < S; ++p) s += *reinterpret_cast<const wq_f4*>(ws + ((long long)p * M + m) * Np + n);
-  wq_epilogue<hb>(epi, s, m, n, N);
+template <int BITS, typename hb, int MF>
+__global__ __launch_bounds__(256) void wq_gemm_kernel(const uint4* __restrict__ codes,
+                                                      const unsigned char* __restrict__ scales,
+                                                      const hb* __restrict__ x, int ldx, int M, int N, int K, int KTn,
+                                                      int cpb, float* __restrict__ ws, SkEpi epi) {
+  __shared__ __attribute__((aligned(16))) hb xs[MF * 16 * WQ_LDX];
+  const int NC = (KTn + 3) >> 2;
+  const int ch0 = blockIdx.y * cpb, ch1 = min(NC, ch0 + cpb);
+  const int Np = gridDim.x * 16 * WqFmt<BITS>::CT;
+  wq_block<BITS, hb, MF>(codes, scales, x, ldx, [M](int r) { return r < M ? r : -1; }, MF, K, KTn, blockIdx.x, ch0,
+                         ch1, xs, [&](sk_f4 s, int m, int n) {
+                           if (m >= M) return;
+                           if (gridDim.y > 1) *reinterpret_cast<sk_f4*>(sk_partial(ws, blockIdx.y, M, m, Np, n)) = s;
+                           else sk_epilogue4<hb>(epi, s, m, n, N);
+                         });
 }
 
-// The routing plan of csrc/moe.hip as the grouped product reads it (device pointers, int32).
-struct WqPlan {
-  const int* cnt;      // [X] assignments per expert
-  const int* off;      // [X + 1] first row of every expert's segment of the sorted buffers
-  const int* src_of;   // [Rcap] assignment n*k + j of a live row; read in gather mode only
-  int Ntok, k, X, A;   // A = Ntok * k
-  long long Rcap;
-};
-
 // Block (nb, e, s) of the grouped product: wq_gemm_kernel's body on expert e's packed matrix, over the expert's live
-// rows only. rows = cnt[e], held to the MF fragments and to the sorted buffer whatever the plan holds.
+// rows only.
 template <int BITS, typename hb, int MF, bool GATHER>
 __global__ __launch_bounds__(256) void wq_gemm_grouped_kernel(const uint4* __restrict__ codes,
                                                               const unsigned char* __restrict__ scales,
                                                               long long cstride, long long sstride,
-                                                              const hb* __restrict__ x, int ldx, WqPlan p, int N, int K,
-                                                              int KTn, int cpb, float* __restrict__ ws, WqEpi epi) {
-  using F = WqFmt<BITS>;
-  constexpr int CT = F::CT, CW = 16 * CT;
-  __shared__ __attribute__((aligned(16))) hb xs[MF * 16 * WQ_LDX];        // reused for the wave reduction below
+                                                              const hb* __restrict__ x, int ldx, SkPlan p, int N, int K,
+                                                              int KTn, int cpb, float* __restrict__ ws, SkEpi epi) {
+  __shared__ __attribute__((aligned(16))) hb xs[MF * 16 * WQ_LDX];
   __shared__ int rowsrc[MF * 16];                                          // the x row of panel row r, -1: zeros
-  static_assert(sizeof(hb) * MF * 16 * WQ_LDX >= 4 * CT * MF * 64 * sizeof(wq_f4), "reduction fits the x panel");
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, c = lane & 15;
-  const int nb = blockIdx.x, e = blockIdx.y;
-  const int off = p.off[e];
-  const long long room = p.Rcap - off;
-  const int rows = off < 0 ? 0 : (int)min((long long)min(p.cnt[e], MF * 16), room);
-  if (rows <= 0) return;                                                   // block-uniform: no byte of an idle expert
-  const int mfl = (rows + 15) >> 4;                                        // live fragments
-  codes += (long long)e * cstride;
-  scales += (long long)e * sstride;
-  if (tid < MF * 16) {
-    int src = -1;
-    if (tid < rows) {
-      if (GATHER) {
-        const int a = p.src_of[off + tid];
-        src = (a >= 0 && a < p.A) ? a / p.k : -1;
-      } else {
-        src = off + tid;
-      }
-    }
-    rowsrc[tid] = src;
-  }
+  const int e = blockIdx.y;
+  const SkGroup g = sk_group<MF>(p, e);
+  if (g.rows <= 0) return;                                                 // block-uniform: no byte of an idle expert
+  sk_group_rows<MF, GATHER>(p, g, rowsrc);
   const int NC = (KTn + 3) >> 2;
   const int ch0 = blockIdx.z * cpb, ch1 = min(NC, ch0 + cpb);
-  wq_f4 acc[CT][MF];
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int f = 0; f < MF; ++f) acc[ct][f] = wq_f4{0.f, 0.f, 0.f, 0.f};
-
-  for (int ch = ch0; ch < ch1; ++ch) {
-    const int kt = ch * 4 + wave;
-    const bool live = kt < KTn;                                        // wave-uniform
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    unsigned sc = 0x7f7f7f7fu;
-    if (live) {
-      const long long tile = (long long)nb * KTn + kt;
-      w = codes[tile * 64 + lane];
-      sc = F::load_scales(scales + (tile * 16 + c) * (CT * 2));
-    }
-    __syncthreads();                                                   // rowsrc is there; the previous chunk is read
-    const int kc = ch * WQ_KC;
-    for (int i = tid; i < mfl * 16 * (WQ_KC / 8); i += 256) {
-      const int r = i >> 5, k8 = (i & 31) * 8;
-      const int src = rowsrc[r];
-      WV8<hb> v = WV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-      if (src >= 0 && kc + k8 < K) v = *reinterpret_cast<const WV8<hb>*>(x + (long long)src * ldx + kc + k8);
-      *reinterpret_cast<WV8<hb>*>(xs + r * WQ_LDX + k8) = v;
-    }
-    __syncthreads();
-    if (live) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int koff = wave * WQ_KT + j * 32 + q * 8;
-        WV8<hb> b[MF];
-#pragma unroll
-        for (int f = 0; f < MF; ++f) {
-          b[f] = WV8<hb>{0, 0, 0, 0, 0, 0, 0, 0};
-          if (f < mfl) b[f] = *reinterpret_cast<const WV8<hb>*>(xs + (f * 16 + c) * WQ_LDX + koff);
-        }
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-          const WV8<hb> a = F::template frag<hb>(w, sc, ct, j);
-#pragma unroll
-          for (int f = 0; f < MF; ++f)
-            if (f < mfl) acc[ct][f] = wq_mma(a, b[f], acc[ct][f]);     // block-uniform: dead fragments cost nothing
-        }
-      }
-    }
-  }
-  // the four waves' sums, in wave order
-  __syncthreads();
-  wq_f4* red = reinterpret_cast<wq_f4*>(xs);
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int f = 0; f < MF; ++f) red[((wave * CT + ct) * MF + f) * 64 + lane] = acc[ct][f];
-  __syncthreads();
-  const int Np = gridDim.x * CW;
-  int pre = 0;                                                           // the compact row of the expert's first
-  if (gridDim.z > 1)
-    for (int i = 0; i < e; ++i) pre += p.cnt[i];
-  WqEpi le = epi;
-  if (epi.bias) le.bias = reinterpret_cast<const float*>(epi.bias) + (long long)e * N;
-  for (int idx = tid; idx < CT * mfl * 64; idx += 256) {
-    const int l = idx & 63, f = (idx >> 6) % mfl, ct = (idx >> 6) / mfl;
-    wq_f4 s = red[((0 * CT + ct) * MF + f) * 64 + l];
-#pragma unroll
-    for (int wv = 1; wv < 4; ++wv) s += red[((wv * CT + ct) * MF + f) * 64 + l];
-    const int m = f * 16 + (l & 15), n = nb * CW + ct * 16 + 4 * (l >> 4);
-    if (m >= rows) continue;
-    if (gridDim.z > 1) {
-      const int cr = pre + m;
-      if (cr >= 0 && cr < p.A) *reinterpret_cast<wq_f4*>(ws + ((long long)blockIdx.z * p.A + cr) * Np + n) = s;
-    } else {
-      wq_epilogue<hb>(le, s, off + m, n, N);
-    }
-  }
-}
-
-// split-K merge of the grouped product: compact row cr belongs to the expert e whose prefix of cnt covers it; the S
-// partial planes [A, Np] summed in split order, then the epilogue into row off[e] + r
-template <typename hb>
-__global__ __launch_bounds__(256) void wq_merge_grouped_kernel(const float* __restrict__ ws, int S, WqPlan p, int mrows,
-                                                               int N, int Np, WqEpi epi) {
-  const int q4 = Np >> 2;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.A * q4) return;
-  const int cr = idx / q4, n = (idx - cr * q4) * 4;
-  if (n >= N) return;
-  int e = 0, run = 0;
-  for (; e < p.X; ++e) {
-    const int ce = p.cnt[e];
-    if (cr < run + ce) break;
-    run += ce;
-  }
-  if (e >= p.X) return;
-  const int r = cr - run, off = p.off[e];
-  if (r < 0 || r >= mrows || off < 0 || (long long)off + r >= p.Rcap) return;     // what the product's blocks wrote
-  wq_f4 s = *reinterpret_cast<const wq_f4*>(ws + (long long)cr * Np + n);
-  for (int sp = 1; sp < S; ++sp) s += *reinterpret_cast<const wq_f4*>(ws + ((long long)sp * p.A + cr) * Np + n);
-  WqEpi le = epi;
-  if (epi.bias) le.bias = reinterpret_cast<const float*>(epi.bias) + (long long)e * N;
-  wq_epilogue<hb>(le, s, off + r, n, N);
+  const int Np = gridDim.x * 16 * WqFmt<BITS>::CT;
+  const int pre = gridDim.z > 1 ? sk_group_pre(p, e) : 0;
+  const SkEpi le = sk_expert_epi(epi, e, N);
+  // rowsrc is read behind the body's first barrier
+  wq_block<BITS, hb, MF>(codes + (long long)e * cstride, scales + (long long)e * sstride, x, ldx,
+                         [&](int r) { return rowsrc[r]; }, g.mfl, K, KTn, blockIdx.x, ch0, ch1, xs,
+                         [&](sk_f4 s, int m, int n) {
+                           if (m >= g.rows) return;
+                           const int cr = pre + m;                         // the compact row
+                           if (gridDim.z == 1) sk_epilogue4<hb>(le, s, g.off + m, n, N);
+                           else if (cr >= 0 && cr < p.A)
+                             *reinterpret_cast<sk_f4*>(sk_partial(ws, blockIdx.z, p.A, cr, Np, n)) = s;
+                         });
 }
 
 // One wave per tile (nb, kt): W [K, N] with element strides (sk, sn) -> the tile's 1024 code bytes and scale bytes.
@@ -464,7 +321,7 @@ __global__ __launch_bounds__(256) void wq_dequant_kernel(const uint4* __restrict
     if (n >= N) continue;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const WV8<hb> v = F::template frag<hb>(w, sc, ct, j);
+      const SV8<hb> v = F::template frag<hb>(w, sc, ct, j);
       const int k0 = kt * WQ_KT + j * 32 + q * 8;
 #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -473,45 +330,23 @@ __global__ __launch_bounds__(256) void wq_dequant_kernel(const uint4* __restrict
   }
 }
 
-inline bool wq_al16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int wq_cw(int bits) { return bits == 8 ? 16 : 32; }
 inline bool wq_shape_ok(int bits, long long K, long long N) {
   return (bits == 8 || bits == 4) && K >= 32 && K % 32 == 0 && N >= 1 && K <= (1 << 24) && N <= (1 << 24);
 }
 
-// split count and chunks per block from (bits, M, N, K) alone: enough blocks for two per compute unit, but never so
-// many that the fp32 partials (written and read once: 8 S M Np bytes) outweigh the weight bytes (K Np bits / 8)
-void wq_split(int bits, int M, int N, int K, int* S, int* cpb) {
-  const int nbk = (N + wq_cw(bits) - 1) / wq_cw(bits);
-  const int NC = ((K + WQ_KT - 1) / WQ_KT + 3) / 4;
-  int s = (512 + nbk - 1) / nbk;
-  const int cap = (int)((long long)K * bits / (64LL * M));
-  if (s > cap) s = cap;
-  if (s > NC) s = NC;
-  if (s < 1) s = 1;
-  *cpb = (NC + s - 1) / s;
-  *S = (NC + *cpb - 1) / *cpb;
+// split count and chunks per block from (bits, M, N, K) alone: sk_split_plan on this format's column blocks and the
+// 256-deep chunks (one 64-deep tile per wave)
+inline void wq_split(int bits, int M, int N, int K, int* S, int* cpb) {
+  sk_split_plan(wq_cw(bits), WQ_KC, bits, M, N, K, S, cpb);
 }
-
-// wq_split for the grouped product, from (bits, Ntok, k, X, N, K) alone: min(X, Ntok * k) experts count as active (the
-// blocks of the others leave at once), and the partials of the Ntok * k live rows are weighed against those experts'
-// weight bytes
-void wq_split_grouped(int bits, int Ntok, int k, int X, int N, int K, int* S, int* cpb) {
-  const int nbk = (N + wq_cw(bits) - 1) / wq_cw(bits);
-  const int NC = ((K + WQ_KT - 1) / WQ_KT + 3) / 4;
-  const int A = Ntok * k, active = X < A ? X : A;
-  const long long blocks = (long long)nbk * active;
-  long long s = (512 + blocks - 1) / blocks;
-  const long long cap = (long long)active * K * bits / (64LL * A);
-  if (s > cap) s = cap;
-  if (s > NC) s = NC;
-  if (s < 1) s = 1;
-  *cpb = (NC + (int)s - 1) / (int)s;
-  *S = (NC + *cpb - 1) / *cpb;
+// wq_split for the grouped product, from (bits, Ntok, k, X, N, K) alone
+inline void wq_split_grouped(int bits, int Ntok, int k, int X, int N, int K, int* S, int* cpb) {
+  sk_split_plan_grouped(wq_cw(bits), WQ_KC, bits, Ntok, k, X, N, K, S, cpb);
 }
 
 inline bool wq_grouped_ok(int bits, int Ntok, int k, int X, long long N, long long K) {
-  return wq_shape_ok(bits, K, N) && Ntok >= 1 && Ntok <= 64 && k >= 1 && k <= 8 && X >= 1 && X <= 64 && k <= X;
+  return wq_shape_ok(bits, K, N) && sk_routing_ok(Ntok, k, X);
 }
 
 }  // namespace
@@ -529,7 +364,7 @@ DL4J_API int dl4j_wq_packed_bytes(int bits, long long K, long long N, long long*
 // W [K, N] (dtype 1 bf16 / 2 fp16, element strides sk, sn) -> codes, scales (16-byte aligned, dl4j_wq_packed_bytes).
 DL4J_API int dl4j_wq_quantize(int bits, int dtype, const void* W, long long sk, long long sn, long long K, long long N,
                               void* codes, void* scales, hipStream_t s) {
-  if (!wq_shape_ok(bits, K, N) || !W || !wq_al16(codes) || !wq_al16(scales) || (dtype != 1 && dtype != 2)) return -1;
+  if (!wq_shape_ok(bits, K, N) || !W || !sk_al16(codes) || !sk_al16(scales) || (dtype != 1 && dtype != 2)) return -1;
   const int KTn = (int)((K + WQ_KT - 1) / WQ_KT);
   const long long tiles = (N + wq_cw(bits) - 1) / wq_cw(bits) * KTn;
   const dim3 grid((unsigned)((tiles + 3) / 4));
@@ -546,7 +381,7 @@ DL4J_API int dl4j_wq_quantize(int bits, int dtype, const void* W, long long sk, 
 // packed -> out [K, N] contiguous in dtype (1 bf16 / 2 fp16).
 DL4J_API int dl4j_wq_dequant(int bits, int dtype, const void* codes, const void* scales, long long K, long long N,
                              void* out, hipStream_t s) {
-  if (!wq_shape_ok(bits, K, N) || !out || !wq_al16(codes) || !wq_al16(scales) || (dtype != 1 && dtype != 2)) return -1;
+  if (!wq_shape_ok(bits, K, N) || !out || !sk_al16(codes) || !sk_al16(scales) || (dtype != 1 && dtype != 2)) return -1;
   const int KTn = (int)((K + WQ_KT - 1) / WQ_KT);
   const long long tiles = (N + wq_cw(bits) - 1) / wq_cw(bits) * KTn;
   const dim3 grid((unsigned)((tiles + 3) / 4));
@@ -566,8 +401,7 @@ DL4J_API long long dl4j_wq_gemm_workspace(int bits, int M, long long N, long lon
   if (!wq_shape_ok(bits, K, N) || M < 1 || M > 64) return -1;
   int S, cpb;
   wq_split(bits, M, (int)N, (int)K, &S, &cpb);
-  const long long Np = (N + wq_cw(bits) - 1) / wq_cw(bits) * wq_cw(bits);
-  return S > 1 ? (long long)S * M * Np : 0;
+  return sk_ws_floats(S, M, N, wq_cw(bits));
 }
 
 // out [M, ldo] = act(x [M, ldx] · deq(codes, scales) + bias + beta·out), 1 <= M <= 64. dtype 1 bf16 / 2 fp16 (x and
@@ -576,17 +410,17 @@ DL4J_API long long dl4j_wq_gemm_workspace(int bits, int M, long long N, long lon
 DL4J_API int dl4j_wq_gemm(int bits, int dtype, const void* x, long long ldx, int M, long long N, long long K,
                           const void* codes, const void* scales, void* out, long long ldo, const void* bias,
                           int bias_dt, int beta, int act, void* ws, hipStream_t s) {
-  if (!wq_shape_ok(bits, K, N) || M < 1 || M > 64 || (dtype != 1 && dtype != 2)) return -1;
-  if (!wq_al16(x) || ldx % 8 != 0 || ldx < K || !wq_al16(codes) || !wq_al16(scales) || !out || ldo < N) return -1;
-  if ((act != 0 && act != 4) || (beta != 0 && beta != 1) || bias_dt < 0 || bias_dt > 2) return -1;
+  if (!wq_shape_ok(bits, K, N) || !sk_dense_ok(M, beta, bias_dt) || !sk_operands_ok(dtype, x, ldx, K, out, ldo, N, act))
+    return -1;
+  if (!sk_al16(codes) || !sk_al16(scales)) return -1;
   int S, cpb;
   wq_split(bits, M, (int)N, (int)K, &S, &cpb);
-  if (S > 1 && !wq_al16(ws)) return -1;
+  if (S > 1 && !sk_al16(ws)) return -1;
   const int KTn = (int)((K + WQ_KT - 1) / WQ_KT), cw = wq_cw(bits);
   const int nbk = (int)((N + cw - 1) / cw);
-  const WqEpi epi{out, bias, (int)ldo, bias_dt, beta, act};
+  const SkEpi epi{out, bias, (int)ldo, bias_dt, beta, act};
   const dim3 grid((unsigned)nbk, (unsigned)S);
-  const int mf = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+  const int mf = sk_mf(M);
 #define L(B, T, F) hipLaunchKernelGGL((wq_gemm_kernel<B, T, F>), grid, dim3(256), 0, s, (const uint4*)codes,      \
                                       (const unsigned char*)scales, (const T*)x, (int)ldx, M, (int)N, (int)K, KTn, \
                                       cpb, (float*)ws, epi)
@@ -597,13 +431,8 @@ DL4J_API int dl4j_wq_gemm(int bits, int dtype, const void* x, long long ldx, int
   else LM(4, _Float16);
 #undef LM
 #undef L
-  int rc = (int)hipGetLastError();
-  if (rc != 0 || S == 1) return rc;
-  const int Np = nbk * cw;
-  const dim3 mg((unsigned)(((long long)M * (Np / 4) + 255) / 256));
-  if (dtype == 1) hipLaunchKernelGGL(wq_merge_kernel<__bf16>, mg, dim3(256), 0, s, (const float*)ws, S, M, (int)N, Np, epi);
-  else hipLaunchKernelGGL(wq_merge_kernel<_Float16>, mg, dim3(256), 0, s, (const float*)ws, S, M, (int)N, Np, epi);
-  return (int)hipGetLastError();
+  const int rc = (int)hipGetLastError();
+  return rc != 0 || S == 1 ? rc : sk_merge(dtype, ws, S, M, (int)N, nbk * cw, epi, s);
 }
 
 // Floats of split-K workspace dl4j_wq_gemm_grouped needs for (bits, Ntok, k, X, N, K): 0 when the product runs
@@ -612,8 +441,7 @@ DL4J_API long long dl4j_wq_gemm_grouped_workspace(int bits, int Ntok, int k, int
   if (!wq_grouped_ok(bits, Ntok, k, X, N, K)) return -1;
   int S, cpb;
   wq_split_grouped(bits, Ntok, k, X, (int)N, (int)K, &S, &cpb);
-  const long long Np = (N + wq_cw(bits) - 1) / wq_cw(bits) * wq_cw(bits);
-  return S > 1 ? (long long)S * Ntok * k * Np : 0;
+  return sk_ws_floats(S, (long long)Ntok * k, N, wq_cw(bits));
 }
 
 // The experts' products of a mixture-of-experts step of Ntok <= 64 tokens on X packed matrices [K, N] (expert e's codes
@@ -629,23 +457,20 @@ DL4J_API int dl4j_wq_gemm_grouped(int bits, int dtype, const void* x, long long 
                                   long long code_stride, long long scale_stride, const int* cnt, const int* off,
                                   const int* src_of, void* out, long long ldo, const float* bias, int act, void* ws,
                                   hipStream_t s) {
-  if (!wq_grouped_ok(bits, Ntok, k, X, N, K) || (dtype != 1 && dtype != 2) || (gather != 0 && gather != 1)) return -1;
+  if (!wq_grouped_ok(bits, Ntok, k, X, N, K) || !sk_operands_ok(dtype, x, ldx, K, out, ldo, N, act)) return -1;
+  if (!sk_plan_ok(gather, Ntok, k, Rcap, cnt, off, src_of, bias) || !sk_al16(codes) || !sk_al16(scales)) return -1;
   long long cb, sb;
   dl4j_wq_packed_bytes(bits, K, N, &cb, &sb);
   if (code_stride < cb || code_stride % 16 || scale_stride < sb || scale_stride % 16) return -1;
-  if (!wq_al16(x) || ldx % 8 != 0 || ldx < K || ldx > 0x7fffffffLL || !wq_al16(codes) || !wq_al16(scales)) return -1;
-  if (!out || ldo < N || ldo > 0x7fffffffLL || Rcap < (long long)Ntok * k || Rcap > 0x7fffffffLL) return -1;
-  const auto al4 = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
-  if (!al4(cnt) || !al4(off) || (gather && !al4(src_of)) || (bias && !al4(bias)) || (act != 0 && act != 4)) return -1;
   int S, cpb;
   wq_split_grouped(bits, Ntok, k, X, (int)N, (int)K, &S, &cpb);
-  if (S > 1 && !wq_al16(ws)) return -1;
+  if (S > 1 && !sk_al16(ws)) return -1;
   const int KTn = (int)((K + WQ_KT - 1) / WQ_KT), cw = wq_cw(bits);
   const int nbk = (int)((N + cw - 1) / cw);
-  const WqEpi epi{out, bias, (int)ldo, 0, 0, act};
-  const WqPlan plan{cnt, off, src_of, Ntok, k, X, Ntok * k, Rcap};
+  const SkEpi epi{out, bias, (int)ldo, 0, 0, act};
+  const SkPlan plan{cnt, off, src_of, Ntok, k, X, Ntok * k, Rcap};
   const dim3 grid((unsigned)nbk, (unsigned)X, (unsigned)S);
-  const int mf = Ntok <= 16 ? 1 : (Ntok <= 32 ? 2 : 4);
+  const int mf = sk_mf(Ntok);
 #define L(B, T, F, G) hipLaunchKernelGGL((wq_gemm_grouped_kernel<B, T, F, G>), grid, dim3(256), 0, s,                \
                                          (const uint4*)codes, (const unsigned char*)scales, code_stride / 16,        \
                                          scale_stride, (const T*)x, (int)ldx, plan, (int)N, (int)K, KTn, cpb,        \
@@ -659,15 +484,6 @@ DL4J_API int dl4j_wq_gemm_grouped(int bits, int dtype, const void* x, long long 
 #undef LM
 #undef LG
 #undef L
-  int rc = (int)hipGetLastError();
-  if (rc != 0 || S == 1) return rc;
-  const int Np = nbk * cw;
-  const dim3 mg((unsigned)(((long long)plan.A * (Np / 4) + 255) / 256));
-  if (dtype == 1)
-    hipLaunchKernelGGL(wq_merge_grouped_kernel<__bf16>, mg, dim3(256), 0, s, (const float*)ws, S, plan, mf * 16, (int)N,
-                       Np, epi);
-  else
-    hipLaunchKernelGGL(wq_merge_grouped_kernel<_Float16>, mg, dim3(256), 0, s, (const float*)ws, S, plan, mf * 16,
-                       (int)N, Np, epi);
-  return (int)hipGetLastError();
+  const int rc = (int)hipGetLastError();
+  return rc != 0 || S == 1 ? rc : sk_merge_grouped(dtype, ws, S, plan, (int)N, nbk * cw, epi, s);
 }

@@ -227,6 +227,58 @@ def test_wq_gemm_grouped(fmt, dt, gather):
                               fmt, dt, K, N, Ntok, kind, gather, bool((i + j) & 1), f"wq grouped {fmt}")
 
 
+# ------------------------------------------------------------------------- one expert: the grouped product IS the dense
+def _one_expert(Ntok, K, dt):
+    """Random (not exact: another summation order would show) x [Ntok, K] and the expert-sorted buffer of the plan
+    moe_route makes of [Ntok, 1] logits: (x, sorted x, plan, the live rows off[0] .. off[0] + Ntok - 1)."""
+    x = (torch.randn(Ntok, K, generator=EO.gen("one expert x", Ntok, K)) * 0.5).to(dt).to(DEV)
+    plan, _ = TN.moe_route(torch.zeros(Ntok, 1, device=DEV), 1)
+    assert plan.cnt.cpu().tolist() == [Ntok]
+    live = slice(int(plan.off[0]), int(plan.off[0]) + Ntok)
+    xs = torch.full((plan.rows, K), NAN, dtype=dt, device=DEV)
+    xs[live] = x[plan.src_of[live].long()]                                  # k = 1: the assignment is the token
+    return x, xs, plan, live
+
+
+ONE_EXPERT = {"skinny": ((3, 96, 77, False), (17, 96, 77, False), (64, 96, 77, False), (3, 3072, 80, True)),
+              "wq": ((3, 96, 77, False), (17, 96, 77, False), (64, 96, 77, False), (3, 288, 40, True))}
+
+
+@pytest.mark.parametrize("dt", DTS, ids=IDS)
+@pytest.mark.parametrize("family,how", [("skinny", 4), ("skinny", 8), ("wq", "fp8"), ("wq", "fp4")],
+                         ids=["width4", "width8", "fp8", "fp4"])
+def test_grouped_of_one_expert_is_the_dense_product(family, how, dt):
+    """X = 1, k = 1, a sorted plan, an fp32 bias, no activation: the live rows of skinny_gemm_grouped / wq_gemm_grouped
+    are the rows of skinny_gemm / wq_gemm on the same weight bytes, bit for bit: one block body, one epilogue, one
+    merge and one split rule per family. The dense and the grouped workspace queries agree at every case, so the two
+    run the same geometry; the last case of each family splits K (asserted)."""
+    lib = TN._lib()
+    for Ntok, K, N, split in ONE_EXPERT[family]:
+        g = EO.gen("one expert", family, how, Ntok, K, N)
+        w = torch.randn(K, N, generator=g) * 0.1
+        bias = torch.randn(N, generator=g).to(DEV)
+        x, xs, plan, live = _one_expert(Ntok, K, dt)
+        if family == "skinny":
+            wg = _framed(w, dt)
+            sizes = (lib.dl4j_skinny_gemm_workspace(how, Ntok, N, K, wg.stride(0), wg.stride(1)),
+                     lib.dl4j_skinny_gemm_grouped_workspace(how, Ntok, 1, 1, N, K))
+            dense = lambda: TN.skinny_gemm(x, wg, bias, None, width=how)  # noqa: E731
+            grouped = lambda: TN.skinny_gemm_grouped(xs, wg.unsqueeze(0), bias, plan, False, width=how)  # noqa: E731
+        else:
+            bits, qw = TN.WQ_FORMATS[how], TN.wq_quantize(w.to(dt).to(DEV), how)
+            qe = TN.QuantExperts(how, 1, K, N, qw.codes.unsqueeze(0), qw.scales.unsqueeze(0))
+            sizes = (lib.dl4j_wq_gemm_workspace(bits, Ntok, N, K),
+                     lib.dl4j_wq_gemm_grouped_workspace(bits, Ntok, 1, 1, N, K))
+            dense = lambda: TN.wq_gemm(x, qw, bias)  # noqa: E731
+            grouped = lambda: TN.wq_gemm_grouped(xs, qe, bias, plan, False)  # noqa: E731
+        what = f"{family} {how} {dt} Ntok={Ntok} K={K} N={N}"
+        assert sizes[0] == sizes[1] and (sizes[0] > 0) == split, f"{what}: workspaces {sizes}"
+        fallback.reset()
+        d, r = dense(), grouped()
+        assert d is not None and r is not None and fallback.count() == 0, f"{what}: {fallback.summary()}"
+        _same_bits(r[live], d.cpu(), what)
+
+
 # ------------------------------------------------------------------------------------------------ GELU epilogues
 # max |gelu_f(z) - GELU(z)| of csrc/mfma_tile.h's device function over fp32 z in [-8, 8], measured on MI355X by
 # _device_gelu_error below against fp64 GELU of the same fp32 inputs: GELU_F_MEASURED. The tests allow twice that.
